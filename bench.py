@@ -6,13 +6,20 @@ colour lookup -> Renderer_ours MLP -> alpha compositing) over one batch of 1024 
 config 2 ("DTU scan1, 3 views, 128 planes, 1024 rays x 128 samples, fp32, 1 MI355X"): synthetic 3-view
 512x640 inputs, pad 24 => neural volume 128x176x208x8, the shipped checkpoint's weights (tests/golden) or
 seeded random weights.  Inputs are resident in HBM before the timed region.  The scene encode (plane sweep +
-CostRegNet, once per scene) is timed separately and reported in `encode_ms`.
+CostRegNet, once per scene) is timed separately and reported in `encode_ms` (--full).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 For N > 1 the driver launches one rank per GPU via torch.distributed.run; rays shard across ranks with no
 data-path collective (weak scaling: every rank renders its own 1024-ray batches of the same scene).
 
-Prints ONE JSON line (rank 0).  Extra objects:
+Prints ONE JSON line (rank 0).  A plain run sets up (scene, one encode of the volume, ray batches), warms up, times the
+K steps and prints the headline (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, ...).
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step returned (rgb_map, input_feat, weights,
+depth_map, alpha of `rendering()` and the raw MLP output it keeps in `rendering.last_raw`) as DIR/<name>.npy, float32;
+the inputs are seeded, so two builds run with the same arguments can be compared output for output.
+--full adds everything beyond the headline (bench_extras.py): the encode timings (default, bf16 and fp32 conv0), the
+per-kernel objects below, the CPU baseline, the end-to-end frame / training-step extras and, at N > 1, the
+collective-carrying legs.  Extra objects of --full:
   roofline      dominant kernel (fused MLP, MFMA-bound): achieved = 251 392 FLOP/sample x samples per launch
                 / average launch duration measured with HIP events on the launch stream
   rooflines     same for the HBM-bound gathers (volume lookup 300 B/sample - the kernel north_star puts the
@@ -36,17 +43,22 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--cpu-batches", type=int, default=20, help="CPU-oracle batches timed for cpu_baseline (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline line: encode timings, per-kernel rooflines, CPU baseline and parity, "
+                         "the end-to-end frame / training-step extras and, at N > 1, the collective-carrying legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32; rank 0)")
+    ap.add_argument("--cpu-batches", type=int, default=20, help="CPU-oracle batches timed for cpu_baseline (0 = skip; --full)")
     ap.add_argument("--mlp-precision", default="fp32", choices=["fp32", "bf16", "bf16x3", "bf16x6", "fp16x3"],
                     help="matrix-core arithmetic of the timed MLP (default fp32 = the headline; the others are the opt-in modes)")
     ap.add_argument("--settle-ms", type=float, default=100.0,
                     help="untimed steps of the same workload run before the W warmup steps until the GPU clocks have left the idle state")
-    ap.add_argument("--no-extras", action="store_true", help="skip the end-to-end frame / training-step timings")
+    ap.add_argument("--no-extras", action="store_true", help="skip the end-to-end frame / training-step timings (--full)")
     ap.add_argument("--shared-gpu-dry-run", action="store_true",
                     help="plumbing check for a 1-GPU box: --gpus N ranks all on cuda:0, collectives over gloo (RCCL refuses several ranks per device); runs the "
                          "torch.distributed.run re-exec and the collective-carrying legs end to end and prints NO headline (no metric / value keys)")
     ap.add_argument("--multi-gpu-legs", action="store_true", help="run the collective-carrying legs (tile-parallel frame, DP training step) "
-                                                                  "also at N = 1 (they always run at N > 1)")
+                                                                  "also at N = 1 (at N > 1 they run with --full)")
     return ap.parse_args()
 
 def self_launch(a):
@@ -71,6 +83,8 @@ def main():
     a = parse()
     if a.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if a.steps < 1 or a.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs an MI355X (no CPU fallback exists for the product path)")
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
@@ -133,7 +147,10 @@ def main():
     except ImportError:
         enc_ready = False
     encode_ms_bf16 = encode_ms_h3 = None
-    if enc_ready:
+    if enc_ready and not a.full:
+        vol, _ = encoder.bench_encode(rig, dev, PAD, iters=1)     # the headline's volume: the same encode, once (its timings are --full's)
+        volume_src = "mvsnet-encode"
+    elif enc_ready:
         vol, encode_ms = encoder.bench_encode(rig, dev, PAD)
         encode_ms["conv0_arithmetic"] = ("guarded fp16x3 (the default of a no-grad encode): two fp16 pieces per operand, x0*w0 + x0*w1 + x1*w0 on v_mfma_f32_16x16x32_f16, fp32 "
                                          "accumulation; a cost value or weight outside fp16's range trips a device-side guard and the fp32 sweep + fp32-MFMA conv0 enqueued behind "
@@ -187,13 +204,18 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        for i in range(a.steps):
+        for i in range(a.steps - 1):
             step(i)
+        last = step(a.steps - 1)              # the last timed step's outputs are kept for --dump-outputs
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
         dt = time.perf_counter() - t0
         gc.enable()
+    last_raw = renderer.rendering.last_raw
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, last, last_raw)
+    del last, last_raw
     dt_rank = dt
     rccl_ranks_seen, per_rank = 1, [round(a.steps * N_RAYS / dt_rank, 1)]
     if world > 1:
@@ -216,12 +238,26 @@ def main():
     ops.set_mlp_precision("fp32")
     # ---------------- N > 1: the collective-carrying paths (every rank takes part; rank 0 reports)
     multi = None
-    if (world > 1 and not a.no_extras) or a.multi_gpu_legs:
+    if (world > 1 and a.full and not a.no_extras) or a.multi_gpu_legs:
         from bench_extras import multi_gpu_legs
         multi = multi_gpu_legs(dev, rank, world)
-    # ---------------- per-kernel launch durations (HIP events on the launch stream), rank 0
+    head = {
+        "metric": "rendered rays/sec (1024-ray batch, 128 samples)", "value": round(rays_per_s, 1), "unit": "rays/s",
+        "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(dt / a.steps * 1e3, 4),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "rccl_ranks_seen": rccl_ranks_seen, "backend": (dist.get_backend() if world > 1 else None), "per_rank_rays_per_s": per_rank,
+        "dtype": {"fp32": "f32", "bf16": "bf16", "bf16x3": "bf16x3 (split-bf16 products, fp32 accumulate)",
+                  "bf16x6": "bf16x6 (fp32 emulated by split-bf16 products, fp32 accumulate)",
+                  "fp16x3": "fp16x3 (fp32 emulated by split-fp16 products, fp32 accumulate)"}[a.mlp_precision], "data": "synthetic",
+        "config": {"workload": "config 2: 3 source views 512x640, 128 depth planes, pad 24 (volume 128x176x208x8), "
+                               f"1024 rays x 128 samples per step, MLP arithmetic {a.mlp_precision}, render-only (volume pre-built)",
+                   "weights": "mvsnerf-v0 checkpoint", "volume": volume_src, "rays_per_step_per_gpu": N_RAYS,
+                   "parallelism": f"ray-sharded x{world}, no data-path collective",
+                   "clock_settle_ms": a.settle_ms},
+    }
+    # ---------------- --full: per-kernel launch durations (HIP events on the launch stream), CPU baseline, extras; rank 0
     roof, roofs, cpu, o = None, [], None, None
-    if rank == 0:
+    if rank == 0 and a.full:
         with torch.no_grad():
             pts, ndc, z, ro, rdir = batches[0]
             vol_cl = ops.channels_last_volume(vol)
@@ -266,25 +302,31 @@ def main():
         if not a.no_extras and world == 1:
             extras = bench_extras.single_gpu_extras(dict(locals()))
         flat = bench_extras.flat_scalars(encode_ms, extras, multi)     # the numbers beyond the headline as top-level scalars (a driver that keeps only flat keys keeps these)
-        print(json.dumps({
-            "metric": "rendered rays/sec (1024-ray batch, 128 samples)", "value": round(rays_per_s, 1), "unit": "rays/s",
-            "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(dt / a.steps * 1e3, 4),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "rccl_ranks_seen": rccl_ranks_seen, "backend": (dist.get_backend() if world > 1 else None), "per_rank_rays_per_s": per_rank,
-            "dtype": {"fp32": "f32", "bf16": "bf16", "bf16x3": "bf16x3 (split-bf16 products, fp32 accumulate)",
-                      "bf16x6": "bf16x6 (fp32 emulated by split-bf16 products, fp32 accumulate)",
-                      "fp16x3": "fp16x3 (fp32 emulated by split-fp16 products, fp32 accumulate)"}[a.mlp_precision], "data": "synthetic",
-            "config": {"workload": "config 2: 3 source views 512x640, 128 depth planes, pad 24 (volume 128x176x208x8), "
-                                   f"1024 rays x 128 samples per step, MLP arithmetic {a.mlp_precision}, render-only (volume pre-built)",
-                       "weights": "mvsnerf-v0 checkpoint", "volume": volume_src, "rays_per_step_per_gpu": N_RAYS,
-                       "parallelism": f"ray-sharded x{world}, no data-path collective",
-                       "clock_settle_ms": a.settle_ms},
+        head.update({
             "encode_ms": encode_ms, "encode_ms_bf16_conv0": encode_ms_bf16, "encode_ms_fp32_conv0": encode_ms_h3,
             "roofline": roof, "rooflines": roofs, "cpu_baseline": cpu, **flat, "multi_gpu": multi, "extras": extras,
-        }))
+        })
+    if rank == 0:
+        print(json.dumps(head))
     if world > 1:
         dist.barrier()                    # rank 0 was alone in the per-kernel section above: nobody tears the group down before it is back
         dist.destroy_process_group()
+
+
+def dump_outputs(d, out, raw):
+    """--dump-outputs: what the last timed step returned (renderer.rendering: rgb_map, input_feat, weights, depth_map, alpha) and the raw MLP
+    output it kept in rendering.last_raw, one float32 DIR/<name>.npy each (about 14 MB in all at the benchmark's shapes)."""
+    import numpy as np
+    names = ("rgb_map", "input_feat", "weights", "depth_map", "alpha")
+    arrays = {n: t for n, t in zip(names, out) if torch.is_tensor(t)}
+    arrays["raw"] = raw
+    arrays = {n: t.detach().float().cpu().numpy() for n, t in arrays.items()}
+    total = sum(x.nbytes for x in arrays.values())
+    if total > 64 << 20:
+        raise SystemExit(f"--dump-outputs: {total} bytes of outputs, more than the 64 MB a dump may hold")
+    os.makedirs(d, exist_ok=True)
+    for n, x in arrays.items():
+        np.save(os.path.join(d, n + ".npy"), x)
 
 
 if __name__ == "__main__":

@@ -11,15 +11,15 @@ export TMPDIR=/tmp
 O=gpurun_out/r6_final
 rm -rf $O; mkdir -p $O
 R="$GRAFT_REPO_ROOT"
-(cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/bench_trace -o b -- python $R/bench.py > $R/$O/bench_under_rocprof.log 2>&1)
+(cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/bench_trace -o b -- python $R/bench.py --full > $R/$O/bench_under_rocprof.log 2>&1)
 grep "^{\"metric\"" $O/bench_under_rocprof.log | tail -1 > $O/r06_bench_under_rocprof.json
 find $O/bench_trace -name "*kernel_stats.csv" -exec cp {} $O/r06_bench_kernel_stats.csv \;
 rm -rf $O/bench_trace
 PASSES=("FETCH_SIZE" "WRITE_SIZE" "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES GRBM_GUI_ACTIVE SQ_WAVE_CYCLES SQ_WAIT_INST_ANY" "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_VMEM SQ_ACTIVE_INST_ANY SQ_INSTS_VALU_MFMA_MOPS_F32")
 for pass in "${PASSES[@]}"; do
   tag=$(echo $pass | tr ' ' '_' | cut -c1-40)
-  (cd /tmp && rocprofv3 --pmc $pass --kernel-trace --output-format csv -d $R/$O/pmc/$tag -o p -- python $R/bench.py --steps 20 --warmup 3 --cpu-batches 0 --no-extras > $R/$O/pmc_$tag.log 2>&1)
-  (cd /tmp && rocprofv3 --pmc $pass --kernel-trace --output-format csv -d $R/$O/pmc/h3_$tag -o p -- python $R/bench.py --steps 20 --warmup 3 --cpu-batches 0 --no-extras --mlp-precision fp16x3 > $R/$O/pmc_h3_$tag.log 2>&1)
+  (cd /tmp && rocprofv3 --pmc $pass --kernel-trace --output-format csv -d $R/$O/pmc/$tag -o p -- python $R/bench.py --full --steps 20 --warmup 3 --cpu-batches 0 --no-extras > $R/$O/pmc_$tag.log 2>&1)
+  (cd /tmp && rocprofv3 --pmc $pass --kernel-trace --output-format csv -d $R/$O/pmc/h3_$tag -o p -- python $R/bench.py --full --steps 20 --warmup 3 --cpu-batches 0 --no-extras --mlp-precision fp16x3 > $R/$O/pmc_h3_$tag.log 2>&1)
   (cd /tmp && rocprofv3 --pmc $pass --kernel-trace --output-format csv -d $R/$O/pmc_enc/$tag -o p -- python $R/scratch/r6/enc_only.py > $R/$O/pmc_enc_$tag.log 2>&1)
   (cd /tmp && rocprofv3 --pmc $pass --kernel-trace --output-format csv -d $R/$O/pmc_train/$tag -o p -- python $R/scratch/r6/train_prof.py amp 3 > $R/$O/pmc_train_$tag.log 2>&1)
 done
@@ -77,6 +77,6 @@ find $O/tr_enc -name "*kernel_stats.csv" -exec cp {} $O/r06_encode_kernel_stats.
 rm -rf $O/tr_enc
 for m in fp32 amp; do python scratch/r6/train_prof.py $m 10 2>&1 | grep -v amdgpu.ids >> $O/r06_train_step_ms.txt; done
 cp $O/r06_pmc_summary.json profiles/r06_pmc_summary.json      # (on the box) so that the bench line below reports the traffic measured on THESE kernel sources
-python bench.py > $O/r06_bench.json 2> $O/r06_bench.err
+python bench.py --full > $O/r06_bench.json 2> $O/r06_bench.err
 tail -c 600 $O/r06_bench.json; cat $O/r06_train_step_ms.txt
 ls -la $O

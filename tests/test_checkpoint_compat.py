@@ -1,16 +1,25 @@
 """CPU: the reference's shipped checkpoint loads into this package's modules UNCHANGED (same state_dict keys and shapes), through
-the reference's own entry point create_nerf_mvs(args) with args.ckpt set.  The .tar only exists in the authoring container
-(/root/reference); on machines without it the key/shape contract is checked against the committed weights fixture instead."""
+the reference's own entry point create_nerf_mvs(args) with args.ckpt set.  The .tar itself is not part of the repository: the test
+writes it again, in the reference's layout, from the committed weights fixture, which holds every tensor of it bit for bit."""
+import collections
 import os
 import types
 
 import numpy as np
-import pytest
 import torch
 
-from tests.util import load_weights
+from tests.util import GOLDEN, load_weights
 
-REF_CKPT = "/root/reference/ckpts/mvsnerf-v0.tar"
+# ckpts/mvsnerf-v0.tar of the reference holds global_step and two state dicts: the fixture's mlp/* and mvs/* arrays, in the fixture's order
+REF_CKPT_GLOBAL_STEP = 181104
+
+
+def _write_reference_checkpoint(path):
+    z = np.load(os.path.join(GOLDEN, "mvsnerf_v0_weights.npz"))
+
+    def sd(prefix):
+        return collections.OrderedDict((k[len(prefix):], torch.from_numpy(z[k])) for k in z.files if k.startswith(prefix))
+    torch.save({"global_step": REF_CKPT_GLOBAL_STEP, "network_fn_state_dict": sd("mlp/"), "network_mvs_state_dict": sd("mvs/")}, path)
 
 
 def _args(ckpt):
@@ -33,13 +42,15 @@ def test_state_dict_contract_matches_the_fixture():
     assert list(models.RefVolume(torch.zeros(1, 8, 8, 8, 8)).state_dict()) == ["feat_volume"]
 
 
-@pytest.mark.skipif(not os.path.exists(REF_CKPT), reason="reference checkpoint only exists in the authoring container")
-def test_reference_checkpoint_loads_through_create_nerf_mvs():
+def test_reference_checkpoint_loads_through_create_nerf_mvs(tmp_path):
     from mvsnerf_amd import models
-    kw_train, kw_test, start, grad_vars = models.create_nerf_mvs(_args(REF_CKPT), use_mvs=True, dir_embedder=False, pts_embedder=True)
+    ref_ckpt = str(tmp_path / "mvsnerf-v0.tar")
+    _write_reference_checkpoint(ref_ckpt)
+    kw_train, kw_test, start, grad_vars = models.create_nerf_mvs(_args(ref_ckpt), use_mvs=True, dir_embedder=False, pts_embedder=True)
     assert {"network_query_fn", "perturb", "N_importance", "network_fine", "N_samples", "network_fn", "network_mvs", "use_viewdirs",
             "white_bkgd", "raw_noise_std"} <= set(kw_train)
-    ck = torch.load(REF_CKPT, map_location="cpu", weights_only=False)
+    ck = torch.load(ref_ckpt, map_location="cpu", weights_only=False)
+    assert list(ck) == ["global_step", "network_fn_state_dict", "network_mvs_state_dict"]
     mlp_sd, mvs_sd = load_weights()
     for k, v in kw_train["network_fn"].state_dict().items():
         assert torch.equal(v.cpu(), ck["network_fn_state_dict"][k]) and np.array_equal(v.cpu().numpy(), mlp_sd[k].numpy())
