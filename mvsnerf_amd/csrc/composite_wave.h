@@ -1,7 +1,7 @@
 // raw2alpha + raw2outputs (renderer.py:18-26, 65-92) for ONE ray by one 64-lane wave.  Separate multiplies and adds with
 // contraction off (the reference sums products it has rounded), so the result does not depend on the surrounding code.
-// (Measured and dropped: calling this from the epilogue of the MLP kernel when a workgroup holds one whole ray, S == 128 -
-// bit-identical, one launch less, but the serial tail of the compositing wave costs the MLP kernel the 5 us the launch saved.)
+// Also the epilogue of the one-launch ray march (raymarch_fused_kernel, mlp.hip) when a tile holds whole rays: with z staged in LDS its serial
+// tail costs that kernel ~3 us of the ~5 us the compositing launch took (CHANGELOG round 7; round 1 had measured it as a wash).
 #pragma once
 #include "common.h"
 

@@ -10,6 +10,8 @@
 #include "mlp_layout.h"
 #include "lds_dma.h"
 #include "knobs.h"
+#include "sample_dev.h"
+#include "composite_wave.h"
 
 using namespace mlp;
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -224,12 +226,95 @@ __device__ __forceinline__ void slab_sync()
     __syncthreads();                                      // ... everybody's have, and everybody left the other buffer
 }
 
+// What the one-launch ray march (raymarch_fused_kernel below) adds to a tile: the lookups that produce its input rows, the view direction
+// and the compositing.  The volume is depth-fastest (MVSNERF_VOL_HWDC) and every offset fits 32 bits (gather_fits_32bit).
+struct RaymarchTileArgs {
+    const float* vol; int D, H, W;
+    const float* img; int V, IH, IW;            // [V][IH][IW][4]
+    const float* w2c; const float* Kmat;        // [V][4][4], [V][3][3]; view 0 is the reference view
+    const float* pts; const float* rays_dir;    // [P][3], [N][3]
+    float* feat; float* dirs_out;               // input_feat [P][F], dirs_tmp [N][3]
+    const float* z; int64_t N; int rays_per_tile;
+    CompositeOut o;
+};
+
+// Prologue of a tile: the arithmetic of gather_fused_kernel<true, true> (sample.hip) for the tile's 128 samples - quad per sample, two passes
+// of 64 samples over the 256 threads, every load of both passes issued before the first is consumed.  The rows go to `stage` (128 x F
+// floats of LDS), from which the MLP lanes take their features and the tile's block of `feat` is written (tile_rows_out).
+__device__ __forceinline__ void tile_lookups(const unsigned tile, const RaymarchTileArgs& a, const float* __restrict__ ndc, int64_t P, int F,
+                                             float* __restrict__ stage)
+{
+#pragma clang fp contract(off)
+    const int tid = threadIdx.x, q = tid & 3;
+    int r[2];
+    bool live[2];
+    unsigned p[2];
+    ZfastTaps zt[2];
+    ColorTap ct[2][2];
+    f32x3 tap[2][2][4];
+    f32x3 nn[2], pp[2];
+#pragma unroll
+    for (int ps = 0; ps < 2; ++ps) {
+        r[ps] = ps * 64 + (tid >> 2);
+        const int64_t p_raw = (int64_t)tile * 128 + r[ps];
+        live[ps] = p_raw < P;
+        p[ps] = (unsigned)(live[ps] ? p_raw : P - 1);
+        nn[ps] = f32x3{ndc[p[ps] * 3 + 0], ndc[p[ps] * 3 + 1], ndc[p[ps] * 3 + 2]};
+        pp[ps] = *reinterpret_cast<const f32x3*>(a.pts + p[ps] * 3);              // one 12-byte load
+    }
+    // this lane's views q and q + 4 (the second one only when V > 4: a uniform branch) are the same in both passes: their matrices travel with
+    // the coordinates.  A lane without a view of its own projects into view V - 1 and does not store: the taps are issued without a
+    // divergent branch, whose join would make the compiler wait for them there.
+    const bool two = a.V > 4;
+    const int vk[2] = {q < a.V ? q : a.V - 1, q + 4 < a.V ? q + 4 : a.V - 1};
+    float Mv[2][12], Kv[2][9];
+#pragma unroll
+    for (int k = 0; k < 2; ++k)
+        if (k == 0 || two) {
+#pragma unroll
+            for (int i = 0; i < 12; ++i) Mv[k][i] = a.w2c[vk[k] * 16 + i];
+#pragma unroll
+            for (int i = 0; i < 9; ++i) Kv[k][i] = a.Kmat[vk[k] * 9 + i];
+        }
+#pragma unroll
+    for (int ps = 0; ps < 2; ++ps) zt[ps] = zfast_taps<true>(a.vol, a.D, a.H, a.W, nn[ps][0], nn[ps][1], nn[ps][2], q);
+#pragma unroll
+    for (int ps = 0; ps < 2; ++ps)
+#pragma unroll
+        for (int k = 0; k < 2; ++k)
+            if (k == 0 || two) {
+                ct[ps][k] = color_project(pp[ps][0], pp[ps][1], pp[ps][2], Mv[k], Kv[k], a.IW, a.IH);
+                color_taps_nhwc4<true, f32x3>(a.img, vk[k], a.IH, a.IW, ct[ps][k], tap[ps][k]);
+            }
+#pragma unroll
+    for (int ps = 0; ps < 2; ++ps) {
+        float* srow = stage + r[ps] * F;
+#pragma unroll
+        for (int k = 0; k < 2; ++k)
+            if ((k == 0 || two) && q + 4 * k < a.V) *reinterpret_cast<f32x4*>(srow + 8 + 16 * k + 4 * q) = color_row(ct[ps][k], tap[ps][k]);
+        const f32x4 acc = zfast_fold_y0_lane(zt[ps]);                             // valid in the y0 lanes
+        if (q < 2) *reinterpret_cast<f32x4*>(srow + q * 4) = acc;
+    }
+}
+
+// The staged rows of the tile's live samples to input_feat, where they form one contiguous block: 16-byte stores issued after the barrier, so
+// that they complete under the first GEMM instead of in front of it.
+__device__ __forceinline__ void tile_rows_out(const unsigned tile, float* __restrict__ feat, const float* __restrict__ stage, int64_t P, int F)
+{
+    const int64_t row0 = (int64_t)tile * 128;
+    const int n4 = (int)(P - row0 < 128 ? P - row0 : 128) * (F / 4);
+    f32x4* dst = reinterpret_cast<f32x4*>(feat + row0 * F);
+    const f32x4* src = reinterpret_cast<const f32x4*>(stage);
+    for (int i = threadIdx.x; i < n4; i += 256) dst[i] = src[i];
+}
+
 // One tile = 128 points = one workgroup's work; `tile` is the workgroup index in the plain kernel and the loop variable of the predicated one below.
-template <bool ALPHA_ONLY, bool SAVE>
+// FUSED (with `fa`): the one-launch ray march - `feat` and `dirs` are not read, the tile produces them; NR > 0: it also composites its rays.
+template <bool ALPHA_ONLY, bool SAVE, bool FUSED = false, int NR = 0>
 __device__ __forceinline__ void mlp_fwd_pipe_tile(
     const unsigned tile, const float* __restrict__ packed, int F, const float* __restrict__ ndc, int ndc_stride,
     const float* __restrict__ feat, int feat_stride, const float* __restrict__ dirs, int dirs_stride,
-    int64_t P, int S, float* __restrict__ raw, float* __restrict__ saved, long long* __restrict__ census)
+    int64_t P, int S, float* __restrict__ raw, float* __restrict__ saved, long long* __restrict__ census, const RaymarchTileArgs* fa = nullptr)
 {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     long long t_start = 0, c_start = 0;
@@ -252,12 +337,40 @@ __device__ __forceinline__ void mlp_fwd_pipe_tile(
     auto save = [&](int slot, float v) { if (SAVE) sv[slot * 64] = v; };
     constexpr int HALF = (int)(ACT_STEPS / 2) * 4 * 64;                   // floats of half a 128x128 layer
 
+    // FUSED: the fragment-ordered vectors are loaded first, all at once (their LDS stores wait until after the lookups), so that no wait for
+    // them also waits for the weight DMA issued behind them
+    constexpr int VEC_PER_THREAD = (V_TOTAL + 255) / 256;
+    float vec_pre[VEC_PER_THREAD];
+    if constexpr (FUSED) {
+#pragma unroll
+        for (int k = 0; k < VEC_PER_THREAD; ++k) vec_pre[k] = tid + 256 * k < V_TOTAL ? packed[L.vec + tid + 256 * k] : 0.0f;
+    }
     slab_dma(buf0, packed + L.biasw, (int)seg_floats(L.fsteps, 4), wave, lane);          // slab 0
-    slab_dma_c<(int)seg_floats(PE_STEPS, 4)>(buf1, packed + L.l0, wave, lane);              // slab 1 (buf1 is free at tile start)
-    for (int i = tid; i < V_TOTAL; i += 256) vec[i] = packed[L.vec + i];
+    // FUSED: the lookups' rows are staged behind slab 0 when they fit there (F <= 28), else in buf1, whose slab then waits for them to be read
+    const bool l0_first = !FUSED || seg_floats(L.fsteps, 4) + 128 * (size_t)F <= SLAB_FLOATS;
+    float* stage = l0_first ? buf0 + seg_floats(L.fsteps, 4) : buf1;
+    if (l0_first) slab_dma_c<(int)seg_floats(PE_STEPS, 4)>(buf1, packed + L.l0, wave, lane);   // slab 1 (buf1 is free at tile start)
+    if constexpr (FUSED) {
+        tile_lookups(tile, *fa, ndc, P, F, stage);
+#pragma unroll
+        for (int k = 0; k < VEC_PER_THREAD; ++k)
+            if (tid + 256 * k < V_TOTAL) vec[tid + 256 * k] = vec_pre[k];
+    } else {
+        for (int i = tid; i < V_TOTAL; i += 256) vec[i] = packed[L.vec + i];
+    }
     const float px = ndc[p * ndc_stride + 0], py = ndc[p * ndc_stride + 1], pz = ndc[p * ndc_stride + 2];
     float fv[MAX_F / 2];
-    {
+    if constexpr (FUSED) {
+        slab_sync();                                                                        // slab 0 and the stage are in LDS
+        const float* fp = stage + (wave * 32 + (lane & 31)) * F + half * (F / 2);
+#pragma unroll
+        for (int i = 0; i < MAX_F / 2; ++i) fv[i] = i < F / 2 ? fp[i] : 0.0f;
+        tile_rows_out(tile, fa->feat, stage, P, F);
+        if (!l0_first) {
+            __syncthreads();                                                                // every wave has its features out of buf1
+            slab_dma_c<(int)seg_floats(PE_STEPS, 4)>(buf1, packed + L.l0, wave, lane);
+        }
+    } else {
         const float* fp = feat + p * feat_stride + half * (F / 2);
 #pragma unroll
         for (int i = 0; i < MAX_F / 2; ++i) fv[i] = i < F / 2 ? fp[i] : 0.0f;
@@ -268,7 +381,7 @@ __device__ __forceinline__ void mlp_fwd_pipe_tile(
     auto hhi = [&](int g, int t) { return h[32 + t]; };
 
     // ---- slab 0: bias = pts_bias(feat)
-    slab_sync();
+    if constexpr (!FUSED) slab_sync();
     stamp();                                                                                // [4] startup done
     {
         f32x16 acc[G][4];
@@ -354,6 +467,16 @@ __device__ __forceinline__ void mlp_fwd_pipe_tile(
         if (live && half == 0) raw[p_raw] = sigma;
         return;
     }
+    // FUSED: the ray's direction and the reference rotation, loaded here so that they land under the feature_linear GEMM
+    float rdir[3] = {0.0f, 0.0f, 0.0f}, rot[11];
+    int64_t ray_of_p = 0;
+    if constexpr (FUSED) {
+        ray_of_p = p / S;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) rdir[c] = fa->rays_dir[ray_of_p * 3 + c];
+#pragma unroll
+        for (int i = 0; i < 11; ++i) rot[i] = fa->w2c[i];
+    }
     // ---- feature_linear: slabs 13 (buf1), 14 (buf0)
     {
         f32x16 acc[G][4];
@@ -368,8 +491,22 @@ __device__ __forceinline__ void mlp_fwd_pipe_tile(
     stamp();                                                                                // [12] feature_linear done
     // ---- views_linears[0] + rgb head: slab 15 (buf1)
     {
+        // compositing in the tile: its 128 z values are one contiguous block, loaded here so that they land under the views GEMM
+        float z_pre = 0.0f;
+        if constexpr (FUSED && NR > 0)
+            if (tid < 128 && (int64_t)tile * 128 + tid < P) z_pre = fa->z[(int64_t)tile * 128 + tid];
         float d0, d1, d2;
-        { const int64_t ray = p / S; d0 = dirs[ray * dirs_stride + 0]; d1 = dirs[ray * dirs_stride + 1]; d2 = dirs[ray * dirs_stride + 2]; }
+        if constexpr (FUSED) {
+            // the ray's view direction in registers: with S > 128 a ray spans tiles, so dirs_tmp is written (by the tile holding the ray's
+            // first sample) and never read back
+            const int64_t ray = ray_of_p;
+            float d[3];
+            dir_feature_of(rdir, rot, 1, d);
+            d0 = d[0]; d1 = d[1]; d2 = d[2];
+            if (live && half == 0 && p_raw == ray * S) { fa->dirs_out[ray * 3 + 0] = d0; fa->dirs_out[ray * 3 + 1] = d1; fa->dirs_out[ray * 3 + 2] = d2; }
+        } else {
+            const int64_t ray = p / S; d0 = dirs[ray * dirs_stride + 0]; d1 = dirs[ray * dirs_stride + 1]; d2 = dirs[ray * dirs_stride + 2];
+        }
         f32x16 acc[G][2];
         slab_sync();
         init_acc<2, G>(acc, vec + V_VIEWS + half * 32);
@@ -394,6 +531,26 @@ __device__ __forceinline__ void mlp_fwd_pipe_tile(
             rgb[c] = 1.0f / (1.0f + expf(-x));
         }
         if (live && half == 0) *reinterpret_cast<f32x4*>(raw + p_raw * 4) = f32x4{rgb[0], rgb[1], rgb[2], sigma};
+        if constexpr (FUSED && NR > 0) {
+            // the tile holds whole rays (128 % S == 0): raw and z staged in buf0 (free since the barrier in front of the views GEMM), then
+            // composite_kernel<NR>'s lane ownership - wave w composites the tile's rays w, w + 4, ...
+            if (half == 0) reinterpret_cast<f32x4*>(buf0)[wave * 32 + (lane & 31)] = f32x4{rgb[0], rgb[1], rgb[2], sigma};
+            float* zs = buf0 + 4 * 128;
+            if (tid < 128) zs[tid] = z_pre;
+            __syncthreads();
+            const f32x4* rs = reinterpret_cast<const f32x4*>(buf0);
+            for (int rl = wave; rl < fa->rays_per_tile; rl += 4) {
+                const int64_t ray = (int64_t)tile * fa->rays_per_tile + rl;
+                if (ray >= fa->N) break;                                                    // wave-uniform
+                f32x4 rv[NR];
+#pragma unroll
+                for (int i = 0; i < NR; ++i) {
+                    const int s = lane * NR + i;
+                    rv[i] = s < S ? rs[rl * S + s] : f32x4{0, 0, 0, 0};
+                }
+                composite_wave<NR>(rv, zs + rl * S, ray, S, lane, fa->o);
+            }
+        }
     }
     if (census && tid == 0) {
         census[tile * 16 + 0] = t_start;
@@ -456,8 +613,56 @@ static int launch_mlp_pipe(const float* packed, int F, const float* ndc, int ndc
     return MVSNERF_OK;
 }
 
-// (The lookups fused into this kernel's prologue were measured in round 2 - 0.2574 ms/step against 0.2551 ms with the separate 11 us gather
-// launch, whose 2048 waves hide the lookup latency that every workgroup's first GEMM would otherwise wait for - and are not built.)
+// ------------------------------------------------------------------------------------------ one-launch ray march
+// mvsnerf_raymarch_fwd's fp32 path in one launch (raymarch.hip): lookups -> MLP -> compositing per 128-sample tile, the same bits as
+// mvsnerf_gather_fwd -> mvsnerf_mlp_fwd -> mvsnerf_composite_fwd.  Measured at config 2: 247.5 us against 255 us for the three launches; the two
+// workgroups of a CU start their tiles together (two rounds of 512), so the lookups are not hidden behind the partner's GEMMs, they are made
+// one round trip deep (tile_lookups).  NR > 0: the tile composites its rays itself (128 % S == 0, NR = ceil(S / 64)).
+template <int NR>
+__global__ __launch_bounds__(256, 2) void raymarch_fused_kernel(const float* __restrict__ packed, int F, const float* __restrict__ ndc, int64_t P, int S,
+                                                                float* __restrict__ raw, RaymarchTileArgs fa)
+{
+    mlp_fwd_pipe_tile<false, false, true, NR>(blockIdx.x, packed, F, ndc, 3, nullptr, F, nullptr, 3, P, S, raw, nullptr, nullptr, &fa);
+}
+
+// Launches the one-launch ray march when it applies (*taken = true), otherwise leaves the batch to the launch sequence (*taken = false):
+// invalid arguments, a DHWC volume or a shape whose offsets need 64 bits go that way - with the sequence's own error codes.  When 128 % S
+// != 0 a tile holds pieces of rays, and the compositing is a separate mvs_composite_fwd launch.
+int mvs_composite_fwd(const float* raw, const float* z, int64_t N, int S, int white_bkgd, float* rgb_map, float* disp, float* acc, float* weights,
+                      float* depth, float* alpha, int* guard, void* stream);                                                                 // composite.hip
+int mvs_raymarch_fused_fwd(const float* vol, int D, int H, int W, int vol_layout, const float* imgs_nhwc4, int V, int IH, int IW, const float* w2c,
+                           const float* K, const float* packed, const float* pts, const float* ndc, const float* z, int64_t N, int S,
+                           const float* rays_dir, float* feat, float* dirs_out, float* raw, int white_bkgd, float* rgb_map, float* disp, float* acc,
+                           float* weights, float* depth, float* alpha, void* stream, bool* taken)
+{
+    *taken = false;
+    const int F = 8 + 4 * V;
+    if (vol_layout != MVSNERF_VOL_HWDC || !vol || !imgs_nhwc4 || !w2c || !K || !packed || !pts || !ndc || !z || !rays_dir || !feat || !dirs_out || !raw) return MVSNERF_OK;
+    if (D < 1 || H < 1 || W < 1 || V < 1 || F > MAX_F || IH < 2 || IW < 2 || N < 1 || S < 1) return MVSNERF_OK;
+    if (!mvs_aligned16(feat) || !mvs_aligned16(vol) || !mvs_aligned16(imgs_nhwc4) || !mvs_aligned16(packed) || !mvs_aligned16(raw)) return MVSNERF_OK;
+    const int64_t P = N * S;
+    if (!gather_fits_32bit(D, H, W, V, IH, IW, P, F)) return MVSNERF_OK;
+    *taken = true;
+    const RaymarchTileArgs fa{vol, D, H, W, imgs_nhwc4, V, IH, IW, w2c, K, pts, rays_dir, feat, dirs_out, z, N, 128 % S == 0 ? 128 / S : 0,
+                              CompositeOut{rgb_map, disp, acc, weights, depth, alpha, white_bkgd, nullptr}};
+    hipStream_t st = (hipStream_t)stream;
+    const size_t lds_bytes = PIPE_LDS_FLOATS * sizeof(float);
+    const unsigned grid = mvs_cdiv(P, 128);
+    static unsigned long long cap[3] = {0, 0, 0};
+#define MVS_FUSED(NR_)                                                                                                                 \
+    do {                                                                                                                               \
+        if (int rc_ = mvs_raise_lds_cap(reinterpret_cast<const void*>(raymarch_fused_kernel<NR_>), (int)lds_bytes, &cap[NR_])) return rc_; \
+        raymarch_fused_kernel<NR_><<<grid, 256, lds_bytes, st>>>(packed, F, ndc, P, S, raw, fa);                                     \
+    } while (0)
+    if (fa.rays_per_tile == 0) MVS_FUSED(0);
+    else if (S <= 64) MVS_FUSED(1);
+    else MVS_FUSED(2);
+#undef MVS_FUSED
+    MVS_LAUNCH_CHECK();
+    if (fa.rays_per_tile == 0)
+        return mvs_composite_fwd(raw, z, N, S, white_bkgd, rgb_map, disp, acc, weights, depth, alpha, nullptr, stream);
+    return MVSNERF_OK;
+}
 
 static int mlp_fwd_checked(const float* packed, int F, const float* ndc, int ndc_stride, const float* feat, int feat_stride,
                            const float* dirs, int dirs_stride, int64_t N, int S, int alpha_only, float* raw, void* stream, long long* census,

@@ -13,6 +13,10 @@ int mvs_mlp_fwd_if(const float* packed, int F, const float* ndc, int ndc_stride,
 int mvs_composite_fwd(const float* raw, const float* z, int64_t N, int S, int white_bkgd, float* rgb_map, float* disp, float* acc, float* weights,
                       float* depth, float* alpha, int* guard, void* stream);                                                                               // composite.hip
 int mvs_guard_consume(int* guard, hipStream_t st);                                                                                                         // encoder.hip
+int mvs_raymarch_fused_fwd(const float* vol, int D, int H, int W, int vol_layout, const float* imgs_nhwc4, int V, int IH, int IW, const float* w2c,
+                           const float* K, const float* packed, const float* pts, const float* ndc, const float* z, int64_t N, int S,
+                           const float* rays_dir, float* feat, float* dirs_out, float* raw, int white_bkgd, float* rgb_map, float* disp, float* acc,
+                           float* weights, float* depth, float* alpha, void* stream, bool* taken);                                                          // mlp.hip
 
 // fp16x3 kernel reporting through guard[0], then the fp32-MFMA kernel predicated on it (same inputs, same output buffer)
 static int mlp_guarded_pair(const void* packed_h, const float* packed_f32, int F, const float* ndc, int ndc_stride, const float* feat, int feat_stride,
@@ -46,6 +50,13 @@ extern "C" int mvsnerf_raymarch_fwd(const mvsnerf_raymarch_args* a, void* stream
     const int F = 8 + 4 * a->V;
     const int64_t P = a->N * a->S;
     int rc;
+    if (a->imgs_nhwc4 && !a->packed_mlp_split && !a->packed_mlp_bf16 && !a->guard) {
+        // fp32 MLP: lookups, MLP and (when a tile holds whole rays) compositing in one launch, when the shapes allow it
+        bool taken;
+        if ((rc = mvs_raymarch_fused_fwd(a->vol, a->D, a->H, a->W, a->vol_layout, a->imgs_nhwc4, a->V, a->IH, a->IW, a->w2c, a->K, a->packed_mlp,
+                                         a->rays_pts, a->rays_ndc, a->z_vals, a->N, a->S, a->rays_dir, a->input_feat, a->dirs_tmp, a->raw, a->white_bkgd,
+                                         a->rgb_map, a->disp, a->acc, a->weights, a->depth, a->alpha, stream, &taken)) || taken) return rc;
+    }
     if (a->imgs_nhwc4) {
         // gen_dir_feature + gen_pts_feats in one launch (channel-last source images supplied by the caller)
         if ((rc = mvsnerf_gather_fwd(a->vol, a->D, a->H, a->W, a->imgs_nhwc4, a->V, a->IH, a->IW, a->w2c, a->K, a->rays_pts, a->rays_ndc,
@@ -86,7 +97,7 @@ extern "C" int mvsnerf_raymarch_fwd_batched(const mvsnerf_raymarch_args* a, int 
 // Full-frame / pixel-range render = the chunk loop of validation_step (train_mvs_nerf_pl.py:198-208):
 //   for each chunk: build_rays_test (utils.py:243-297) -> rendering (renderer.py:138-165) -> keep rgb and depth.
 // The whole loop is enqueued from ONE host call (4 launches per sub-batch: ray generation, fused gather, MLP,
-// compositing), so a frame is not paced by ~0.1 ms of Python/ctypes work per 1024-ray chunk.  Rays are independent,
+// compositing; 2 with the fp32 MLP: ray generation, one-launch ray march), so a frame is not paced by ~0.1 ms of Python/ctypes work per 1024-ray chunk.  Rays are independent,
 // so the sub-batch size is free (results do not depend on it); temporaries live in a caller-provided workspace that is
 // reused by every sub-batch (stream order makes that safe).
 // ---------------------------------------------------------------------------------------------
@@ -131,6 +142,13 @@ extern "C" int mvsnerf_render_pixels_fwd(const mvsnerf_render_args* a, void* str
         const int64_t n = a->n_pixels - off < B ? a->n_pixels - off : B;
         if ((rc = mvsnerf_raygen_fwd(nullptr, nullptr, a->first_pixel + off, a->W_img, a->H_img, a->W_ref, a->H_ref, a->K_tgt, a->c2w_tgt, a->K_ref, a->w2c_ref,
                                      a->near_far_tgt, a->near_far_ref, a->pad, a->lindisp, nullptr, n, S, pts, rdir, ndc, z, nullptr, stream))) return rc;
+        if (!guarded && !a->packed_mlp_split && !a->packed_mlp_bf16) {
+            bool taken;
+            if ((rc = mvs_raymarch_fused_fwd(a->vol, a->D, a->H, a->W, a->vol_layout, a->imgs_nhwc4, a->V, a->IH, a->IW, a->w2c, a->K, a->packed_mlp, pts,
+                                             ndc, z, n, S, rdir, feat, dirs, raw, a->white_bkgd, a->rgb + off * 3, a->disp ? a->disp + off : nullptr,
+                                             a->acc ? a->acc + off : nullptr, nullptr, a->depth ? a->depth + off : nullptr, nullptr, stream, &taken))) return rc;
+            if (taken) continue;
+        }
         if ((rc = mvsnerf_gather_fwd(a->vol, a->D, a->H, a->W, a->imgs_nhwc4, a->V, a->IH, a->IW, a->w2c, a->K, pts, ndc, n, S, rdir,
                                      feat, F, dirs, a->vol_layout, stream))) return rc;
         if (guarded)

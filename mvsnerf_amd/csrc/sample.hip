@@ -316,17 +316,9 @@ __global__ __launch_bounds__(256) void gather_fused_kernel(GatherArgs a)
     for (int v = q; v < a.V; v += 4) {
         const int IW = a.IW, IH = a.IH;
         const ColorTap t = color_project(px, py, pz, a.w2c + v * 16, a.Kmat + v * 9, IW, IH);
-        const float* pl = a.img + (SMALL ? (int64_t)((__umul24(v * IH + t.y0, IW) + t.x0) << 2) : (((int64_t)v * IH + t.y0) * IW + t.x0) * 4);
-        const float* zt = reinterpret_cast<const float*>(&g_zero_tap);
-        const f32x4 t_nw = ldg16(pl);
-        const f32x4 t_ne = ldg16(t.x1in ? pl + 4 : zt);
-        const f32x4 t_sw = ldg16(t.y1in ? pl + (int64_t)IW * 4 : zt);
-        const f32x4 t_se = ldg16((t.x1in && t.y1in) ? pl + (int64_t)IW * 4 + 4 : zt);
-        f32x4 o;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) o[c] = color_blend(t, t_nw[c], t_ne[c], t_sw[c], t_se[c]);
-        o[3] = color_mask(t);
-        if (live) *reinterpret_cast<f32x4*>(frow + 8 + 4 * v) = o;
+        f32x4 tap[4];
+        color_taps_nhwc4<SMALL>(a.img, v, IH, IW, t, tap);
+        if (live) *reinterpret_cast<f32x4*>(frow + 8 + 4 * v) = color_row(t, tap);
     }
     // ---- fold the volume taps in ATen's term order and roundings (sample_dev.h)
     if constexpr (ZFAST) {
@@ -354,9 +346,7 @@ extern "C" int mvsnerf_gather_fwd(const float* vol, int D, int H, int W, const f
     if (N == 0) return MVSNERF_OK;
     const int64_t P = N * S;
     const GatherArgs a{vol, D, H, W, imgs_nhwc4, V, IH, IW, w2c, K, pts, ndc, P, N, rays_dir, feat, feat_stride, dirs_out};
-    const bool small = (int64_t)D * H < (1 << 24) && W < (1 << 24) && (int64_t)H * W < (1 << 24) && D < (1 << 24) && (int64_t)D * H * W * 8 < ((int64_t)1 << 31) &&
-                       (int64_t)V * IH < (1 << 24) && IW < (1 << 24) && (int64_t)V * IH * IW * 4 < ((int64_t)1 << 31) &&
-                       P * (int64_t)(feat_stride > 3 ? feat_stride : 3) < ((int64_t)1 << 31);
+    const bool small = gather_fits_32bit(D, H, W, V, IH, IW, P, feat_stride);
     const unsigned grid = mvs_cdiv(P * 4, 256);
     hipStream_t st = (hipStream_t)stream;
     if (vol_layout == MVSNERF_VOL_HWDC) {

@@ -80,6 +80,38 @@ __device__ __forceinline__ float color_blend(const ColorTap& t, float nw, float 
 
 __device__ __forceinline__ float color_mask(const ColorTap& t) { return (t.gx > -1.0f && t.gx < 1.0f && t.gy > -1.0f && t.gy < 1.0f) ? 1.0f : 0.0f; }
 
+// The four bilinear taps of view v from channel-last images img[v][IH][IW][4] (out-of-image neighbours read the zero block), and the
+// {r, g, b, mask} row they blend to.  SMALL: 32-bit offsets (gather_fits_32bit).  PIX = f32x4: 16-byte pixels; f32x3: the three colour
+// channels only (12-byte loads: no dead fourth register, which the register allocator may otherwise reuse and wait for the load to land).
+typedef float f32x3 __attribute__((ext_vector_type(3)));
+template <typename PIX>
+__device__ __forceinline__ PIX ldg_pix(const float* p)
+{
+    typedef const PIX __attribute__((address_space(1))) * gptr;
+    return *(gptr)p;
+}
+
+template <bool SMALL, typename PIX = f32x4>
+__device__ __forceinline__ void color_taps_nhwc4(const float* __restrict__ img, int v, int IH, int IW, const ColorTap& t, PIX (&tap)[4])
+{
+    const float* pl = img + (SMALL ? (int64_t)((__umul24(v * IH + t.y0, IW) + t.x0) << 2) : (((int64_t)v * IH + t.y0) * IW + t.x0) * 4);
+    const float* zt = reinterpret_cast<const float*>(&g_zero_tap);
+    tap[0] = ldg_pix<PIX>(pl);
+    tap[1] = ldg_pix<PIX>(t.x1in ? pl + 4 : zt);
+    tap[2] = ldg_pix<PIX>(t.y1in ? pl + (int64_t)IW * 4 : zt);
+    tap[3] = ldg_pix<PIX>((t.x1in && t.y1in) ? pl + (int64_t)IW * 4 + 4 : zt);
+}
+
+template <typename PIX>
+__device__ __forceinline__ f32x4 color_row(const ColorTap& t, const PIX (&tap)[4])
+{
+    f32x4 o;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) o[c] = color_blend(t, tap[0][c], tap[1][c], tap[2][c], tap[3][c]);
+    o[3] = color_mask(t);
+    return o;
+}
+
 // dirs = normalise(d) @ R^T  (renderer.py:142-147, 111-122); R == null: no rotation
 __device__ __forceinline__ void dir_feature_of(const float* __restrict__ d3, const float* __restrict__ R, int normalize, float* __restrict__ o3)
 {
@@ -168,6 +200,15 @@ __device__ __forceinline__ ZfastTaps zfast_taps(const float* __restrict__ vol, i
         t.v[k] = ldg16(in ? vol + vox_off8_zfast<SMALL>((int)czf, (int)cyf, (int)cxf, D, W) + ch : zt);
     }
     return t;
+}
+
+// Whether the fused gathers may index in 32 bits (their SMALL instantiation): every voxel, pixel and feature-row offset fits, and the
+// voxel / pixel offsets are formed with 24-bit multiplies.
+inline bool gather_fits_32bit(int D, int H, int W, int V, int IH, int IW, int64_t P, int feat_stride)
+{
+    return (int64_t)D * H < (1 << 24) && W < (1 << 24) && (int64_t)H * W < (1 << 24) && D < (1 << 24) && (int64_t)D * H * W * 8 < ((int64_t)1 << 31) &&
+           (int64_t)V * IH < (1 << 24) && IW < (1 << 24) && (int64_t)V * IH * IW * 4 < ((int64_t)1 << 31) &&
+           P * (int64_t)(feat_stride > 3 ? feat_stride : 3) < ((int64_t)1 << 31);
 }
 
 // the four channel sums of this lane's half; valid in the y0 lanes (q < 2)
