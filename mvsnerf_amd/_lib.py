@@ -20,6 +20,7 @@ _c_l = ctypes.c_int64
 
 class RaymarchArgs(ctypes.Structure):
     """mvsnerf_raymarch_args (include/mvsnerf_hip.h)."""
+    __slots__ = ()  # a misspelt field name in a keyword fill raises instead of being stored beside the fields
     _fields_ = [
         ("vol", _c_fp), ("D", _c_i), ("H", _c_i), ("W", _c_i),
         ("imgs", _c_fp), ("V", _c_i), ("IH", _c_i), ("IW", _c_i),
@@ -34,6 +35,7 @@ class RaymarchArgs(ctypes.Structure):
 
 class RaymarchTrainArgs(ctypes.Structure):
     """mvsnerf_raymarch_train_args (include/mvsnerf_hip.h)."""
+    __slots__ = ()
     _fields_ = [
         ("vol", _c_fp), ("D", _c_i), ("H", _c_i), ("W", _c_i), ("C", _c_i),
         ("imgs_nhwc4", _c_fp), ("V", _c_i), ("IH", _c_i), ("IW", _c_i),
@@ -47,6 +49,7 @@ class RaymarchTrainArgs(ctypes.Structure):
 
 class RaymarchBwdArgs(ctypes.Structure):
     """mvsnerf_raymarch_bwd_args (include/mvsnerf_hip.h)."""
+    __slots__ = ()
     _fields_ = [
         ("packed_mlp", _c_fp), ("packed_bwd", _c_fp), ("bf16", _c_i), ("F", _c_i),
         ("raw", _c_fp), ("saved", _c_fp), ("z_vals", _c_fp), ("rays_ndc", _c_fp),
@@ -60,6 +63,7 @@ class RaymarchBwdArgs(ctypes.Structure):
 
 class RenderArgs(ctypes.Structure):
     """mvsnerf_render_args (include/mvsnerf_hip.h)."""
+    __slots__ = ()
     _fields_ = [
         ("vol", _c_fp), ("D", _c_i), ("H", _c_i), ("W", _c_i),
         ("imgs_nhwc4", _c_fp), ("V", _c_i), ("IH", _c_i), ("IW", _c_i),
@@ -75,6 +79,7 @@ class RenderArgs(ctypes.Structure):
 
 class SweepConv0Args(ctypes.Structure):
     """mvsnerf_sweep_conv0_args (include/mvsnerf_hip.h): the guarded head of a no-grad scene encode."""
+    __slots__ = ()
     _fields_ = [
         ("feats_cl", _c_fp), ("imgs_cl", _c_fp), ("proj", _c_fp), ("depth", _c_fp),
         ("V", _c_i), ("H", _c_i), ("W", _c_i), ("D", _c_i), ("pad", _c_i), ("CP", _c_i),

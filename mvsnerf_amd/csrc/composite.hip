@@ -5,6 +5,7 @@
 // HBM-bound: 20 B read + 8 B written per sample.
 #include "common.h"
 #include "composite_wave.h"
+#include "march.h"
 
 template <int CHUNK>   // CHUNK > 0: samples per lane known at compile time (values stay in registers, composite_wave.h)
 __global__ __launch_bounds__(256) void composite_kernel(
@@ -69,9 +70,6 @@ __global__ __launch_bounds__(256) void composite_kernel(
     }
 }
 
-int mvs_composite_fwd(const float* raw, const float* z, int64_t N, int S, int white_bkgd, float* rgb_map, float* disp, float* acc, float* weights,
-                      float* depth, float* alpha, int* guard, void* stream);
-
 extern "C" int mvsnerf_composite_fwd(const float* raw, const float* z, int64_t N, int S, int white_bkgd,
                                      float* rgb_map, float* disp, float* acc, float* weights,
                                      float* depth, float* alpha, void* stream)
@@ -79,7 +77,6 @@ extern "C" int mvsnerf_composite_fwd(const float* raw, const float* z, int64_t N
     return mvs_composite_fwd(raw, z, N, S, white_bkgd, rgb_map, disp, acc, weights, depth, alpha, nullptr, stream);
 }
 
-// guard != NULL: the launch also ends a guarded 16-bit sequence (raymarch.hip)
 int mvs_composite_fwd(const float* raw, const float* z, int64_t N, int S, int white_bkgd, float* rgb_map, float* disp, float* acc, float* weights,
                       float* depth, float* alpha, int* guard, void* stream)
 {

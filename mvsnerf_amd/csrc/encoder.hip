@@ -13,6 +13,7 @@
 #include "conv3d_bf16_layout.h"
 #include "act.h"
 #include "knobs.h"
+#include "march.h"
 
 // =============================================================================================
 // small layout / resize helpers
@@ -830,7 +831,6 @@ __global__ void guard_consume_kernel(int* guard)
     if (guard[0]) { guard[1] += 1; guard[0] = 0; }
 }
 
-// for entries outside this file (raymarch.hip)
 int mvs_guard_consume(int* guard, hipStream_t st)
 {
     guard_consume_kernel<<<1, 1, 0, st>>>(guard);

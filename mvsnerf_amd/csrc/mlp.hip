@@ -12,6 +12,7 @@
 #include "knobs.h"
 #include "sample_dev.h"
 #include "composite_wave.h"
+#include "march.h"
 
 using namespace mlp;
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -625,42 +626,40 @@ __global__ __launch_bounds__(256, 2) void raymarch_fused_kernel(const float* __r
     mlp_fwd_pipe_tile<false, false, true, NR>(blockIdx.x, packed, F, ndc, 3, nullptr, F, nullptr, 3, P, S, raw, nullptr, nullptr, &fa);
 }
 
-// Launches the one-launch ray march when it applies (*taken = true), otherwise leaves the batch to the launch sequence (*taken = false):
-// invalid arguments, a DHWC volume or a shape whose offsets need 64 bits go that way - with the sequence's own error codes.  When 128 % S
-// != 0 a tile holds pieces of rays, and the compositing is a separate mvs_composite_fwd launch.
-int mvs_composite_fwd(const float* raw, const float* z, int64_t N, int S, int white_bkgd, float* rgb_map, float* disp, float* acc, float* weights,
-                      float* depth, float* alpha, int* guard, void* stream);                                                                 // composite.hip
-int mvs_raymarch_fused_fwd(const float* vol, int D, int H, int W, int vol_layout, const float* imgs_nhwc4, int V, int IH, int IW, const float* w2c,
-                           const float* K, const float* packed, const float* pts, const float* ndc, const float* z, int64_t N, int S,
-                           const float* rays_dir, float* feat, float* dirs_out, float* raw, int white_bkgd, float* rgb_map, float* disp, float* acc,
-                           float* weights, float* depth, float* alpha, void* stream, bool* taken)
+// mvs_raymarch_fused_applies / mvs_raymarch_fused_fwd (march.h): a batch they do not take - invalid arguments, a DHWC volume, a shape whose
+// offsets need 64 bits, another MLP - goes through the launch sequence of march_batch (raymarch.hip), with that sequence's own error codes.
+bool mvs_raymarch_fused_applies(const MarchBatch& b)
 {
-    *taken = false;
-    const int F = 8 + 4 * V;
-    if (vol_layout != MVSNERF_VOL_HWDC || !vol || !imgs_nhwc4 || !w2c || !K || !packed || !pts || !ndc || !z || !rays_dir || !feat || !dirs_out || !raw) return MVSNERF_OK;
-    if (D < 1 || H < 1 || W < 1 || V < 1 || F > MAX_F || IH < 2 || IW < 2 || N < 1 || S < 1) return MVSNERF_OK;
-    if (!mvs_aligned16(feat) || !mvs_aligned16(vol) || !mvs_aligned16(imgs_nhwc4) || !mvs_aligned16(packed) || !mvs_aligned16(raw)) return MVSNERF_OK;
-    const int64_t P = N * S;
-    if (!gather_fits_32bit(D, H, W, V, IH, IW, P, F)) return MVSNERF_OK;
-    *taken = true;
-    const RaymarchTileArgs fa{vol, D, H, W, imgs_nhwc4, V, IH, IW, w2c, K, pts, rays_dir, feat, dirs_out, z, N, 128 % S == 0 ? 128 / S : 0,
-                              CompositeOut{rgb_map, disp, acc, weights, depth, alpha, white_bkgd, nullptr}};
-    hipStream_t st = (hipStream_t)stream;
+    if (b.packed_bf16 || b.packed_split || b.guard) return false;
+    const int F = 8 + 4 * b.V;
+    if (b.vol_layout != MVSNERF_VOL_HWDC || !b.vol || !b.imgs_nhwc4 || !b.w2c || !b.K || !b.packed || !b.pts || !b.ndc || !b.z || !b.rays_dir ||
+        !b.feat || !b.dirs || !b.raw) return false;
+    if (b.D < 1 || b.H < 1 || b.W < 1 || b.V < 1 || F > MAX_F || b.IH < 2 || b.IW < 2 || b.N < 1 || b.S < 1) return false;
+    if (!mvs_aligned16(b.feat) || !mvs_aligned16(b.vol) || !mvs_aligned16(b.imgs_nhwc4) || !mvs_aligned16(b.packed) || !mvs_aligned16(b.raw)) return false;
+    return gather_fits_32bit(b.D, b.H, b.W, b.V, b.IH, b.IW, b.N * b.S, F);
+}
+
+int mvs_raymarch_fused_fwd(const MarchBatch& b, hipStream_t st)
+{
+    const int F = 8 + 4 * b.V, S = b.S;
+    const int64_t P = b.N * S;
+    const RaymarchTileArgs fa{b.vol, b.D, b.H, b.W, b.imgs_nhwc4, b.V, b.IH, b.IW, b.w2c, b.K, b.pts, b.rays_dir, b.feat, b.dirs, b.z, b.N,
+                              128 % S == 0 ? 128 / S : 0, CompositeOut{b.rgb_map, b.disp, b.acc, b.weights, b.depth, b.alpha, b.white_bkgd, nullptr}};
     const size_t lds_bytes = PIPE_LDS_FLOATS * sizeof(float);
     const unsigned grid = mvs_cdiv(P, 128);
     static unsigned long long cap[3] = {0, 0, 0};
 #define MVS_FUSED(NR_)                                                                                                                 \
     do {                                                                                                                               \
         if (int rc_ = mvs_raise_lds_cap(reinterpret_cast<const void*>(raymarch_fused_kernel<NR_>), (int)lds_bytes, &cap[NR_])) return rc_; \
-        raymarch_fused_kernel<NR_><<<grid, 256, lds_bytes, st>>>(packed, F, ndc, P, S, raw, fa);                                     \
+        raymarch_fused_kernel<NR_><<<grid, 256, lds_bytes, st>>>(b.packed, F, b.ndc, P, S, b.raw, fa);                               \
     } while (0)
     if (fa.rays_per_tile == 0) MVS_FUSED(0);
     else if (S <= 64) MVS_FUSED(1);
     else MVS_FUSED(2);
 #undef MVS_FUSED
     MVS_LAUNCH_CHECK();
-    if (fa.rays_per_tile == 0)
-        return mvs_composite_fwd(raw, z, N, S, white_bkgd, rgb_map, disp, acc, weights, depth, alpha, nullptr, stream);
+    if (fa.rays_per_tile == 0)                      // a tile holds pieces of rays: the compositing is a launch of its own
+        return mvs_composite_fwd(b.raw, b.z, b.N, S, b.white_bkgd, b.rgb_map, b.disp, b.acc, b.weights, b.depth, b.alpha, nullptr, st);
     return MVSNERF_OK;
 }
 
@@ -680,7 +679,6 @@ static int mlp_fwd_checked(const float* packed, int F, const float* ndc, int ndc
     return launch_mlp_pipe<false, false>(packed, F, ndc, ndc_stride, feat, feat_stride, dirs, dirs_stride, P, S, raw, st, nullptr, census, run_if);
 }
 
-// mvsnerf_mlp_fwd predicated on a guard word (raymarch.hip: the fp32 re-run of a guarded fp16x3 batch)
 int mvs_mlp_fwd_if(const float* packed, int F, const float* ndc, int ndc_stride, const float* feat, int feat_stride,
                    const float* dirs, int dirs_stride, int64_t N, int S, int alpha_only, float* raw, const int* run_if, void* stream)
 {

@@ -11,6 +11,7 @@
 #include "lds_dma.h"
 #include "mlp_layout.h"
 #include "mlp_b16_dev.h"
+#include "march.h"
 #include "knobs.h"
 
 using namespace mlp;

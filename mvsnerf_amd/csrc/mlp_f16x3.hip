@@ -37,6 +37,7 @@
 #include "lds_dma.h"
 #include "mlp_layout.h"
 #include "mlp_b16_dev.h"
+#include "march.h"
 
 using namespace mlp;
 

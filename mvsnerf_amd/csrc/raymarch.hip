@@ -2,21 +2,9 @@
 // the batch on one stream from a single host call (one FFI crossing per 1024-ray batch instead of ~40
 // ATen launches).
 #include "common.h"
+#include "march.h"
 
 extern "C" int mvsnerf_abi_version(void) { return 12; }
-
-// internal pieces of the guarded 16-bit sequences (include/mvsnerf_hip.h)
-int mvs_mlp_f16x3_fwd(const void* packed_h, const float* packed_f32, int F, const float* ndc, int ndc_stride, const float* feat, int feat_stride,
-                      const float* dirs, int dirs_stride, int64_t P, int S, int alpha_only, float* raw, hipStream_t st, int* guard);                       // mlp_f16x3.hip
-int mvs_mlp_fwd_if(const float* packed, int F, const float* ndc, int ndc_stride, const float* feat, int feat_stride,
-                   const float* dirs, int dirs_stride, int64_t N, int S, int alpha_only, float* raw, const int* run_if, void* stream);                      // mlp.hip
-int mvs_composite_fwd(const float* raw, const float* z, int64_t N, int S, int white_bkgd, float* rgb_map, float* disp, float* acc, float* weights,
-                      float* depth, float* alpha, int* guard, void* stream);                                                                               // composite.hip
-int mvs_guard_consume(int* guard, hipStream_t st);                                                                                                         // encoder.hip
-int mvs_raymarch_fused_fwd(const float* vol, int D, int H, int W, int vol_layout, const float* imgs_nhwc4, int V, int IH, int IW, const float* w2c,
-                           const float* K, const float* packed, const float* pts, const float* ndc, const float* z, int64_t N, int S,
-                           const float* rays_dir, float* feat, float* dirs_out, float* raw, int white_bkgd, float* rgb_map, float* disp, float* acc,
-                           float* weights, float* depth, float* alpha, void* stream, bool* taken);                                                          // mlp.hip
 
 // fp16x3 kernel reporting through guard[0], then the fp32-MFMA kernel predicated on it (same inputs, same output buffer)
 static int mlp_guarded_pair(const void* packed_h, const float* packed_f32, int F, const float* ndc, int ndc_stride, const float* feat, int feat_stride,
@@ -40,6 +28,43 @@ extern "C" int mvsnerf_mlp_fwd_guarded(const void* packed_fp16, const float* pac
     return mvs_guard_consume(guard, (hipStream_t)stream);
 }
 
+// A guard needs the fp16 split planes (the guarded sequence); checked before anything of the batch is launched.
+static bool mlp_choice_ok(const MarchBatch& b) { return !b.guard || (b.packed_split && b.n_split == MVSNERF_SPLIT_FP16); }
+
+// The kernels of one batch, enqueued on `st`: the one-launch ray march when it applies, else lookups -> MLP -> compositing.  The launchers
+// validate the rest of the arguments.
+static int march_batch(const MarchBatch& b, hipStream_t st)
+{
+    if (!mlp_choice_ok(b)) return MVSNERF_EINVAL;
+    // fp32 MLP: lookups, MLP and (when a tile holds whole rays) compositing in one launch, when the shapes allow it
+    if (mvs_raymarch_fused_applies(b)) return mvs_raymarch_fused_fwd(b, st);
+    const int F = 8 + 4 * b.V;
+    int rc;
+    if (b.imgs_nhwc4) {
+        // gen_dir_feature + gen_pts_feats in one launch (channel-last source images supplied by the caller)
+        if ((rc = mvsnerf_gather_fwd(b.vol, b.D, b.H, b.W, b.imgs_nhwc4, b.V, b.IH, b.IW, b.w2c, b.K, b.pts, b.ndc, b.N, b.S, b.rays_dir, b.feat, F,
+                                     b.dirs, b.vol_layout, st))) return rc;
+    } else {
+        // view-direction feature in the reference camera frame (renderer.py:142-147)
+        if ((rc = mvsnerf_dir_feature_fwd(b.rays_dir, b.w2c, b.N, 1, b.dirs, st))) return rc;
+        // gen_pts_feats (renderer.py:124-136): input_feat[..., :8] = volume lookup, [..., 8:] = colours + masks
+        if ((rc = mvsnerf_volume_sample_fwd(b.vol, b.D, b.H, b.W, 8, b.ndc, b.N * b.S, b.feat, F, b.vol_layout, st))) return rc;
+        if ((rc = mvsnerf_color_sample_fwd(b.imgs, b.V, b.IH, b.IW, b.w2c, b.K, b.pts, b.N * b.S, 1, b.feat + 8, F, st))) return rc;
+    }
+    // network_query_fn (renderer.py:156 -> run_network_mvs 42-63)
+    if (b.guard)
+        rc = mlp_guarded_pair(b.packed_split, b.packed, F, b.ndc, 3, b.feat, F, b.dirs, 3, b.N, b.S, 0, b.raw, b.guard, st);
+    else if (b.packed_split)
+        rc = mvsnerf_mlp_fwd_split(b.packed_split, b.packed, F, b.n_split, b.ndc, 3, b.feat, F, b.dirs, 3, b.N, b.S, 0, b.raw, st);
+    else if (b.packed_bf16)
+        rc = mvsnerf_mlp_fwd_bf16(b.packed_bf16, b.packed, F, b.ndc, 3, b.feat, F, b.dirs, 3, b.N, b.S, 0, b.raw, st);
+    else
+        rc = mvsnerf_mlp_fwd(b.packed, F, b.ndc, 3, b.feat, F, b.dirs, 3, b.N, b.S, 0, b.raw, st);
+    if (rc) return rc;
+    // raw2outputs (renderer.py:162); in a guarded sequence the same launch counts a fallback and re-arms the guard
+    return mvs_composite_fwd(b.raw, b.z, b.N, b.S, b.white_bkgd, b.rgb_map, b.disp, b.acc, b.weights, b.depth, b.alpha, b.guard, st);
+}
+
 extern "C" int mvsnerf_raymarch_fwd(const mvsnerf_raymarch_args* a, void* stream)
 {
     if (!a) return MVSNERF_EINVAL;
@@ -47,42 +72,12 @@ extern "C" int mvsnerf_raymarch_fwd(const mvsnerf_raymarch_args* a, void* stream
         !a->rays_dir || !a->dirs_tmp || !a->input_feat || !a->raw)
         return MVSNERF_EINVAL;
     if (a->N < 0 || a->S < 1 || a->V < 1) return MVSNERF_EINVAL;
-    const int F = 8 + 4 * a->V;
-    const int64_t P = a->N * a->S;
-    int rc;
-    if (a->imgs_nhwc4 && !a->packed_mlp_split && !a->packed_mlp_bf16 && !a->guard) {
-        // fp32 MLP: lookups, MLP and (when a tile holds whole rays) compositing in one launch, when the shapes allow it
-        bool taken;
-        if ((rc = mvs_raymarch_fused_fwd(a->vol, a->D, a->H, a->W, a->vol_layout, a->imgs_nhwc4, a->V, a->IH, a->IW, a->w2c, a->K, a->packed_mlp,
-                                         a->rays_pts, a->rays_ndc, a->z_vals, a->N, a->S, a->rays_dir, a->input_feat, a->dirs_tmp, a->raw, a->white_bkgd,
-                                         a->rgb_map, a->disp, a->acc, a->weights, a->depth, a->alpha, stream, &taken)) || taken) return rc;
-    }
-    if (a->imgs_nhwc4) {
-        // gen_dir_feature + gen_pts_feats in one launch (channel-last source images supplied by the caller)
-        if ((rc = mvsnerf_gather_fwd(a->vol, a->D, a->H, a->W, a->imgs_nhwc4, a->V, a->IH, a->IW, a->w2c, a->K, a->rays_pts, a->rays_ndc,
-                                     a->N, a->S, a->rays_dir, a->input_feat, F, a->dirs_tmp, a->vol_layout, stream))) return rc;
-    } else {
-        // view-direction feature in the reference camera frame (renderer.py:142-147)
-        if ((rc = mvsnerf_dir_feature_fwd(a->rays_dir, a->w2c, a->N, 1, a->dirs_tmp, stream))) return rc;
-        // gen_pts_feats (renderer.py:124-136): input_feat[..., :8] = volume lookup, [..., 8:] = colours + masks
-        if ((rc = mvsnerf_volume_sample_fwd(a->vol, a->D, a->H, a->W, 8, a->rays_ndc, P, a->input_feat, F, a->vol_layout, stream))) return rc;
-        if ((rc = mvsnerf_color_sample_fwd(a->imgs, a->V, a->IH, a->IW, a->w2c, a->K, a->rays_pts, P, 1, a->input_feat + 8, F, stream))) return rc;
-    }
-    // network_query_fn (renderer.py:156 -> run_network_mvs 42-63)
-    const bool guarded = a->guard && a->packed_mlp_split && a->n_split == MVSNERF_SPLIT_FP16;
-    if (a->guard && !guarded) return MVSNERF_EINVAL;
-    if (guarded)
-        rc = mlp_guarded_pair(a->packed_mlp_split, a->packed_mlp, F, a->rays_ndc, 3, a->input_feat, F, a->dirs_tmp, 3, a->N, a->S, 0, a->raw, a->guard, stream);
-    else if (a->packed_mlp_split)
-        rc = mvsnerf_mlp_fwd_split(a->packed_mlp_split, a->packed_mlp, F, a->n_split, a->rays_ndc, 3, a->input_feat, F, a->dirs_tmp, 3, a->N, a->S, 0, a->raw, stream);
-    else if (a->packed_mlp_bf16)
-        rc = mvsnerf_mlp_fwd_bf16(a->packed_mlp_bf16, a->packed_mlp, F, a->rays_ndc, 3, a->input_feat, F, a->dirs_tmp, 3, a->N, a->S, 0, a->raw, stream);
-    else
-        rc = mvsnerf_mlp_fwd(a->packed_mlp, F, a->rays_ndc, 3, a->input_feat, F, a->dirs_tmp, 3, a->N, a->S, 0, a->raw, stream);
-    if (rc) return rc;
-    // raw2outputs (renderer.py:162); in a guarded sequence the same launch counts a fallback and re-arms the guard
-    return mvs_composite_fwd(a->raw, a->z_vals, a->N, a->S, a->white_bkgd, a->rgb_map, a->disp, a->acc, a->weights, a->depth, a->alpha,
-                             guarded && P > 0 ? a->guard : nullptr, stream);
+    return march_batch({.vol = a->vol, .D = a->D, .H = a->H, .W = a->W, .vol_layout = a->vol_layout, .imgs = a->imgs, .imgs_nhwc4 = a->imgs_nhwc4,
+                        .V = a->V, .IH = a->IH, .IW = a->IW, .w2c = a->w2c, .K = a->K, .pts = a->rays_pts, .ndc = a->rays_ndc, .z = a->z_vals,
+                        .rays_dir = a->rays_dir, .N = a->N, .S = a->S, .white_bkgd = a->white_bkgd, .feat = a->input_feat, .dirs = a->dirs_tmp, .raw = a->raw,
+                        .rgb_map = a->rgb_map, .disp = a->disp, .acc = a->acc, .weights = a->weights, .depth = a->depth, .alpha = a->alpha,
+                        .packed = a->packed_mlp, .packed_bf16 = a->packed_mlp_bf16, .packed_split = a->packed_mlp_split, .n_split = a->n_split,
+                        .guard = a->guard}, (hipStream_t)stream);
 }
 
 extern "C" int mvsnerf_raymarch_fwd_batched(const mvsnerf_raymarch_args* a, int K, void* stream)
@@ -126,8 +121,6 @@ extern "C" int mvsnerf_render_pixels_fwd(const mvsnerf_render_args* a, void* str
     if (a->first_pixel + a->n_pixels > (int64_t)a->W_img * a->H_img) return MVSNERF_EINVAL;
     if (a->workspace_floats < render_ws_floats(a->batch_rays, a->S, a->V)) return MVSNERF_EINVAL;
     const int F = 8 + 4 * a->V, S = a->S;
-    const bool guarded = a->guard && a->packed_mlp_split && a->n_split == MVSNERF_SPLIT_FP16;
-    if (a->guard && !guarded) return MVSNERF_EINVAL;
     const int64_t B = a->batch_rays, P = B * S;
     auto r4 = [](int64_t n) { return (n + 3) & ~(int64_t)3; };
     float* pts = a->workspace;
@@ -137,32 +130,22 @@ extern "C" int mvsnerf_render_pixels_fwd(const mvsnerf_render_args* a, void* str
     float* raw = feat + r4((int64_t)F * P);
     float* rdir = raw + r4(4 * P);
     float* dirs = rdir + r4(3 * B);
-    int rc;
+    // every sub-batch: the same workspace slices, its own ray count and output rows (set in the loop); weights and alpha are not produced
+    MarchBatch b{.vol = a->vol, .D = a->D, .H = a->H, .W = a->W, .vol_layout = a->vol_layout, .imgs_nhwc4 = a->imgs_nhwc4, .V = a->V, .IH = a->IH,
+                 .IW = a->IW, .w2c = a->w2c, .K = a->K, .pts = pts, .ndc = ndc, .z = z, .rays_dir = rdir, .S = S, .white_bkgd = a->white_bkgd,
+                 .feat = feat, .dirs = dirs, .raw = raw, .packed = a->packed_mlp, .packed_bf16 = a->packed_mlp_bf16,
+                 .packed_split = a->packed_mlp_split, .n_split = a->n_split, .guard = a->guard};
+    if (!mlp_choice_ok(b)) return MVSNERF_EINVAL;
     for (int64_t off = 0; off < a->n_pixels; off += B) {
-        const int64_t n = a->n_pixels - off < B ? a->n_pixels - off : B;
-        if ((rc = mvsnerf_raygen_fwd(nullptr, nullptr, a->first_pixel + off, a->W_img, a->H_img, a->W_ref, a->H_ref, a->K_tgt, a->c2w_tgt, a->K_ref, a->w2c_ref,
-                                     a->near_far_tgt, a->near_far_ref, a->pad, a->lindisp, nullptr, n, S, pts, rdir, ndc, z, nullptr, stream))) return rc;
-        if (!guarded && !a->packed_mlp_split && !a->packed_mlp_bf16) {
-            bool taken;
-            if ((rc = mvs_raymarch_fused_fwd(a->vol, a->D, a->H, a->W, a->vol_layout, a->imgs_nhwc4, a->V, a->IH, a->IW, a->w2c, a->K, a->packed_mlp, pts,
-                                             ndc, z, n, S, rdir, feat, dirs, raw, a->white_bkgd, a->rgb + off * 3, a->disp ? a->disp + off : nullptr,
-                                             a->acc ? a->acc + off : nullptr, nullptr, a->depth ? a->depth + off : nullptr, nullptr, stream, &taken))) return rc;
-            if (taken) continue;
-        }
-        if ((rc = mvsnerf_gather_fwd(a->vol, a->D, a->H, a->W, a->imgs_nhwc4, a->V, a->IH, a->IW, a->w2c, a->K, pts, ndc, n, S, rdir,
-                                     feat, F, dirs, a->vol_layout, stream))) return rc;
-        if (guarded)
-            rc = mlp_guarded_pair(a->packed_mlp_split, a->packed_mlp, F, ndc, 3, feat, F, dirs, 3, n, S, 0, raw, a->guard, stream);
-        else if (a->packed_mlp_split)
-            rc = mvsnerf_mlp_fwd_split(a->packed_mlp_split, a->packed_mlp, F, a->n_split, ndc, 3, feat, F, dirs, 3, n, S, 0, raw, stream);
-        else if (a->packed_mlp_bf16)
-            rc = mvsnerf_mlp_fwd_bf16(a->packed_mlp_bf16, a->packed_mlp, F, ndc, 3, feat, F, dirs, 3, n, S, 0, raw, stream);
-        else
-            rc = mvsnerf_mlp_fwd(a->packed_mlp, F, ndc, 3, feat, F, dirs, 3, n, S, 0, raw, stream);
-        if (rc) return rc;
-        if ((rc = mvs_composite_fwd(raw, z, n, S, a->white_bkgd, a->rgb + off * 3, a->disp ? a->disp + off : nullptr,
-                                    a->acc ? a->acc + off : nullptr, nullptr, a->depth ? a->depth + off : nullptr, nullptr,
-                                    guarded ? a->guard : nullptr, stream))) return rc;
+        b.N = a->n_pixels - off < B ? a->n_pixels - off : B;
+        if (int rc = mvsnerf_raygen_fwd(nullptr, nullptr, a->first_pixel + off, a->W_img, a->H_img, a->W_ref, a->H_ref, a->K_tgt, a->c2w_tgt, a->K_ref,
+                                        a->w2c_ref, a->near_far_tgt, a->near_far_ref, a->pad, a->lindisp, nullptr, b.N, S, pts, rdir, ndc, z, nullptr, stream))
+            return rc;
+        b.rgb_map = a->rgb + off * 3;
+        b.disp = a->disp ? a->disp + off : nullptr;
+        b.acc = a->acc ? a->acc + off : nullptr;
+        b.depth = a->depth ? a->depth + off : nullptr;
+        if (int rc = march_batch(b, (hipStream_t)stream)) return rc;
     }
     return MVSNERF_OK;
 }

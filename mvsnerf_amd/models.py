@@ -154,7 +154,7 @@ class Renderer_ours(nn.Module):
         return self._packed_s[1], n_split
 
     def packed_alt(self, feat_dim=None, fresh=False):
-        """Keyword arguments selecting the MLP kernel of ops.raymarch / ops.render_pixels for the current ops.MLP_PRECISION."""
+        """Keyword arguments selecting the MLP kernel of ops.raymarch / ops.render_pixels / ops.mlp_forward for the current ops.MLP_PRECISION."""
         mode = ops.inference_mlp_mode()
         if mode == "bf16":
             return {"packed_bf16": self.packed_bf16(feat_dim, fresh)}
@@ -173,18 +173,8 @@ class Renderer_ours(nn.Module):
         F = feat.shape[-1]
         vd = None if alpha_only else viewdirs.contiguous()        # named: a temporary would be freed before the launch
         dptr = 0 if alpha_only else ops.dev_f32(vd, "viewdirs")
-        mode = ops.inference_mlp_mode()
-        if mode == "bf16":
-            return ops.mlp_forward_bf16(self.packed_bf16(F), self.packed(F), F, ops.dev_f32(pts, "pts"), 3, ops.dev_f32(feat, "feat"), F,
-                                        dptr, 3, N, S, alpha_only, pts.device)
-        if mode == "guarded":
-            ps, _ = self.packed_split(F, ops.N_SPLIT["fp16x3"])
-            return ops.mlp_forward_guarded(ps, self.packed(F), F, ops.dev_f32(pts, "pts"), 3, ops.dev_f32(feat, "feat"), F, dptr, 3, N, S, alpha_only, pts.device)
-        if mode in ops.N_SPLIT:
-            ps, ns = self.packed_split(F, ops.N_SPLIT[mode])
-            return ops.mlp_forward_split(ps, ns, self.packed(F), F, ops.dev_f32(pts, "pts"), 3, ops.dev_f32(feat, "feat"), F,
-                                         dptr, 3, N, S, alpha_only, pts.device)
-        return ops.mlp_forward(self.packed(F), F, ops.dev_f32(pts, "pts"), 3, ops.dev_f32(feat, "feat"), F, dptr, 3, N, S, alpha_only, pts.device)
+        return ops.mlp_forward(self.packed(F), F, ops.dev_f32(pts, "pts"), 3, ops.dev_f32(feat, "feat"), F, dptr, 3, N, S, alpha_only, pts.device,
+                               **self.packed_alt(F))
 
     def _rows(self, x, alpha_only):
         ops._need_no_grad(x, *self.parameters(), op="Renderer_ours")

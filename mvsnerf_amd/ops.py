@@ -408,21 +408,6 @@ def mlp_pack_split(weights, F, n_split):
     return packed
 
 
-def mlp_forward_split(packed_split, n_split, packed, F, ndc_ptr, ndc_stride, feat_ptr, feat_stride, dirs_ptr, dirs_stride, N, S, alpha_only, device):
-    raw = torch.empty((N * S, 1 if alpha_only else 4), device=device, dtype=torch.float32)
-    check(_lib.lib().mvsnerf_mlp_fwd_split(packed_split.data_ptr(), packed.data_ptr(), F, n_split, ndc_ptr, ndc_stride, feat_ptr, feat_stride,
-                                           dirs_ptr, dirs_stride, N, S, int(alpha_only), raw.data_ptr(), stream_ptr()), "mlp_fwd_split")
-    return raw
-
-
-def mlp_forward_guarded(packed_h, packed, F, ndc_ptr, ndc_stride, feat_ptr, feat_stride, dirs_ptr, dirs_stride, N, S, alpha_only, device):
-    raw = torch.empty((N * S, 1 if alpha_only else 4), device=device, dtype=torch.float32)
-    check(_lib.lib().mvsnerf_mlp_fwd_guarded(packed_h.data_ptr(), packed.data_ptr(), F, ndc_ptr, ndc_stride, feat_ptr, feat_stride,
-                                             dirs_ptr, dirs_stride, N, S, int(alpha_only), raw.data_ptr(), guard_words(device).data_ptr(), stream_ptr()),
-          "mlp_fwd_guarded")
-    return raw
-
-
 def mlp_pack_bf16(weights, F):
     n = _lib.lib().mvsnerf_mlp_packed_bf16_elems(F)
     packed = torch.empty(n, device=weights[0].device, dtype=torch.bfloat16)
@@ -431,18 +416,31 @@ def mlp_pack_bf16(weights, F):
     return packed
 
 
-def mlp_forward_bf16(packed_bf16, packed, F, ndc_ptr, ndc_stride, feat_ptr, feat_stride, dirs_ptr, dirs_stride, N, S, alpha_only, device):
-    raw = torch.empty((N * S, 1 if alpha_only else 4), device=device, dtype=torch.float32)
-    check(_lib.lib().mvsnerf_mlp_fwd_bf16(packed_bf16.data_ptr(), packed.data_ptr(), F, ndc_ptr, ndc_stride, feat_ptr, feat_stride,
-                                          dirs_ptr, dirs_stride, N, S, int(alpha_only), raw.data_ptr(), stream_ptr()), "mlp_fwd_bf16")
+def mlp_forward(packed, F, ndc_ptr, ndc_stride, feat_ptr, feat_stride, dirs_ptr, dirs_stride, N, S, alpha_only, device, *,
+                packed_bf16=None, packed_split=None, guard=None):
+    """Network query (run_network_mvs, renderer.py:42-63) -> raw (N*S, 1 if alpha_only else 4).  The keywords choose the kernel as the ray march
+    does (Renderer_ours.packed_alt returns them): guard + packed_split = (fp16x3 planes, 18) -> the guarded sequence, packed_split = (planes,
+    n_split) -> the split kernel, packed_bf16 -> bf16, none -> fp32."""
+    l, raw = _lib.lib(), torch.empty((N * S, 1 if alpha_only else 4), device=device, dtype=torch.float32)
+    io = (ndc_ptr, ndc_stride, feat_ptr, feat_stride, dirs_ptr, dirs_stride, N, S, int(alpha_only), raw.data_ptr())
+    if guard is not None:
+        if packed_split is None or packed_split[1] != N_SPLIT["fp16x3"]:
+            raise ValueError("mlp_forward: a guard needs the fp16x3 split planes (the guarded sequence)")
+        check(l.mvsnerf_mlp_fwd_guarded(packed_split[0].data_ptr(), packed.data_ptr(), F, *io, guard.data_ptr(), stream_ptr()), "mlp_fwd_guarded")
+    elif packed_split is not None:
+        check(l.mvsnerf_mlp_fwd_split(packed_split[0].data_ptr(), packed.data_ptr(), F, packed_split[1], *io, stream_ptr()), "mlp_fwd_split")
+    elif packed_bf16 is not None:
+        check(l.mvsnerf_mlp_fwd_bf16(packed_bf16.data_ptr(), packed.data_ptr(), F, *io, stream_ptr()), "mlp_fwd_bf16")
+    else:
+        check(l.mvsnerf_mlp_fwd(packed.data_ptr(), F, *io, stream_ptr()), "mlp_fwd")
     return raw
 
 
-def mlp_forward(packed, F, ndc_ptr, ndc_stride, feat_ptr, feat_stride, dirs_ptr, dirs_stride, N, S, alpha_only, device):
-    raw = torch.empty((N * S, 1 if alpha_only else 4), device=device, dtype=torch.float32)
-    check(_lib.lib().mvsnerf_mlp_fwd(packed.data_ptr(), F, ndc_ptr, ndc_stride, feat_ptr, feat_stride, dirs_ptr, dirs_stride,
-                                     N, S, int(alpha_only), raw.data_ptr(), stream_ptr()), "mlp_fwd")
-    return raw
+def _mlp_fields(packed_bf16, packed_split, guard):
+    """The MLP-choice fields of mvsnerf_raymarch_args and mvsnerf_render_args."""
+    return dict(packed_mlp_bf16=0 if packed_bf16 is None else packed_bf16.data_ptr(),
+                packed_mlp_split=0 if packed_split is None else packed_split[0].data_ptr(),
+                n_split=0 if packed_split is None else int(packed_split[1]), guard=0 if guard is None else guard.data_ptr())
 
 
 # ------------------------------------------------------------------ compositing
@@ -465,37 +463,27 @@ def composite(raw, z_vals, white_bkgd=False):
 
 # ------------------------------------------------------------------ fused ray march
 def _raymarch_block(vol_cl, imgs, w2cs, intrinsics, packed, rays_pts, rays_ndc, z_vals, rays_dir, white_bkgd, packed_bf16, packed_split, guard, want, imgs_cl, cur):
-    """Output tensors + the filled mvsnerf_raymarch_args of one batch."""
+    """Output tensors + the filled mvsnerf_raymarch_args (_lib.RaymarchArgs) of one batch."""
     N, S = z_vals.shape
     V = imgs.shape[0]
     F = 8 + 4 * V
-    dev = rays_pts.device
     D, H, W, C = vol_cl.shape
     if C != 8:
         raise RuntimeError("raymarch: the neural volume must have 8 channels")
-    empty = torch.empty
-    out = {
-        "input_feat": empty((N, S, F), device=dev, dtype=torch.float32), "raw": empty((N, S, 4), device=dev, dtype=torch.float32),
-        "rgb_map": empty((N, 3), device=dev, dtype=torch.float32), "weights": empty((N, S), device=dev, dtype=torch.float32),
-        "depth": empty((N,), device=dev, dtype=torch.float32), "alpha": empty((N, S), device=dev, dtype=torch.float32),
-    }
-    for k in want:
-        out[k] = empty((N,), device=dev, dtype=torch.float32)
-    out["_dirs_tmp"] = dirs_tmp = empty((N, 3), device=dev, dtype=torch.float32)
+    shapes = {"input_feat": (N, S, F), "raw": (N, S, 4), "rgb_map": (N, 3), "weights": (N, S), "depth": (N,), "alpha": (N, S), **{k: (N,) for k in want},
+              "_dirs_tmp": (N, 3)}
+    out = {k: torch.empty(sh, device=rays_pts.device, dtype=torch.float32) for k, sh in shapes.items()}
     if imgs_cl is None and FUSED_GATHER:
         imgs_cl = channels_last_images(imgs)
     vp, vl = vol_ptr_layout(vol_cl, cur)
-    a = (
-        vp, D, H, W, dev_f32(imgs, "imgs", cur), V, imgs.shape[2], imgs.shape[3],
-        dev_f32(w2cs, "w2cs", cur), dev_f32(intrinsics, "intrinsics", cur), dev_f32(packed, "packed", cur),
-        dev_f32(rays_pts, "rays_pts", cur), dev_f32(rays_ndc, "rays_ndc", cur), dev_f32(z_vals, "z_vals", cur), dev_f32(rays_dir, "rays_dir", cur),
-        N, S, int(bool(white_bkgd)), dirs_tmp.data_ptr(), out["input_feat"].data_ptr(), out["raw"].data_ptr(),
-        out["rgb_map"].data_ptr(), out["disp"].data_ptr() if "disp" in out else 0, out["acc"].data_ptr() if "acc" in out else 0, out["weights"].data_ptr(),
-        out["depth"].data_ptr(), out["alpha"].data_ptr(), 0 if packed_bf16 is None else packed_bf16.data_ptr(),
-        imgs_cl.data_ptr() if (FUSED_GATHER and imgs_cl is not None) else 0,
-        0 if packed_split is None else packed_split[0].data_ptr(), 0 if packed_split is None else int(packed_split[1]),
-        0 if guard is None else guard.data_ptr(), vl)
-    return out, a
+    ptrs = {k: out[k].data_ptr() if k in out else 0 for k in ("input_feat", "raw", "rgb_map", "disp", "acc", "weights", "depth", "alpha")}
+    return out, _lib.RaymarchArgs(
+        vol=vp, D=D, H=H, W=W, vol_layout=vl, imgs=dev_f32(imgs, "imgs", cur), V=V, IH=imgs.shape[2], IW=imgs.shape[3],
+        imgs_nhwc4=imgs_cl.data_ptr() if (FUSED_GATHER and imgs_cl is not None) else 0,
+        w2c=dev_f32(w2cs, "w2cs", cur), K=dev_f32(intrinsics, "intrinsics", cur), packed_mlp=dev_f32(packed, "packed", cur),
+        rays_pts=dev_f32(rays_pts, "rays_pts", cur), rays_ndc=dev_f32(rays_ndc, "rays_ndc", cur), z_vals=dev_f32(z_vals, "z_vals", cur),
+        rays_dir=dev_f32(rays_dir, "rays_dir", cur), N=N, S=S, white_bkgd=int(bool(white_bkgd)), dirs_tmp=out["_dirs_tmp"].data_ptr(), **ptrs,
+        **_mlp_fields(packed_bf16, packed_split, guard))
 
 
 def raymarch(vol_cl, imgs, w2cs, intrinsics, packed, rays_pts, rays_ndc, z_vals, rays_dir, white_bkgd=False, packed_bf16=None, packed_split=None,
@@ -504,9 +492,8 @@ def raymarch(vol_cl, imgs, w2cs, intrinsics, packed, rays_pts, rays_ndc, z_vals,
     want: which of the optional per-ray maps `disp` / `acc` to produce (rendering() returns neither: it passes ()).
     imgs_cl: the channel-last copy of `imgs` when the caller already holds it (renderer's per-scene cache)."""
     _need_no_grad(vol_cl, imgs, rays_pts, rays_ndc, z_vals, rays_dir, op="raymarch")
-    out, a = _raymarch_block(vol_cl, imgs, w2cs, intrinsics, packed, rays_pts, rays_ndc, z_vals, rays_dir, white_bkgd, packed_bf16, packed_split,
-                             guard, want, imgs_cl, torch.cuda.current_device())
-    blk = _lib.RaymarchArgs(*a)
+    out, blk = _raymarch_block(vol_cl, imgs, w2cs, intrinsics, packed, rays_pts, rays_ndc, z_vals, rays_dir, white_bkgd, packed_bf16, packed_split,
+                               guard, want, imgs_cl, torch.cuda.current_device())
     check(_lib.lib().mvsnerf_raymarch_fwd(ctypes.byref(blk), stream_ptr()), "raymarch_fwd")
     return out
 
@@ -520,8 +507,8 @@ def raymarch_batched(vol_cl, imgs, w2cs, intrinsics, packed, ray_batches, white_
     outs, blocks = [], (_lib.RaymarchArgs * len(ray_batches))()
     for k, (pts, ndc, z, rdir) in enumerate(ray_batches):
         _need_no_grad(vol_cl, imgs, pts, ndc, z, rdir, op="raymarch_batched")
-        out, a = _raymarch_block(vol_cl, imgs, w2cs, intrinsics, packed, pts, ndc, z, rdir, white_bkgd, packed_bf16, packed_split, guard, want, imgs_cl, cur)
-        blocks[k] = _lib.RaymarchArgs(*a)
+        out, blocks[k] = _raymarch_block(vol_cl, imgs, w2cs, intrinsics, packed, pts, ndc, z, rdir, white_bkgd, packed_bf16, packed_split, guard, want,
+                                         imgs_cl, cur)
         outs.append(out)
     check(_lib.lib().mvsnerf_raymarch_fwd_batched(blocks, len(ray_batches), stream_ptr()), "raymarch_fwd_batched")
     return outs
@@ -558,13 +545,12 @@ def render_pixels(vol_cl, imgs, w2cs, intrinsics, packed, H, W, K_tgt, c2w_tgt, 
     c = _Keep()
     vp, vl = vol_ptr_layout(vol_cl)
     a = _lib.RenderArgs(
-        vp, D, Hv, Wv, channels_last_images(imgs).data_ptr(), V, imgs.shape[2], imgs.shape[3],
-        c(w2cs, "w2cs"), c(intrinsics, "intrinsics"), packed.data_ptr(), 0 if packed_bf16 is None else packed_bf16.data_ptr(),
-        c(K_tgt, "K_tgt"), c(c2w_tgt, "c2w_tgt"), c(K_ref, "K_ref"), c(w2c_ref, "w2c_ref"), c(nf_tgt, "near_far_tgt"), c(nf_ref, "near_far_ref"),
-        W, H, int(pad), int(bool(lindisp)), 0 if ref_hw is None else int(ref_hw[1]), 0 if ref_hw is None else int(ref_hw[0]), int(first_pixel), n, int(N_samples), int(bool(white_bkgd)), B,
-        ws.data_ptr(), ws_n, out["rgb"].data_ptr(), *[0 if out[k] is None else out[k].data_ptr() for k in ("depth", "acc", "disp")],
-        0 if packed_split is None else packed_split[0].data_ptr(), 0 if packed_split is None else int(packed_split[1]),
-        0 if guard is None else guard.data_ptr(), vl)
+        vol=vp, D=D, H=Hv, W=Wv, vol_layout=vl, imgs_nhwc4=channels_last_images(imgs).data_ptr(), V=V, IH=imgs.shape[2], IW=imgs.shape[3],
+        w2c=c(w2cs, "w2cs"), K=c(intrinsics, "intrinsics"), packed_mlp=packed.data_ptr(), K_tgt=c(K_tgt, "K_tgt"), c2w_tgt=c(c2w_tgt, "c2w_tgt"),
+        K_ref=c(K_ref, "K_ref"), w2c_ref=c(w2c_ref, "w2c_ref"), near_far_tgt=c(nf_tgt, "near_far_tgt"), near_far_ref=c(nf_ref, "near_far_ref"),
+        W_img=W, H_img=H, pad=int(pad), lindisp=int(bool(lindisp)), W_ref=0 if ref_hw is None else int(ref_hw[1]), H_ref=0 if ref_hw is None else int(ref_hw[0]),
+        first_pixel=int(first_pixel), n_pixels=n, S=int(N_samples), white_bkgd=int(bool(white_bkgd)), batch_rays=B, workspace=ws.data_ptr(),
+        workspace_floats=ws_n, **{k: 0 if out[k] is None else out[k].data_ptr() for k in out}, **_mlp_fields(packed_bf16, packed_split, guard))
     check(lib.mvsnerf_render_pixels_fwd(ctypes.byref(a), stream_ptr()), "render_pixels_fwd")
     return {k: v for k, v in out.items() if v is not None}
 

@@ -47,6 +47,21 @@ def test_c_abi_rejects_bad_arguments_without_launching():
     assert not hasattr(l, "mvsnerf_tune") and not hasattr(l, "mvsnerf_debug_set_census")     # the library has no A/B switches (csrc/knobs.h: constants)
 
 
+def test_ray_march_rejects_a_guard_without_fp16_planes_before_launching():
+    # a whole batch (N > 0) on host buffers: the MLP choice is validated before the lookups or the ray generation are enqueued
+    l = _lib.lib()
+    buf = (ctypes.c_float * 64)()
+    p = ctypes.addressof(buf)
+    common = dict(vol=p, D=4, H=4, W=4, imgs_nhwc4=p, V=1, IH=4, IW=4, w2c=p, K=p, packed_mlp=p, S=1, guard=p)
+    rm = dict(common, imgs=p, rays_pts=p, rays_ndc=p, z_vals=p, rays_dir=p, N=1, dirs_tmp=p, input_feat=p, raw=p)
+    rp = dict(common, K_tgt=p, c2w_tgt=p, K_ref=p, w2c_ref=p, near_far_tgt=p, near_far_ref=p, W_img=2, H_img=2, n_pixels=1, batch_rays=1,
+              workspace=p, workspace_floats=l.mvsnerf_render_workspace_floats(1, 1, 1), rgb=p)
+    for split in (dict(), dict(packed_mlp_split=p, n_split=2)):          # no split planes; bf16x3 planes instead of fp16x3
+        assert l.mvsnerf_raymarch_fwd(ctypes.byref(_lib.RaymarchArgs(**rm, **split)), 0) == EINVAL
+        assert l.mvsnerf_raymarch_fwd_batched(ctypes.byref(_lib.RaymarchArgs(**rm, **split)), 1, 0) == EINVAL
+        assert l.mvsnerf_render_pixels_fwd(ctypes.byref(_lib.RenderArgs(**rp, **split)), 0) == EINVAL
+
+
 def test_python_layer_raises_and_names_the_op():
     with pytest.raises(RuntimeError, match="volume_sample_fwd failed: invalid argument"):
         _lib.check(EINVAL, "volume_sample_fwd")
@@ -56,6 +71,8 @@ def test_python_layer_raises_and_names_the_op():
         ops.volume_sample(torch.zeros(4, 4, 4, 8), torch.zeros(2, 3))                         # host tensors: no CPU fallback
     with pytest.raises(RuntimeError, match="feat_dim 21 unsupported"):
         ops.mlp_pack([], [], 21)
+    with pytest.raises(ValueError, match="a guard needs the fp16x3 split planes"):                  # as mvsnerf_raymarch_fwd: EINVAL
+        ops.mlp_forward(None, 20, 0, 3, 0, 20, 0, 3, 1, 1, False, "cpu", packed_split=(None, 2), guard=torch.zeros(4))
 
 
 def test_missing_library_is_loud(monkeypatch):
