@@ -224,6 +224,43 @@ int mvsnerf_conv3d_f16x3_fwd(const float* x, const float* scale, const float* sh
 int mvsnerf_conv3d_f16x3_guarded_fwd(const float* x, const float* scale, const float* shift, int Cin, int cin_ld, int D, int H, int W,
                                      const void* w_f16x3, const float* w_f32, int Cout, int stride, float* out, float* stats_part,
                                      int* guard, int consume, void* stream);
+/* ---- rendering a fine-tuned scene (train_mvs_nerf_finetuning_pl.py:192-252, validation_step of the fine-tuning script) ----
+ * gather_colorvol: gen_pts_feats of --use_color_volume (renderer.py:134-135: the per-sample feature row is ONE trilinear lookup of the
+ *   (8 + 4V)-channel volume) and gen_dir_feature (renderer.py:111-122, 142-147) in one launch.  vol: C channels per voxel, C % 4 == 0,
+ *   8 < C <= 40 (other C: MVSNERF_EUNSUPPORTED), memory order vol_layout, 16-byte aligned; ndc[N][S][3]; feat[N*S][feat_stride]
+ *   (feat_stride % 4 == 0, 16-byte aligned) receives channels 0..C-1, bit-identical to mvsnerf_volume_sample_fwd's; rays_dir[N][3] and
+ *   dirs_out[N][3] may both be NULL (lookup only), w2c_ref[4][4] may be NULL (no rotation): dirs_out = mvsnerf_dir_feature_fwd(normalize = 1).
+ *   force_offsets64 != 0 runs the 64-bit-offset form of the kernel whatever the sizes (what a volume or batch beyond 2^31 floats takes; for tests).
+ * raymarch_colorvol_fwd_batched: K batches of mvsnerf_raymarch_fwd_batched on a C = 8 + 4V-channel colour volume (a->vol: [..][C] in a->vol_layout):
+ *   gather_colorvol instead of the image gather, then the batch's MLP choice and compositing.  imgs, imgs_nhwc4, K and rays_pts are not read.
+ * render_rays: the chunk loop of that validation_step enqueued from one host call - per sub-batch of batch_rays rays taken from
+ *   rays[first_ray .. first_ray + n_rays) ([..][8] = origin, direction, near, far): coarse depths near (1 - t[s]) + far t[s] (lindisp: in
+ *   disparity) with points and reference-view NDC coordinates; with a density volume and n_importance > 0 ray_marcher_fine on
+ *   u[first_ray + ..][n_importance] and the points of the merged S + n_importance depths; the ray march (C == 8: image gather as
+ *   mvsnerf_render_pixels_fwd; C == 8 + 4V: gather_colorvol, no images / K needed; else MVSNERF_EUNSUPPORTED); rgb[n_rays][3] and, when
+ *   non-NULL, depth / acc / disp[n_rays] leave the call.  Results do not depend on batch_rays.  workspace: render_rays_workspace_floats(
+ *   batch_rays, S, n_importance, F = 8 + 4V) floats, 16-byte aligned, reused by every sub-batch.  Arguments are validated before the first launch. */
+int mvsnerf_gather_colorvol_fwd(const float* vol, int D, int H, int W, int C, const float* ndc, int64_t N, int S,
+                                const float* rays_dir, const float* w2c_ref, float* feat, int feat_stride, float* dirs_out,
+                                int vol_layout, int force_offsets64, void* stream);
+int mvsnerf_raymarch_colorvol_fwd_batched(const mvsnerf_raymarch_args* a, int K, int C, void* stream);
+typedef struct {
+    const float* vol; int D, H, W, C, vol_layout;  /* C = 8 (neural volume + source images) or 8 + 4V (colour volume) */
+    const float* imgs_nhwc4; int V, IH, IW;        /* [V][IH][IW][4] source images (C == 8; else NULL); V source views either way */
+    const float* w2c; const float* K;              /* [V][4][4], [V][3][3] source views (C == 8; else NULL) */
+    const float* K_ref; const float* w2c_ref; const float* near_far_ref;   /* reference view [3][3], [4][4], [2] */
+    int W_ref, H_ref, pad, lindisp;
+    const float* packed_mlp; const void* packed_mlp_bf16; const void* packed_mlp_split; int n_split; int* guard;   /* as mvsnerf_render_args */
+    const float* rays; int64_t first_ray, n_rays;  /* [>= first_ray + n_rays][8] */
+    const float* t; int S;                         /* [S] = linspace(0, 1, S) */
+    const float* density; int DD, DH, DW;          /* NULL, or the density volume [DD][DH][DW] of ray_marcher_fine */
+    const float* u; int n_importance;              /* NULL / 0, or uniform draws [>= first_ray + n_rays][n_importance] */
+    int white_bkgd, batch_rays;
+    float* workspace; size_t workspace_floats;
+    float* rgb; float* depth; float* acc; float* disp;     /* rgb required, others may be NULL */
+} mvsnerf_render_rays_args;
+size_t mvsnerf_render_rays_workspace_floats(int batch_rays, int S, int n_importance, int F);
+int mvsnerf_render_rays_fwd(const mvsnerf_render_rays_args* a, void* stream);
 
 #ifdef __cplusplus
 }

@@ -77,6 +77,26 @@ class RenderArgs(ctypes.Structure):
     ]
 
 
+class RenderRaysArgs(ctypes.Structure):
+    """mvsnerf_render_rays_args (include/mvsnerf_hip_internal.h)."""
+    __slots__ = ()
+    _fields_ = [
+        ("vol", _c_fp), ("D", _c_i), ("H", _c_i), ("W", _c_i), ("C", _c_i), ("vol_layout", _c_i),
+        ("imgs_nhwc4", _c_fp), ("V", _c_i), ("IH", _c_i), ("IW", _c_i),
+        ("w2c", _c_fp), ("K", _c_fp),
+        ("K_ref", _c_fp), ("w2c_ref", _c_fp), ("near_far_ref", _c_fp),
+        ("W_ref", _c_i), ("H_ref", _c_i), ("pad", _c_i), ("lindisp", _c_i),
+        ("packed_mlp", _c_fp), ("packed_mlp_bf16", _c_fp), ("packed_mlp_split", _c_fp), ("n_split", _c_i), ("guard", _c_fp),
+        ("rays", _c_fp), ("first_ray", _c_l), ("n_rays", _c_l),
+        ("t", _c_fp), ("S", _c_i),
+        ("density", _c_fp), ("DD", _c_i), ("DH", _c_i), ("DW", _c_i),
+        ("u", _c_fp), ("n_importance", _c_i),
+        ("white_bkgd", _c_i), ("batch_rays", _c_i),
+        ("workspace", _c_fp), ("workspace_floats", ctypes.c_size_t),
+        ("rgb", _c_fp), ("depth", _c_fp), ("acc", _c_fp), ("disp", _c_fp),
+    ]
+
+
 class SweepConv0Args(ctypes.Structure):
     """mvsnerf_sweep_conv0_args (include/mvsnerf_hip.h): the guarded head of a no-grad scene encode."""
     __slots__ = ()
@@ -227,6 +247,10 @@ SIGNATURES = {
     "mvsnerf_raymarch_fwd_batched": (_c_i, [ctypes.POINTER(RaymarchArgs), _c_i, _c_fp]),
     "mvsnerf_raymarch_train_fwd": (_c_i, [ctypes.POINTER(RaymarchTrainArgs), _c_fp]),
     "mvsnerf_raymarch_bwd": (_c_i, [ctypes.POINTER(RaymarchBwdArgs), _c_fp]),
+    "mvsnerf_gather_colorvol_fwd": (_c_i, [_c_fp] + [_c_i] * 4 + [_c_fp, _c_l, _c_i, _c_fp, _c_fp, _c_fp, _c_i, _c_fp, _c_i, _c_i, _c_fp]),
+    "mvsnerf_raymarch_colorvol_fwd_batched": (_c_i, [ctypes.POINTER(RaymarchArgs), _c_i, _c_i, _c_fp]),
+    "mvsnerf_render_rays_workspace_floats": (ctypes.c_size_t, [_c_i] * 4),
+    "mvsnerf_render_rays_fwd": (_c_i, [ctypes.POINTER(RenderRaysArgs), _c_fp]),
 }
 
 _lib = None

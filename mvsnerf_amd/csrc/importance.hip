@@ -7,6 +7,7 @@
 // deterministic function of the inputs.  One 64-lane wave per ray; per-wave arrays live in LDS.  All HBM/latency-bound
 // integer+fp32 work: no MFMA.
 #include "common.h"
+#include "march.h"
 
 constexpr int IMP_MAX = 512;     // max samples / bins / importance samples per ray held in LDS
 
@@ -189,19 +190,45 @@ extern "C" int mvsnerf_ray_marcher_fine_fwd(const float* density, int D, int H, 
     return MVSNERF_OK;
 }
 
+// The coarse depths of ray_marcher (data/ray_utils.py:152-197 without jitter) as train.ray_marcher forms them with torch: (1 - t) rounded, two
+// rounded products, one sum; lindisp: the reciprocals are IEEE divisions like torch's.
+__device__ __forceinline__ float coarse_depth(float near, float far, float t, int lindisp)
+{
+#pragma clang fp contract(off)
+    const float omt = 1.0f - t;
+    if (lindisp) {
+        const float a = (1.0f / near) * omt, b = (1.0f / far) * t;
+        return 1.0f / (a + b);
+    }
+    const float a = near * omt, b = far * t;
+    return a + b;
+}
+
 // pts = o + d*z and their reference-view NDC coordinates (get_ndc_coordinate, utils.py:112-146), one thread per sample.
-// rays_o: [N][3], or [1][3] broadcast when o_stride == 0.
-__global__ __launch_bounds__(256) void ray_points_kernel(const float* __restrict__ rays_o, int o_stride, const float* __restrict__ rays_d,
+// rays_o: [N][o_stride], or [1][3] broadcast when o_stride == 0; rays_d: [N][d_stride].
+// tvals != NULL: the depths are not read but FORMED here from the rays' own (near, far) = near_far_rays[n * nf_stride + 0 / 1] and t = tvals[s]
+// and written to z_out (the coarse depths of a frame rendered from explicit rays, mvsnerf_render_rays_fwd); dir_out != NULL: rays_d compacted to [N][3].
+__global__ __launch_bounds__(256) void ray_points_kernel(const float* __restrict__ rays_o, int o_stride, const float* __restrict__ rays_d, int d_stride,
                                                          const float* __restrict__ z_vals, const float* __restrict__ w2c, const float* __restrict__ Kr,
                                                          const float* __restrict__ nf_ref, int W_ref, int H_ref, int pad, int lindisp,
-                                                         int64_t N, int S, float* __restrict__ pts, float* __restrict__ ndc)
+                                                         int64_t N, int S, float* __restrict__ pts, float* __restrict__ ndc,
+                                                         const float* __restrict__ tvals, const float* __restrict__ near_far_rays, int nf_stride,
+                                                         float* __restrict__ z_out, float* __restrict__ dir_out)
 {
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= N * S) return;
     const int64_t n = t / S;
-    const float z = z_vals[t];
     const float* o = rays_o + n * o_stride;
-    const float* d = rays_d + n * 3;
+    const float* d = rays_d + n * d_stride;
+    float z;
+    if (tvals) {
+        const int s = (int)(t - n * S);
+        z = coarse_depth(near_far_rays[n * nf_stride], near_far_rays[n * nf_stride + 1], tvals[s], lindisp);
+        z_out[t] = z;
+        if (dir_out && s == 0) { dir_out[n * 3 + 0] = d[0]; dir_out[n * 3 + 1] = d[1]; dir_out[n * 3 + 2] = d[2]; }
+    } else {
+        z = z_vals[t];
+    }
     const float px = o[0] + d[0] * z, py = o[1] + d[1] * z, pz = o[2] + d[2] * z;      // o + d*z
     pts[t * 3 + 0] = px; pts[t * 3 + 1] = py; pts[t * 3 + 2] = pz;
     if (!ndc) return;
@@ -223,15 +250,27 @@ __global__ __launch_bounds__(256) void ray_points_kernel(const float* __restrict
     ndc[t * 3 + 0] = nx; ndc[t * 3 + 1] = ny; ndc[t * 3 + 2] = nz;
 }
 
+// march.h: the launcher behind mvsnerf_ray_points_fwd, with the strides of rays kept as [N][8] rows and the depth-forming form of the kernel
+int mvs_ray_points(const float* rays_o, int o_stride, const float* rays_d, int d_stride, const float* z_vals,
+                   const float* w2c_ref, const float* K_ref, const float* near_far_ref, int W_ref, int H_ref, int pad, int lindisp,
+                   int64_t N, int S, float* rays_pts, float* rays_ndc,
+                   const float* tvals, const float* near_far_rays, int nf_stride, float* z_out, float* dir_out, void* stream)
+{
+    if (!rays_o || !rays_d || !rays_pts || N < 0 || S < 1) return MVSNERF_EINVAL;
+    if (tvals ? (!near_far_rays || !z_out) : !z_vals) return MVSNERF_EINVAL;
+    if (rays_ndc && (!w2c_ref || !K_ref || !near_far_ref || W_ref < 2 || H_ref < 2 || pad < 0)) return MVSNERF_EINVAL;
+    if (N == 0) return MVSNERF_OK;
+    ray_points_kernel<<<mvs_cdiv(N * S, 256), 256, 0, (hipStream_t)stream>>>(rays_o, o_stride, rays_d, d_stride, z_vals, w2c_ref, K_ref, near_far_ref,
+                                                                            W_ref, H_ref, pad, lindisp, N, S, rays_pts, rays_ndc,
+                                                                            tvals, near_far_rays, nf_stride, z_out, dir_out);
+    MVS_LAUNCH_CHECK();
+    return MVSNERF_OK;
+}
+
 extern "C" int mvsnerf_ray_points_fwd(const float* rays_o, int o_is_per_ray, const float* rays_d, const float* z_vals,
                                       const float* w2c_ref, const float* K_ref, const float* near_far_ref, int W_ref, int H_ref, int pad, int lindisp,
                                       int64_t N, int S, float* rays_pts, float* rays_ndc, void* stream)
 {
-    if (!rays_o || !rays_d || !z_vals || !rays_pts || N < 0 || S < 1) return MVSNERF_EINVAL;
-    if (rays_ndc && (!w2c_ref || !K_ref || !near_far_ref || W_ref < 2 || H_ref < 2 || pad < 0)) return MVSNERF_EINVAL;
-    if (N == 0) return MVSNERF_OK;
-    ray_points_kernel<<<mvs_cdiv(N * S, 256), 256, 0, (hipStream_t)stream>>>(rays_o, o_is_per_ray ? 3 : 0, rays_d, z_vals, w2c_ref, K_ref, near_far_ref,
-                                                                            W_ref, H_ref, pad, lindisp, N, S, rays_pts, rays_ndc);
-    MVS_LAUNCH_CHECK();
-    return MVSNERF_OK;
+    return mvs_ray_points(rays_o, o_is_per_ray ? 3 : 0, rays_d, 3, z_vals, w2c_ref, K_ref, near_far_ref, W_ref, H_ref, pad, lindisp, N, S, rays_pts, rays_ndc,
+                          nullptr, nullptr, 0, nullptr, nullptr, stream);
 }

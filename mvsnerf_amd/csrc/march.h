@@ -5,7 +5,8 @@
 
 // N rays x S samples of rendering() (renderer.py:138-165): an mvsnerf_raymarch_args batch or one sub-batch of mvsnerf_render_args
 struct MarchBatch {
-    const float* vol; int D, H, W, vol_layout;      // 8-channel volume, memory order MVSNERF_VOL_*
+    const float* vol; int D, H, W, vol_layout;      // volume, memory order MVSNERF_VOL_*
+    int C;                                          // its channels: 8 (neural volume; colours gathered from the source images) or 8 + 4V (colour volume: imgs*, K, pts unused)
     const float* imgs; const float* imgs_nhwc4; int V, IH, IW;   // [V][3][IH][IW] (three stand-alone lookups), [V][IH][IW][4] or NULL (one gather)
     const float* w2c; const float* K;               // [V][4][4], [V][3][3]; view 0 is the reference view
     const float* pts; const float* ndc; const float* z; const float* rays_dir;   // [N][S][3], [N][S][3], [N][S], [N][3]
@@ -33,3 +34,9 @@ int mvs_guard_consume(int* guard, hipStream_t st);
 // When 128 % S != 0 the launcher enqueues the compositing as a separate mvs_composite_fwd launch.
 bool mvs_raymarch_fused_applies(const MarchBatch& b);
 int mvs_raymarch_fused_fwd(const MarchBatch& b, hipStream_t st);
+// importance.hip: mvsnerf_ray_points_fwd with row strides for the origins / directions (rays kept as [N][8] rows) and, with tvals != NULL, the
+// coarse depths near (1 - t) + far t formed in the launch from near_far_rays[n * nf_stride + 0 / 1] and written to z_out (dir_out: directions as [N][3])
+int mvs_ray_points(const float* rays_o, int o_stride, const float* rays_d, int d_stride, const float* z_vals,
+                   const float* w2c_ref, const float* K_ref, const float* near_far_ref, int W_ref, int H_ref, int pad, int lindisp,
+                   int64_t N, int S, float* rays_pts, float* rays_ndc,
+                   const float* tvals, const float* near_far_rays, int nf_stride, float* z_out, float* dir_out, void* stream);

@@ -36,11 +36,15 @@ static bool mlp_choice_ok(const MarchBatch& b) { return !b.guard || (b.packed_sp
 static int march_batch(const MarchBatch& b, hipStream_t st)
 {
     if (!mlp_choice_ok(b)) return MVSNERF_EINVAL;
-    // fp32 MLP: lookups, MLP and (when a tile holds whole rays) compositing in one launch, when the shapes allow it
-    if (mvs_raymarch_fused_applies(b)) return mvs_raymarch_fused_fwd(b, st);
     const int F = 8 + 4 * b.V;
+    if (b.C != 8 && b.C != F) return MVSNERF_EUNSUPPORTED;
+    // fp32 MLP: lookups, MLP and (when a tile holds whole rays) compositing in one launch, when the shapes allow it
+    if (b.C == 8 && mvs_raymarch_fused_applies(b)) return mvs_raymarch_fused_fwd(b, st);
     int rc;
-    if (b.imgs_nhwc4) {
+    if (b.C != 8) {
+        // --use_color_volume (renderer.py:134-135): the feature row is one lookup of the (8 + 4V)-channel volume; same launch: the direction feature
+        if ((rc = mvsnerf_gather_colorvol_fwd(b.vol, b.D, b.H, b.W, b.C, b.ndc, b.N, b.S, b.rays_dir, b.w2c, b.feat, F, b.dirs, b.vol_layout, 0, st))) return rc;
+    } else if (b.imgs_nhwc4) {
         // gen_dir_feature + gen_pts_feats in one launch (channel-last source images supplied by the caller)
         if ((rc = mvsnerf_gather_fwd(b.vol, b.D, b.H, b.W, b.imgs_nhwc4, b.V, b.IH, b.IW, b.w2c, b.K, b.pts, b.ndc, b.N, b.S, b.rays_dir, b.feat, F,
                                      b.dirs, b.vol_layout, st))) return rc;
@@ -72,7 +76,7 @@ extern "C" int mvsnerf_raymarch_fwd(const mvsnerf_raymarch_args* a, void* stream
         !a->rays_dir || !a->dirs_tmp || !a->input_feat || !a->raw)
         return MVSNERF_EINVAL;
     if (a->N < 0 || a->S < 1 || a->V < 1) return MVSNERF_EINVAL;
-    return march_batch({.vol = a->vol, .D = a->D, .H = a->H, .W = a->W, .vol_layout = a->vol_layout, .imgs = a->imgs, .imgs_nhwc4 = a->imgs_nhwc4,
+    return march_batch({.vol = a->vol, .D = a->D, .H = a->H, .W = a->W, .vol_layout = a->vol_layout, .C = 8, .imgs = a->imgs, .imgs_nhwc4 = a->imgs_nhwc4,
                         .V = a->V, .IH = a->IH, .IW = a->IW, .w2c = a->w2c, .K = a->K, .pts = a->rays_pts, .ndc = a->rays_ndc, .z = a->z_vals,
                         .rays_dir = a->rays_dir, .N = a->N, .S = a->S, .white_bkgd = a->white_bkgd, .feat = a->input_feat, .dirs = a->dirs_tmp, .raw = a->raw,
                         .rgb_map = a->rgb_map, .disp = a->disp, .acc = a->acc, .weights = a->weights, .depth = a->depth, .alpha = a->alpha,
@@ -131,7 +135,7 @@ extern "C" int mvsnerf_render_pixels_fwd(const mvsnerf_render_args* a, void* str
     float* rdir = raw + r4(4 * P);
     float* dirs = rdir + r4(3 * B);
     // every sub-batch: the same workspace slices, its own ray count and output rows (set in the loop); weights and alpha are not produced
-    MarchBatch b{.vol = a->vol, .D = a->D, .H = a->H, .W = a->W, .vol_layout = a->vol_layout, .imgs_nhwc4 = a->imgs_nhwc4, .V = a->V, .IH = a->IH,
+    MarchBatch b{.vol = a->vol, .D = a->D, .H = a->H, .W = a->W, .vol_layout = a->vol_layout, .C = 8, .imgs_nhwc4 = a->imgs_nhwc4, .V = a->V, .IH = a->IH,
                  .IW = a->IW, .w2c = a->w2c, .K = a->K, .pts = pts, .ndc = ndc, .z = z, .rays_dir = rdir, .S = S, .white_bkgd = a->white_bkgd,
                  .feat = feat, .dirs = dirs, .raw = raw, .packed = a->packed_mlp, .packed_bf16 = a->packed_mlp_bf16,
                  .packed_split = a->packed_mlp_split, .n_split = a->n_split, .guard = a->guard};
@@ -141,6 +145,101 @@ extern "C" int mvsnerf_render_pixels_fwd(const mvsnerf_render_args* a, void* str
         if (int rc = mvsnerf_raygen_fwd(nullptr, nullptr, a->first_pixel + off, a->W_img, a->H_img, a->W_ref, a->H_ref, a->K_tgt, a->c2w_tgt, a->K_ref,
                                         a->w2c_ref, a->near_far_tgt, a->near_far_ref, a->pad, a->lindisp, nullptr, b.N, S, pts, rdir, ndc, z, nullptr, stream))
             return rc;
+        b.rgb_map = a->rgb + off * 3;
+        b.disp = a->disp ? a->disp + off : nullptr;
+        b.acc = a->acc ? a->acc + off : nullptr;
+        b.depth = a->depth ? a->depth + off : nullptr;
+        if (int rc = march_batch(b, (hipStream_t)stream)) return rc;
+    }
+    return MVSNERF_OK;
+}
+
+// K batches on a colour volume (rendering_batched under --use_color_volume): the stable batch struct, the channel count beside it
+extern "C" int mvsnerf_raymarch_colorvol_fwd_batched(const mvsnerf_raymarch_args* a, int K, int C, void* stream)
+{
+    if (!a || K < 0) return MVSNERF_EINVAL;
+    for (int k = 0; k < K; ++k) {
+        const mvsnerf_raymarch_args* x = a + k;
+        if (!x->vol || !x->w2c || !x->packed_mlp || !x->rays_ndc || !x->z_vals || !x->rays_dir || !x->dirs_tmp || !x->input_feat || !x->raw) return MVSNERF_EINVAL;
+        if (x->N < 0 || x->S < 1 || x->V < 1) return MVSNERF_EINVAL;
+        if (C != 8 + 4 * x->V) return MVSNERF_EUNSUPPORTED;
+        if (int rc = march_batch({.vol = x->vol, .D = x->D, .H = x->H, .W = x->W, .vol_layout = x->vol_layout, .C = C, .V = x->V, .w2c = x->w2c,
+                                  .ndc = x->rays_ndc, .z = x->z_vals, .rays_dir = x->rays_dir, .N = x->N, .S = x->S, .white_bkgd = x->white_bkgd,
+                                  .feat = x->input_feat, .dirs = x->dirs_tmp, .raw = x->raw, .rgb_map = x->rgb_map, .disp = x->disp, .acc = x->acc,
+                                  .weights = x->weights, .depth = x->depth, .alpha = x->alpha, .packed = x->packed_mlp, .packed_bf16 = x->packed_mlp_bf16,
+                                  .packed_split = x->packed_mlp_split, .n_split = x->n_split, .guard = x->guard}, (hipStream_t)stream)) return rc;
+    }
+    return MVSNERF_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// A frame of a fine-tuned scene from explicit rays = the chunk loop of the fine-tuning script's validation_step
+// (train_mvs_nerf_finetuning_pl.py:192-252: ray_marcher -> get_ndc_coordinate -> [ray_marcher_fine -> get_ndc_coordinate] -> rendering per chunk),
+// enqueued from ONE host call like mvsnerf_render_pixels_fwd above.  Per sub-batch: coarse depths + points + NDC (one launch), with a density
+// volume the merged depths (ray_marcher_fine) and their points (two launches), then march_batch (image gather or colour-volume gather, MLP,
+// compositing).  Temporaries live in the caller's workspace, reused by every sub-batch (stream order makes that safe).
+// ---------------------------------------------------------------------------------------------
+static int64_t ws_r4(int64_t n) { return (n + 3) & ~(int64_t)3; }       // every workspace block starts on 16 bytes
+
+static size_t render_rays_ws_floats(int64_t B, int S, int NI, int F)
+{
+    const int64_t P = B * (S + NI);
+    // pts, ndc (3P each), z (P), coarse z (B*S, importance sampling only), feat (F*P), raw (4P), rays_dir + dirs (3B each)
+    return (size_t)(ws_r4(3 * P) * 2 + ws_r4(P) + (NI > 0 ? ws_r4(B * S) : 0) + ws_r4((int64_t)F * P) + ws_r4(4 * P) + ws_r4(3 * B) * 2);
+}
+
+extern "C" size_t mvsnerf_render_rays_workspace_floats(int batch_rays, int S, int n_importance, int F)
+{
+    if (batch_rays < 1 || S < 1 || n_importance < 0 || F < 12 || (F & 3)) return 0;
+    return render_rays_ws_floats(batch_rays, S, n_importance, F);
+}
+
+extern "C" int mvsnerf_render_rays_fwd(const mvsnerf_render_rays_args* a, void* stream)
+{
+    if (!a) return MVSNERF_EINVAL;
+    if (a->n_rays == 0) return MVSNERF_OK;                         // empty ray range (a rank with no chunks): nothing to do
+    if (!a->vol || !a->packed_mlp || !a->K_ref || !a->w2c_ref || !a->near_far_ref || !a->rays || !a->t || !a->workspace || !a->rgb) return MVSNERF_EINVAL;
+    if (a->n_rays < 0 || a->first_ray < 0 || a->S < 1 || a->V < 1 || a->batch_rays < 1 || a->W_ref < 2 || a->H_ref < 2 || a->pad < 0 ||
+        a->D < 1 || a->H < 1 || a->W < 1 || a->n_importance < 0)
+        return MVSNERF_EINVAL;
+    if (a->vol_layout != MVSNERF_VOL_DHWC && a->vol_layout != MVSNERF_VOL_HWDC) return MVSNERF_EINVAL;
+    const bool fine = a->density && a->n_importance > 0;
+    if (fine && (!a->u || a->DD < 1 || a->DH < 1 || a->DW < 1 || a->S < 3)) return MVSNERF_EINVAL;
+    const int F = 8 + 4 * a->V, S = a->S, NI = fine ? a->n_importance : 0, St = S + NI;
+    if (a->C != 8 && a->C != F) return MVSNERF_EUNSUPPORTED;
+    if (F > 40 || (fine && (S > 512 || NI > 512))) return MVSNERF_EUNSUPPORTED;
+    if (a->C == 8 && (!a->imgs_nhwc4 || !a->w2c || !a->K || a->IH < 2 || a->IW < 2)) return MVSNERF_EINVAL;
+    if (a->workspace_floats < render_rays_ws_floats(a->batch_rays, S, NI, F)) return MVSNERF_EINVAL;
+    if (!mvs_aligned16(a->workspace) || !mvs_aligned16(a->vol) || !mvs_aligned16(a->packed_mlp) || (a->C == 8 && !mvs_aligned16(a->imgs_nhwc4))) return MVSNERF_EALIGN;
+    const int64_t B = a->batch_rays, P = B * St;
+    float* pts = a->workspace;
+    float* ndc = pts + ws_r4(3 * P);
+    float* z = ndc + ws_r4(3 * P);
+    float* zc = z + ws_r4(P);                                      // coarse depths of a sub-batch (importance sampling only; else z itself)
+    float* feat = zc + (NI > 0 ? ws_r4(B * S) : 0);
+    float* raw = feat + ws_r4((int64_t)F * P);
+    float* rdir = raw + ws_r4(4 * P);
+    float* dirs = rdir + ws_r4(3 * B);
+    // a colour volume needs the reference view's w2c only (the direction feature); the image gather reads view 0 of w2c as the reference view
+    MarchBatch b{.vol = a->vol, .D = a->D, .H = a->H, .W = a->W, .vol_layout = a->vol_layout, .C = a->C, .imgs_nhwc4 = a->C == 8 ? a->imgs_nhwc4 : nullptr,
+                 .V = a->V, .IH = a->IH, .IW = a->IW, .w2c = a->C == 8 ? a->w2c : a->w2c_ref, .K = a->K, .pts = pts, .ndc = ndc, .z = z, .rays_dir = rdir,
+                 .S = St, .white_bkgd = a->white_bkgd, .feat = feat, .dirs = dirs, .raw = raw, .packed = a->packed_mlp, .packed_bf16 = a->packed_mlp_bf16,
+                 .packed_split = a->packed_mlp_split, .n_split = a->n_split, .guard = a->guard};
+    if (!mlp_choice_ok(b)) return MVSNERF_EINVAL;
+    for (int64_t off = 0; off < a->n_rays; off += B) {
+        b.N = a->n_rays - off < B ? a->n_rays - off : B;
+        const float* r = a->rays + (a->first_ray + off) * 8;
+        // ray_marcher + get_ndc_coordinate: depths from (near, far) = r[6], r[7] of every ray and t, points, NDC; directions compacted to [N][3]
+        if (int rc = mvs_ray_points(r, 8, r + 3, 8, nullptr, a->w2c_ref, a->K_ref, a->near_far_ref, a->W_ref, a->H_ref, a->pad, a->lindisp, b.N, S, pts, ndc,
+                                    a->t, r + 6, 8, fine ? zc : z, rdir, stream))
+            return rc;
+        if (fine) {
+            // ray_marcher_fine + get_ndc_coordinate of the merged depths
+            if (int rc = mvsnerf_ray_marcher_fine_fwd(a->density, a->DD, a->DH, a->DW, ndc, zc, a->u + (a->first_ray + off) * NI, b.N, S, NI, z, stream)) return rc;
+            if (int rc = mvs_ray_points(r, 8, r + 3, 8, z, a->w2c_ref, a->K_ref, a->near_far_ref, a->W_ref, a->H_ref, a->pad, a->lindisp, b.N, St, pts, ndc,
+                                        nullptr, nullptr, 0, nullptr, nullptr, stream))
+                return rc;
+        }
         b.rgb_map = a->rgb + off * 3;
         b.disp = a->disp ? a->disp + off : nullptr;
         b.acc = a->acc ? a->acc + off : nullptr;

@@ -361,6 +361,100 @@ extern "C" int mvsnerf_gather_fwd(const float* vol, int D, int H, int W, const f
 }
 
 // ---------------------------------------------------------------------------------------------
+// Wide-channel trilinear lookup: volumes with C = 4Q channels, 8 < C <= 40 - the (8 + 4V)-channel colour volume of --use_color_volume
+// (renderer.py:134-135; 20 channels at three source views, 28 at five) - and, in the same launch, the per-ray view-direction feature:
+// the colour-volume counterpart of gather_fused_kernel (one launch produces input_feat and dirs).
+// One lane owns one (sample, channel quad).  The Q lanes of a sample are neighbours, so per corner they read the voxel's 4C contiguous bytes
+// with one 16-byte load each, and the sample's output row is written with one 16-byte store per lane.  Coordinates, floor, weights and the
+// in-range tests are formed once per lane (the generic kernel: once per channel, with eight scalar loads each).
+// A block of 256 threads holds floor(256 / Q) samples (at most 6 idle threads): the (sample, quad) split of a thread is then a division of a
+// number below 256, one multiply and one shift, instead of a 64-bit division of the global thread id.
+// Same bits as volume_sample_generic_kernel: the same un-normalisation expression, weight ((wx * wy) * wz), every product v * w rounded (fp
+// contraction off), corners added in the order k = 0..7 (x fastest) from 0 with out-of-range corners SKIPPED - the loads of such corners go
+// to the zero block so that no lane branches, the additions are predicated because a NaN weight times zero is not zero.  NaN / huge
+// coordinates are rejected by the float compares before any int conversion is used.
+// ---------------------------------------------------------------------------------------------
+struct WideGatherArgs {
+    const float* vol; int D, H, W, C;
+    const float* ndc; int64_t P; int64_t N;     // P samples; N rays whose direction feature is written (0 without dirs_out)
+    const float* rays_dir; const float* w2c;    // [N][3], reference view's w2c [4][4] (may be NULL: no rotation)
+    float* feat; int feat_stride; float* dirs_out;
+    int spb, magic;                             // samples per block = 256 / Q; ceil(65536 / Q)
+};
+
+template <bool SMALL, bool ZFAST>      // SMALL: voxel, sample and feature-row offsets fit 32 bits (checked by the launcher); ZFAST: MVSNERF_VOL_HWDC
+__global__ __launch_bounds__(256) void volume_sample_wide_kernel(WideGatherArgs a)
+{
+#pragma clang fp contract(off)
+    const int Q = a.C >> 2;
+    const int ps = (int)(((unsigned)threadIdx.x * (unsigned)a.magic) >> 16);     // threadIdx.x / Q, exact below 256 for Q <= 10
+    const int cq = (int)threadIdx.x - ps * Q;
+    const int64_t p_raw = (int64_t)blockIdx.x * a.spb + ps;
+    if (ps >= a.spb || p_raw >= a.P) return;
+    using idx_t = typename std::conditional<SMALL, unsigned, int64_t>::type;
+    const idx_t p = (idx_t)p_raw;
+    const int D = a.D, H = a.H, W = a.W;
+    typedef float f32x3 __attribute__((ext_vector_type(3)));
+    const f32x3 nd = *reinterpret_cast<const f32x3*>(a.ndc + p * 3);
+    const float ix = ((nd[0] * 2.0f - 1.0f + 1.0f) / 2.0f) * (float)(W - 1);
+    const float iy = ((nd[1] * 2.0f - 1.0f + 1.0f) / 2.0f) * (float)(H - 1);
+    const float iz = ((nd[2] * 2.0f - 1.0f + 1.0f) / 2.0f) * (float)(D - 1);
+    const float fx = floorf(ix), fy = floorf(iy), fz = floorf(iz);
+    const float* zt = reinterpret_cast<const float*>(&g_zero_tap);
+    f32x4 v[8];
+    float w[8];
+    bool in[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const int zc = k >> 2, yc = (k >> 1) & 1, xc = k & 1;
+        const float cx = fx + xc, cy = fy + yc, cz = fz + zc;
+        w[k] = ((xc ? ix - fx : fx + 1.0f - ix) * (yc ? iy - fy : fy + 1.0f - iy)) * (zc ? iz - fz : fz + 1.0f - iz);
+        in[k] = cx >= 0.0f && cx <= (float)(W - 1) && cy >= 0.0f && cy <= (float)(H - 1) && cz >= 0.0f && cz <= (float)(D - 1);
+        idx_t vox;
+        if constexpr (ZFAST) vox = ((idx_t)(int)cy * (idx_t)W + (idx_t)(int)cx) * (idx_t)D + (idx_t)(int)cz;
+        else vox = ((idx_t)(int)cz * (idx_t)H + (idx_t)(int)cy) * (idx_t)W + (idx_t)(int)cx;
+        v[k] = ldg16(in[k] ? a.vol + vox * (idx_t)a.C + (idx_t)(cq * 4) : zt);
+    }
+    f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const f32x4 s = acc + v[k] * w[k];
+        acc = in[k] ? s : acc;
+    }
+    *reinterpret_cast<f32x4*>(a.feat + p * (idx_t)a.feat_stride + (idx_t)(cq * 4)) = acc;
+    // view-direction feature: the last lane of sample number n < N handles ray n (no p / S division), as in gather_fused_kernel
+    if (cq == Q - 1 && p_raw < a.N) dir_feature_of(a.rays_dir + p_raw * 3, a.w2c, 1, a.dirs_out + p_raw * 3);
+}
+
+extern "C" int mvsnerf_gather_colorvol_fwd(const float* vol, int D, int H, int W, int C, const float* ndc, int64_t N, int S,
+                                           const float* rays_dir, const float* w2c_ref, float* feat, int feat_stride, float* dirs_out,
+                                           int vol_layout, int force_offsets64, void* stream)
+{
+    if (vol_layout != MVSNERF_VOL_DHWC && vol_layout != MVSNERF_VOL_HWDC) return MVSNERF_EINVAL;
+    if (!vol || !ndc || !feat || D < 1 || H < 1 || W < 1 || C < 1 || N < 0 || S < 1 || feat_stride < C) return MVSNERF_EINVAL;
+    if (dirs_out && !rays_dir) return MVSNERF_EINVAL;
+    if ((C & 3) || C <= 8 || C > 40) return MVSNERF_EUNSUPPORTED;
+    if ((feat_stride & 3) || !mvs_aligned16(feat) || !mvs_aligned16(vol)) return MVSNERF_EALIGN;
+    if (N == 0) return MVSNERF_OK;
+    const int64_t P = N * S;
+    const int Q = C >> 2, spb = 256 / Q;
+    if ((P + spb - 1) / spb >= ((int64_t)1 << 31)) return MVSNERF_EUNSUPPORTED;
+    const WideGatherArgs a{vol, D, H, W, C, ndc, P, dirs_out ? N : 0, rays_dir, w2c_ref, feat, feat_stride, dirs_out, spb, (65536 + Q - 1) / Q};
+    const bool small = !force_offsets64 && (int64_t)D * H * W * C < ((int64_t)1 << 31) && P * (int64_t)feat_stride < ((int64_t)1 << 31);
+    const unsigned grid = (unsigned)((P + spb - 1) / spb);
+    hipStream_t st = (hipStream_t)stream;
+    if (vol_layout == MVSNERF_VOL_HWDC) {
+        if (small) volume_sample_wide_kernel<true, true><<<grid, 256, 0, st>>>(a);
+        else volume_sample_wide_kernel<false, true><<<grid, 256, 0, st>>>(a);
+    } else {
+        if (small) volume_sample_wide_kernel<true, false><<<grid, 256, 0, st>>>(a);
+        else volume_sample_wide_kernel<false, false><<<grid, 256, 0, st>>>(a);
+    }
+    MVS_LAUNCH_CHECK();
+    return MVSNERF_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
 // Boundary transposes (C small): one thread per voxel, C strided reads / one contiguous C-vector write.
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void ncdhw_to_ndhwc_kernel(const float* __restrict__ src, float* __restrict__ dst, int C, int64_t n_vox)

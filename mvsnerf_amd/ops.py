@@ -134,6 +134,27 @@ def gather(vol_cl, imgs, w2cs, intrinsics, rays_pts, rays_ndc, rays_dir=None):
     return feat, dirs
 
 
+def gather_colorvol(vol_cl, rays_ndc, rays_dir=None, w2c_ref=None, force_offsets64=False):
+    """gen_pts_feats of --use_color_volume (+ gen_dir_feature when rays_dir is given) in one launch: vol_cl (D,H,W,C) with C % 4 == 0,
+    8 < C <= 40; rays_ndc (N,S,3) -> (input_feat (N,S,C), dirs (N,3) | None).  The bits of volume_sample / dir_feature(normalize=True).
+    force_offsets64: run the kernel's 64-bit-offset form whatever the sizes (tests)."""
+    _need_no_grad(vol_cl, rays_ndc, rays_dir, op="gather_colorvol")
+    if rays_ndc.dim() != 3 or rays_ndc.shape[-1] != 3:
+        raise RuntimeError(f"gather_colorvol: rays_ndc must be (N,S,3), got {tuple(rays_ndc.shape)}")
+    N, S = rays_ndc.shape[:2]
+    D, H, W, C = vol_cl.shape
+    feat = torch.empty((N, S, C), device=rays_ndc.device, dtype=torch.float32)
+    dirs = None if rays_dir is None else torch.empty((N, 3), device=rays_ndc.device, dtype=torch.float32)
+    if rays_dir is not None and tuple(rays_dir.shape) != (N, 3):
+        raise RuntimeError(f"gather_colorvol: rays_dir must be ({N},3), got {tuple(rays_dir.shape)}")
+    vp, vl = vol_ptr_layout(vol_cl)
+    check(_lib.lib().mvsnerf_gather_colorvol_fwd(vp, D, H, W, C, dev_f32(rays_ndc, "rays_ndc"), N, S,
+                                                 0 if rays_dir is None else dev_f32(rays_dir, "rays_dir"),
+                                                 0 if w2c_ref is None else dev_f32(w2c_ref, "w2c_ref"), feat.data_ptr(), C,
+                                                 0 if dirs is None else dirs.data_ptr(), vl, int(bool(force_offsets64)), stream_ptr()), "gather_colorvol_fwd")
+    return feat, dirs
+
+
 def ndhwc_to_ncdhw(vol_cl):
     """vol[d][y][x][c] memory -> a contiguous (C,D,H,W) tensor (boundary helper for callers that want the reference's layout)."""
     D, H, W, C = vol_cl.shape
@@ -512,6 +533,90 @@ def raymarch_batched(vol_cl, imgs, w2cs, intrinsics, packed, ray_batches, white_
         outs.append(out)
     check(_lib.lib().mvsnerf_raymarch_fwd_batched(blocks, len(ray_batches), stream_ptr()), "raymarch_fwd_batched")
     return outs
+
+
+def raymarch_colorvol_batched(vol_cl, w2cs, packed, ray_batches, white_bkgd=False, packed_bf16=None, packed_split=None, guard=None, want=()):
+    """raymarch_batched on an (8 + 4V)-channel colour volume (mvsnerf_raymarch_colorvol_fwd_batched): ray_batches = [(rays_ndc, z_vals, rays_dir), ...];
+    w2cs (V,4,4), view 0 the reference view.  No images, intrinsics or points are needed: the feature row is one lookup of the volume."""
+    cur = torch.cuda.current_device()
+    D, H, W, C = vol_cl.shape
+    V = w2cs.shape[0]
+    if C != 8 + 4 * V:
+        raise RuntimeError(f"raymarch_colorvol_batched: the volume has {C} channels, 8 + 4V is {8 + 4 * V}")
+    vp, vl = vol_ptr_layout(vol_cl, cur)
+    outs, blocks = [], (_lib.RaymarchArgs * len(ray_batches))()
+    for k, (ndc, z, rdir) in enumerate(ray_batches):
+        _need_no_grad(vol_cl, ndc, z, rdir, op="raymarch_colorvol_batched")
+        N, S = z.shape
+        shapes = {"input_feat": (N, S, C), "raw": (N, S, 4), "rgb_map": (N, 3), "weights": (N, S), "depth": (N,), "alpha": (N, S), **{q: (N,) for q in want},
+                  "_dirs_tmp": (N, 3)}
+        out = {q: torch.empty(sh, device=ndc.device, dtype=torch.float32) for q, sh in shapes.items()}
+        ptrs = {q: out[q].data_ptr() if q in out else 0 for q in ("input_feat", "raw", "rgb_map", "disp", "acc", "weights", "depth", "alpha")}
+        blocks[k] = _lib.RaymarchArgs(vol=vp, D=D, H=H, W=W, vol_layout=vl, V=V, w2c=dev_f32(w2cs, "w2cs", cur), packed_mlp=dev_f32(packed, "packed", cur),
+                                      rays_ndc=dev_f32(ndc, "rays_ndc", cur), z_vals=dev_f32(z, "z_vals", cur), rays_dir=dev_f32(rdir, "rays_dir", cur),
+                                      N=N, S=S, white_bkgd=int(bool(white_bkgd)), dirs_tmp=out["_dirs_tmp"].data_ptr(), **ptrs,
+                                      **_mlp_fields(packed_bf16, packed_split, guard))
+        outs.append(out)
+    check(_lib.lib().mvsnerf_raymarch_colorvol_fwd_batched(blocks, len(ray_batches), C, stream_ptr()), "raymarch_colorvol_fwd_batched")
+    return outs
+
+
+def render_rays(vol_cl, rays, t, packed, K_ref, w2c_ref, nf_ref, ref_hw, n_views, imgs=None, w2cs=None, intrinsics=None, first_ray=0, n_rays=None,
+                density=None, u=None, pad=0, lindisp=False, white_bkgd=False, batch_rays=16384, want=("depth",), packed_bf16=None, packed_split=None,
+                guard=None):
+    """Rays [first_ray, first_ray + n_rays) of `rays` (N,8) = [o | d | near | far] of a fine-tuned scene in ONE FFI call (mvsnerf_render_rays_fwd: the
+    chunk loop of the fine-tuning script's validation_step).  vol_cl (D,H,W,C): C == 8 renders from the volume and the source images (imgs (V,3,IH,IW)
+    un-normalised, w2cs (V,4,4), intrinsics (V,3,3)); C == 8 + 4*n_views is a colour volume and needs none of them.  t (S,) = linspace(0,1,S);
+    density (DD,DH,DW) + u (N,NI): importance sampling (ray_marcher_fine).  Returns dict with rgb (n,3) and the requested extras among depth/acc/disp (n,)."""
+    _need_no_grad(vol_cl, rays, imgs, density, op="render_rays")
+    lib = _lib.lib()
+    if rays.dim() != 2 or rays.shape[1] != 8:
+        raise RuntimeError(f"render_rays: rays must be (N,8), got {tuple(rays.shape)}")
+    n = rays.shape[0] - first_ray if n_rays is None else int(n_rays)
+    if first_ray < 0 or n < 0 or first_ray + n > rays.shape[0]:
+        raise RuntimeError(f"render_rays: rays [{first_ray}, {first_ray + n}) outside the {rays.shape[0]} given")
+    V = int(n_views)
+    D, Hv, Wv, C = vol_cl.shape
+    F, S = 8 + 4 * V, int(t.shape[0])
+    fine = density is not None and u is not None and u.shape[-1] > 0
+    NI = int(u.shape[1]) if fine else 0
+    if fine and u.shape[0] != rays.shape[0]:
+        raise RuntimeError(f"render_rays: u must hold one row per ray ({rays.shape[0]}), got {tuple(u.shape)}")
+    if C == 8 and (imgs is None or w2cs is None or intrinsics is None or imgs.shape[0] != V):
+        raise RuntimeError("render_rays: an 8-channel volume needs imgs (n_views,3,H,W), w2cs and intrinsics")
+    dev = vol_cl.device
+    f32 = dict(device=dev, dtype=torch.float32)
+    B = int(min(batch_rays, max(n, 1)))
+    ws_n = lib.mvsnerf_render_rays_workspace_floats(B, S, NI, F)
+    if ws_n == 0:
+        raise RuntimeError(f"render_rays: unsupported sizes (batch_rays {B}, S {S}, n_importance {NI}, F {F})")
+    # one workspace per (size, device, STREAM), as render_pixels keeps them
+    key = ("rays", ws_n, dev.index if dev.index is not None else torch.cuda.current_device(), torch.cuda.current_stream(dev).cuda_stream)
+    ws = _render_ws.get(key)
+    if ws is None:
+        while len(_render_ws) >= 4:
+            _render_ws.pop(next(iter(_render_ws)))
+        ws = _render_ws[key] = torch.empty(ws_n, **f32)
+    out = {"rgb": torch.empty((n, 3), **f32)}
+    for k in ("depth", "acc", "disp"):
+        out[k] = torch.empty((n,), **f32) if k in want else None
+    if n == 0:
+        return {k: v for k, v in out.items() if v is not None}
+    c = _Keep()
+    vp, vl = vol_ptr_layout(vol_cl)
+    src = {}
+    if C == 8:
+        src = dict(imgs_nhwc4=channels_last_images(imgs).data_ptr(), IH=imgs.shape[2], IW=imgs.shape[3], w2c=c(w2cs, "w2cs"), K=c(intrinsics, "intrinsics"))
+    if fine:
+        src.update(density=c(density, "density_volume"), DD=density.shape[0], DH=density.shape[1], DW=density.shape[2], u=c(u, "u"), n_importance=NI)
+    a = _lib.RenderRaysArgs(
+        vol=vp, D=D, H=Hv, W=Wv, C=C, vol_layout=vl, V=V, K_ref=c(K_ref, "K_ref"), w2c_ref=c(w2c_ref, "w2c_ref"),
+        near_far_ref=c(nf_ref.reshape(-1)[:2], "near_far_ref"), W_ref=int(ref_hw[1]), H_ref=int(ref_hw[0]), pad=int(pad), lindisp=int(bool(lindisp)),
+        packed_mlp=packed.data_ptr(), rays=c(rays, "rays"), first_ray=int(first_ray), n_rays=n, t=c(t, "t"), S=S,
+        white_bkgd=int(bool(white_bkgd)), batch_rays=B, workspace=ws.data_ptr(), workspace_floats=ws_n,
+        **{k: 0 if out[k] is None else out[k].data_ptr() for k in out}, **src, **_mlp_fields(packed_bf16, packed_split, guard))
+    check(lib.mvsnerf_render_rays_fwd(ctypes.byref(a), stream_ptr()), "render_rays_fwd")
+    return {k: v for k, v in out.items() if v is not None}
 
 
 def render_pixels(vol_cl, imgs, w2cs, intrinsics, packed, H, W, K_tgt, c2w_tgt, K_ref, w2c_ref, nf_tgt, nf_ref, N_samples,

@@ -162,16 +162,26 @@ def rendering(args, pose_ref, rays_pts, rays_ndc, depth_candidates, rays_o, rays
 def rendering_batched(args, pose_ref, ray_batches, volume_feature=None, imgs=None, network_fn=None, network_query_fn=None, white_bkgd=False, **kwargs):
     """K calls of rendering() (renderer.py:138-165) on one scene as ONE host call: ray_batches = [(rays_pts, rays_ndc, depth_candidates, rays_o,
     rays_dir), ...] (rendering()'s positional ray arguments).  Returns the list of rendering()'s 6-tuples.  No gradients (inference loops:
-    validation_step's chunk loop, notebooks' render loops); an extension - the reference has no such entry, its loop body is rendering()."""
+    validation_step's chunk loop, notebooks' render loops); an extension - the reference has no such entry, its loop body is rendering().
+    With args.use_color_volume the feature rows come from the (8 + 4V)-channel volume (ops.raymarch_colorvol_batched), still one host call."""
     from .models import MVSNeRF, RefVolume
     vol = volume_feature.feat_volume if isinstance(volume_feature, RefVolume) else volume_feature
     if not (pose_ref is not None and isinstance(network_fn, MVSNeRF) and getattr(network_query_fn, "_mvsnerf_fused", False) and vol is not None):
         raise NotImplementedError("rendering_batched: the fused configuration only (what create_nerf_mvs builds); call rendering() per batch otherwise")
-    if bool(getattr(args, "use_color_volume", False)):
-        raise NotImplementedError("rendering_batched: use_color_volume renders piecewise - call rendering() per batch")
     V = imgs.shape[1]
     if args.feat_dim != 8 + 4 * V:
         raise RuntimeError(f"args.feat_dim {args.feat_dim} != 8 + 4*V ({V} views)")
+    if bool(getattr(args, "use_color_volume", False)):
+        # renderer.py:134-135: the feature row is one lookup of the (8 + 4V)-channel volume - the same one host call, the colour-volume gather
+        # (ops.gather_colorvol's kernel) in place of the image gather
+        if vol.shape[-4] != args.feat_dim:
+            raise RuntimeError(f"use_color_volume: the volume has {vol.shape[-4]} channels, feat_dim is {args.feat_dim}")
+        outs = ops.raymarch_colorvol_batched(ops.channels_last_volume(vol), pose_ref["w2cs"][:V].contiguous(), network_fn.packed(args.feat_dim),
+                                             [(b[1].contiguous(), b[2].contiguous(), b[4].contiguous()) for b in ray_batches], white_bkgd,
+                                             **network_fn.packed_alt(args.feat_dim, fresh=True))
+        if outs:
+            rendering.last_raw = outs[-1]["raw"]
+        return [(o["rgb_map"], o["input_feat"], o["weights"], o["depth"], o["alpha"], {}) for o in outs]
     sc = _scene_views(imgs, pose_ref, V)
     packed = network_fn.packed(args.feat_dim)
     outs = ops.raymarch_batched(ops.channels_last_volume(vol), sc[0], sc[1], sc[2], packed,

@@ -583,6 +583,97 @@ class MVSSystemFinetune(_ModuleShim):
             self.log("train/PSNR", mse2psnr2(img_loss), prog_bar=True)
         return {"loss": img_loss}
 
+    # -- rendering the fine-tuned scene (train_mvs_nerf_finetuning_pl.py:192-252) ---------------------
+    @torch.no_grad()
+    def render_rays(self, rays, chunk=None, batch_rays=16384, u=None, whole_frame_off=False):
+        """The rendering part of the fine-tuning script's validation_step (:204-237) for the dataset's rays (N,8) = [o | d | near | far]: per
+        chunk ray_marcher -> get_ndc_coordinate -> [ray_marcher_fine, when a density volume exists and args.N_importance > 0] -> rendering, from
+        the learnt `self.volume` (8 channels + the source images, or the (8 + 4V)-channel colour volume of --use_color_volume).  Returns
+        (rgb (N,3), depth (N,)).  One library call per rank (ops.render_rays: the chunk loop runs inside the library), the rays sharded over the
+        ranks in contiguous chunk ranges exactly as MVSSystem.render_view shards pixels.
+        u: the (N, N_importance) uniform draw of sample_pdf (drawn once with torch.rand when None).  batch_rays: rays per sub-batch inside the
+        library call (free parameter: the results do not depend on it).  whole_frame_off=True runs the reference's per-chunk Python loop
+        (ray_marcher -> ops.ray_points -> ray_marcher_fine -> rendering) instead; both produce the same values."""
+        args = self.args
+        chunk = int(chunk or args.chunk)
+        dev = self.imgs.device
+        rays = rays.reshape(-1, 8).to(dev, torch.float32).contiguous()
+        N = rays.shape[0]
+        if N == 0:
+            return torch.empty((0, 3), device=dev), torch.empty((0,), device=dev)
+        lindisp = bool(getattr(args, "use_disp", False))
+        white = bool(self.render_kwargs_train.get("white_bkgd", getattr(args, "white_bkgd", False)))
+        H, W = self.imgs.shape[-2:]
+        w2c_ref, K_ref = self.pose_source["w2cs"][0], self.pose_source["intrinsics"][0]
+        NI = int(getattr(args, "N_importance", 0) or 0)
+        fine = self.density_volume is not None and NI > 0
+        if fine:
+            u = torch.rand((N, NI), device=dev) if u is None else u.to(dev, torch.float32).contiguous()
+            if tuple(u.shape) != (N, NI):
+                raise RuntimeError(f"render_rays: u must be ({N}, {NI}), got {tuple(u.shape)}")
+        kw = self.render_kwargs_train
+        net = kw["network_fn"]
+        V = self.imgs.shape[1]
+        vol = self.volume.feat_volume
+        color_vol = bool(getattr(args, "use_color_volume", False))
+
+        if whole_frame_off:
+            def render_chunk(idx):
+                r = rays[idx * chunk:(idx + 1) * chunk]
+                _, rays_o, rays_d, z = ray_marcher(r, N_samples=args.N_samples, lindisp=lindisp)
+                pts, ndc = ops.ray_points(rays_o, rays_d, z, w2c_ref, K_ref, self.near_far_source, ref_hw=(H, W), pad=args.pad, lindisp=lindisp)
+                if fine:
+                    pts, rays_o, rays_d, z = ray_marcher_fine(r, self.density_volume, z, ndc, N_importance=NI, u=u[idx * chunk:(idx + 1) * chunk].contiguous())
+                    pts, ndc = ops.ray_points(rays_o, rays_d, z, w2c_ref, K_ref, self.near_far_source, ref_hw=(H, W), pad=args.pad, lindisp=lindisp)
+                rgb, _, _, depth, _, _ = rendering(args, self.pose_source, pts, ndc, z, rays_o, rays_d.contiguous(), self.volume, self.imgs, **kw)
+                return rgb, depth
+            return D.render_frame(render_chunk, 1, N, chunk)
+
+        if not (isinstance(net, MVSNeRF) and getattr(kw.get("network_query_fn"), "_mvsnerf_fused", False)):
+            raise NotImplementedError("render_rays: the fused configuration only (what create_nerf_mvs builds); whole_frame_off=True runs the per-chunk loop")
+        if args.feat_dim != 8 + 4 * V or vol.shape[1] != (args.feat_dim if color_vol else 8):
+            raise RuntimeError(f"render_rays: volume with {vol.shape[1]} channels, feat_dim {args.feat_dim}, {V} source views")
+        vol_cl = ops.channels_last_volume(vol)
+        t = torch.linspace(0, 1, args.N_samples, device=dev)
+        src = {} if color_vol else dict(imgs=self.imgs[0].contiguous(), w2cs=self.pose_source["w2cs"][:V].contiguous(),
+                                        intrinsics=self.pose_source["intrinsics"][:V].contiguous())
+        if fine:
+            src.update(density=self.density_volume, u=u)
+
+        def render_range(first, n):
+            o = ops.render_rays(vol_cl, rays, t, net.packed(args.feat_dim), K_ref, w2c_ref, self.near_far_source, (H, W), V, first_ray=first, n_rays=n,
+                                pad=args.pad, lindisp=lindisp, white_bkgd=white, batch_rays=batch_rays, **src, **net.packed_alt(args.feat_dim))
+            return o["rgb"], o["depth"]
+        return D.render_frame_pixels(render_range, 1, N, chunk, device=dev)
+
+    @torch.no_grad()
+    def validation_step(self, batch, batch_nb):
+        """:192-252.  batch = {'rays': (1,N,8) | (N,8), 'rgbs': (1,H,W,3) | (H,W,3) | (N,3)} - one view of the val split.  Renders the rays
+        (render_rays) and returns the reference's log dict: 'val_psnr_all'.  Left out, as in MVSSystem.validation_step: the TensorBoard
+        image grids and the PNG dump; `last_val_images` keeps what they show.  The reference re-scales the reference intrinsics and the pad
+        by imgScale_test / imgScale_train (:215-218); only ratio 1 is supported."""
+        args = self.args
+        ratio = float(getattr(args, "imgScale_test", 1.0)) / float(getattr(args, "imgScale_train", 1.0))
+        if ratio != 1.0:
+            raise NotImplementedError("validation_step: imgScale_test / imgScale_train != 1 re-scales the reference intrinsics and the volume's pad "
+                                      f"(train_mvs_nerf_finetuning_pl.py:215-218); only ratio 1 is supported, got {ratio}")
+        from .utils import mse2psnr
+        rays = batch["rays"].reshape(-1, 8)
+        img = batch["rgbs"].to(torch.float32).cpu()
+        img = img[0] if img.dim() == 4 else img                                                          # (H,W,3) or (N,3)
+        rgb, depth = self.render_rays(rays)
+        rgb = torch.clamp(rgb.cpu().reshape(img.shape), 0, 1)                                           # :237
+        depth = depth.cpu().reshape(img.shape[:-1])
+        img_err_abs = (rgb - img).abs()
+        log = {"val_psnr_all": mse2psnr(torch.mean(img_err_abs ** 2))}                                    # :240
+        self.idx = getattr(self, "idx", 0) + 1
+        self.last_val_images = {"rgb": rgb, "depth": depth, "err": img_err_abs}
+        return log
+
+    def validation_epoch_end(self, outputs):
+        """:254-276 (the with_depth keys need logs this validation_step does not produce, as in the reference's own)."""
+        self.log("val/PSNR_all", torch.stack([torch.as_tensor(x["val_psnr_all"], dtype=torch.float64).reshape(()) for x in outputs]).mean(), prog_bar=True)
+
     def save_ckpt(self, name="latest"):
         """:277-291 of the fine-tuning script: adds the `volume` state dict."""
         save_dir = f"runs_fine_tuning/{getattr(self.args, 'expname', 'exp')}/ckpts/"
