@@ -46,7 +46,7 @@ def test_featurenet_forward_vs_oracle(N, H, W):
     assert float((out_e - ref_e).abs().max()) < 1e-4 * max(1.0, float(ref_e.abs().max()))
 
 
-@pytest.mark.parametrize("N,H,W", [(3, 64, 96), (2, 50, 70)])
+@pytest.mark.parametrize("N,H,W", [(3, 64, 96), (2, 50, 70), (1, 33, 17), (2, 37, 45)])      # the last two: odd at every level
 def test_featurenet_backward_vs_autograd(N, H, W):
     from oracle import mvsnerf_oracle as O
     fn, sd0 = _net()
