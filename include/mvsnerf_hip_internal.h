@@ -183,6 +183,17 @@ int mvsnerf_mlp_fwd_census(const float* packed, int F,
                            const float* ndc, int ndc_stride, const float* feat, int feat_stride,
                            const float* dirs, int dirs_stride, int64_t N, int S, int alpha_only,
                            float* raw, long long* census, void* stream);
+/* Folded pack.  feature_linear and views_linears.0 have no activation between them, so a no-grad forward may run them as one affine map
+ * (W' = Wv[:, :128] * Wf, b' = bv + Wv[:, :128] * bf, formed on the device in double and rounded to fp32 once).  mvsnerf_mlp_pack_fold writes
+ * everything mvsnerf_mlp_pack writes - the standard layout, same offsets, same bits - sets one of the vector block's pad floats to 1.0f and appends
+ * the folded views segment and bias behind the standard buffer: `packed` holds mvsnerf_mlp_packed_fold_floats(F) floats.  The buffer describes
+ * itself: every fp32 no-grad kernel handed it (mvsnerf_mlp_fwd, mvsnerf_mlp_fwd_guarded's fp32 half, mvsnerf_raymarch_fwd*, mvsnerf_render_*)
+ * skips the feature_linear GEMM and returns the same bits as every other; mvsnerf_mlp_fwd_train, the backward and the 16-bit kernels read the
+ * standard part only and compute what they compute from a mvsnerf_mlp_pack buffer.  The stable mvsnerf_mlp_pack always writes 0.0f to that pad,
+ * so a stable-tier caller with an exact mvsnerf_mlp_packed_floats(F) buffer can never make a kernel read past it - also when it re-packs into
+ * memory that held a folded buffer before. */
+size_t mvsnerf_mlp_packed_fold_floats(int F);
+int mvsnerf_mlp_pack_fold(const float* const w[11], const float* const b[11], int F, float* packed, void* stream);
 /* (described in mvsnerf_hip.h: "---- Guarded 16-bit sequences (ABI v10) ---- ...") */
 typedef struct {
     const float* feats_cl; const float* imgs_cl;   /* [V][H][W][32], [V][H][W][4] as for mvsnerf_planesweep_costvar_fwd (with_img = 1) */

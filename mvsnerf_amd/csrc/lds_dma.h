@@ -22,6 +22,14 @@ __device__ __forceinline__ void lds_dma_1k(const void* src_uniform, unsigned lds
                  :: "v"(lane_byte), "s"(src_uniform), "s"(lds_byte_uniform) : "memory");   // M0 is not allocatable: the compiler only writes it right before its own M0 users
 }
 
+// one dword per lane: lanes read 4 B each at src + lane_byte (src wave-uniform, any per-lane offset), LDS receives them at lds_byte + lane * 4.
+// A load whose value is wanted much later costs no VGPR this way.
+__device__ __forceinline__ void lds_dma_dword(const void* src_uniform, unsigned lds_byte_uniform, unsigned lane_byte)
+{
+    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %0, %1"
+                 :: "v"(lane_byte), "s"(src_uniform), "s"(lds_byte_uniform) : "memory");
+}
+
 // n_pieces KB from src to dst, piece i handled by wave i % WAVES (wave = this wave's index, wave-uniform)
 template <int WAVES>
 __device__ __forceinline__ void lds_dma(void* __restrict__ dst, const void* __restrict__ src, int n_pieces, int wave, int lane)

@@ -5,7 +5,9 @@
 // weights as A operand streamed through a 64 KB LDS buffer and the activations as B operand straight
 // from the previous layer's accumulator registers (see mlp_layout.h) - the 86-wide input and all
 // 128-wide activations of the reference (~1.5 GB of ATen traffic per 1024x128 batch) never exist in
-// memory.  MFMA-bound: 251 392 FLOP per point against 12 B + 4*F B read and 16 B written.
+// memory.  MFMA-bound: 251 392 FLOP per point (the reference network's count; 1 976 MFMAs per wave of 32 points) against 12 B + 4*F B read
+// and 16 B written.  With a folded buffer (mvsnerf_mlp_pack_fold, mlp_layout.h) the no-grad kernels run feature_linear and views_linears.0 as one
+// affine map: 1 720 MFMAs per wave, 218 624 FLOP per point issued for the same result.
 #include "common.h"
 #include "mlp_layout.h"
 #include "lds_dma.h"
@@ -40,6 +42,9 @@ __device__ inline void pack_segment(float* __restrict__ dst, const float* __rest
     }
 }
 
+// FOLD: the fold tail of mlp_layout.h behind the standard buffer and V_FOLD = 1.  One thread per tail element, a sequential double chain over
+// j = 0..127 (products of two fp32 values are exact in double, so this is `acc = acc + a*b` in float64, j ascending), rounded to fp32 once.
+template <bool FOLD>
 __global__ __launch_bounds__(256) void mlp_pack_kernel(PackArgs a, float* __restrict__ packed)
 {
     const Layout L = layout(a.F);
@@ -68,7 +73,7 @@ __global__ __launch_bounds__(256) void mlp_pack_kernel(PackArgs a, float* __rest
             const int k = i - V_WA;
             x = a.w[8][act_n(k & 63, k >> 6)];
         } else if (i < V_WR) {
-            x = (i == V_BA) ? a.b[8][0] : 0.0f;
+            x = (i == V_BA) ? a.b[8][0] : (FOLD && i == V_FOLD) ? 1.0f : 0.0f;
         } else if (i < V_BR) {                   // rgb weight [3][2][32]
             const int k = i - V_WR, c = k >> 6, h = (k >> 5) & 1, q = k & 31;
             x = a.w[10][c * 64 + act_n(q, h)];
@@ -77,6 +82,35 @@ __global__ __launch_bounds__(256) void mlp_pack_kernel(PackArgs a, float* __rest
             x = c < 3 ? a.b[10][c] : 0.0f;
         }
         v[i] = x;
+    }
+    if constexpr (FOLD) {
+        const float* Wv = a.w[9];
+        const float* Wf = a.w[7];
+        float* fw = packed + fold_views_off(a.F);
+        float* fb = packed + fold_bias_off(a.F);
+        constexpr int total = (int)seg_floats(VIEW_STEPS, 2);
+        for (int i = tid; i < total + 64; i += nt) {
+            if (i < total) {                     // as pack_segment(.., K_VIEWS, VIEW_STEPS, 2, ..) on [W' | Wv[:, 128:131]]
+                const int lane = (i >> 2) & 63, rest = i >> 8;
+                const int t = (rest >> 1) * 4 + (i & 3);
+                const int col = kmap_col(K_VIEWS, t, lane >> 5, a.F);
+                const float* wrow = Wv + (size_t)((rest & 1) * 32 + (lane & 31)) * (WIDTH + 3);
+                float x = 0.0f;
+                if (col >= WIDTH) {
+                    x = wrow[col];
+                } else if (col >= 0) {
+                    double acc = 0.0;
+                    for (int j = 0; j < WIDTH; ++j) acc = acc + (double)wrow[j] * (double)Wf[j * WIDTH + col];
+                    x = (float)acc;
+                }
+                fw[i] = x;
+            } else {
+                const int k = i - total, n = act_n(k & 31, k >> 5);
+                double acc = (double)a.b[9][n];
+                for (int j = 0; j < WIDTH; ++j) acc = acc + (double)Wv[(size_t)n * (WIDTH + 3) + j] * (double)a.b[7][j];
+                fb[k] = (float)acc;
+            }
+        }
     }
 }
 
@@ -88,7 +122,14 @@ extern "C" size_t mvsnerf_mlp_packed_floats(int F)
     return off16(F);
 }
 
-extern "C" int mvsnerf_mlp_pack(const float* const w[11], const float* const b[11], int F, float* packed, void* stream)
+extern "C" size_t mvsnerf_mlp_packed_fold_floats(int F)
+{
+    if (F < 2 || F > MAX_F || (F & 1)) return 0;
+    return fold_total(F);
+}
+
+template <bool FOLD>
+static int mlp_pack_impl(const float* const w[11], const float* const b[11], int F, float* packed, void* stream)
 {
     if (!w || !b || !packed) return MVSNERF_EINVAL;
     if (F < 2 || F > MAX_F || (F & 1)) return MVSNERF_EUNSUPPORTED;
@@ -99,9 +140,19 @@ extern "C" int mvsnerf_mlp_pack(const float* const w[11], const float* const b[1
         a.w[i] = w[i]; a.b[i] = b[i];
     }
     a.F = F;
-    mlp_pack_kernel<<<64, 256, 0, (hipStream_t)stream>>>(a, packed);
+    mlp_pack_kernel<FOLD><<<64, 256, 0, (hipStream_t)stream>>>(a, packed);
     MVS_LAUNCH_CHECK();
     return MVSNERF_OK;
+}
+
+extern "C" int mvsnerf_mlp_pack(const float* const w[11], const float* const b[11], int F, float* packed, void* stream)
+{
+    return mlp_pack_impl<false>(w, b, F, packed, stream);
+}
+
+extern "C" int mvsnerf_mlp_pack_fold(const float* const w[11], const float* const b[11], int F, float* packed, void* stream)
+{
+    return mlp_pack_impl<true>(w, b, F, packed, stream);
 }
 
 // ------------------------------------------------------------------------------------------ compute
@@ -202,10 +253,12 @@ __device__ __forceinline__ float pe_operand(int t, int half, float px, float py,
 // Measured on MI355X: 0.237 ms per 1024x128 batch = 139 TFLOP/s = 88 % of the 157.3 TFLOP/s fp32-MFMA peak; PMC:
 // matrix pipes busy 85 % of the kernel's duration.  What the rest is: VALU instructions cost matrix-pipe issue time on this
 // chip whichever wave issues them (scratch/mfma_mix.hip: one v_fma per MFMA takes 12 % off the MFMA rate), ~1 950 of them per
-// 1 976 MFMAs here; launch ramp / tail of a two-round grid.  Negative results kept out of the code: (i) staggering /
+// 1 976 MFMAs here (folded: ~1 880 per 1 720 - the 64 register moves and one accumulator initialisation of feature_linear go with its
+// 256 MFMAs); launch ramp / tail of a two-round grid.  Negative results kept out of the code: (i) staggering /
 // prioritising the two co-resident workgroups of a CU: no change; (ii) reading A fragments straight from L2 (no LDS stage, no
 // barriers): 114 TFLOP/s; (iii) 64 points per wave at one wave per SIMD: 114 TFLOP/s.
-// Same arithmetic as mlp_fwd_kernel<.., G=1, ..>, different weight logistics: the packed weights are cut into 16 slabs
+// Same arithmetic as mlp_fwd_kernel<.., G=1, ..>, different weight logistics: the packed weights are cut into 16 slabs (folded: 14 - feature_linear's two are not
+// fetched, the folded views segment takes the place of the plain one)
 // of <= 34 KB (half a 128x128 layer = 32 k-steps) that alternate between two LDS buffers.  While the MFMAs of slab i
 // run, slab i+1 arrives by LDS-DMA (global_load_lds_dwordx4: no VGPRs, no ds_write pass); one barrier per slab.
 constexpr int SLAB_FLOATS = 8704;                        // 34 KB = 34 k-steps x 4 blocks x 64 lanes (views: 68 x 2)
@@ -383,6 +436,16 @@ __device__ __forceinline__ void mlp_fwd_pipe_tile(
 
     // ---- slab 0: bias = pts_bias(feat)
     if constexpr (!FUSED) slab_sync();
+    // A folded buffer (V_FOLD, mlp_layout.h) describes itself: every fp32 no-grad kernel handed it makes the same, wave-uniform choice,
+    // read from the LDS copy of the vector block.  The training forward ignores the flag (the backward consumes S_FE), the sigma-only
+    // launch never reaches the tail.  The folded bias takes the LDS place of V_VIEWS, which a folded tile does not read (one LDS-DMA
+    // dword per lane of wave 0; the slab barriers below cover it).
+    constexpr bool MAY_FOLD = !ALPHA_ONLY && !SAVE;
+    bool fold = false;
+    if constexpr (MAY_FOLD) {
+        fold = __builtin_amdgcn_readfirstlane(__float_as_int(vec[V_FOLD])) != 0;
+        if (fold && wave == 0) lds_dma_dword(packed + fold_bias_off(F), lds_byte_addr(vec + V_VIEWS), lane * 4);
+    }
     stamp();                                                                                // [4] startup done
     {
         f32x16 acc[G][4];
@@ -408,6 +471,15 @@ __device__ __forceinline__ void mlp_fwd_pipe_tile(
     // ---- slab 1: layer 0
     slab_sync();
     slab_dma_c<HALF>(buf0, packed + L.l1, wave, lane);                                      // slab 2
+    // FUSED: the rays' directions, wanted by the views GEMM, fetched here - where h is not live yet - by LDS-DMA into the 2 KB of buf0 that no
+    // slab from here on reaches (none is longer than HALF in buf0; the staged rows were last read in front of the barrier above): they hold no
+    // register meanwhile.  Lane (m, half) fetches component `half` of point m's ray, then component 2: [3][32] (+ 32 unused) per wave.
+    float* rdir_lds = buf0 + HALF + wave * 128;
+    if constexpr (FUSED) {
+        const unsigned ray_of_p = (unsigned)p / (unsigned)S;                                // every offset fits 32 bits
+        lds_dma_dword(fa->rays_dir, lds_byte_addr(rdir_lds), (ray_of_p * 3 + half) * 4);
+        lds_dma_dword(fa->rays_dir, lds_byte_addr(rdir_lds + 64), (ray_of_p * 3 + 2) * 4);
+    }
     {
         f32x16 acc[G][4];
         init_acc<4, G>(acc, vec + V_L0 + half * 64);
@@ -449,7 +521,12 @@ __device__ __forceinline__ void mlp_fwd_pipe_tile(
         slab_sync();
         gemm_stage<8, 4, G>(buf1, acc, lane, hlo, [&]() { slab_dma_c<HALF>(buf0, packed + L.l5b + HALF, wave, lane); });
         slab_sync();
-        gemm_stage<8, 4, G>(buf0, acc, lane, hhi, [&]() { if (!ALPHA_ONLY) slab_dma_c<HALF>(buf1, packed + L.feat, wave, lane); });
+        // next slab: the first half of feature_linear, or - folded - the folded views segment, which fills the buffer (SLAB_FLOATS).  One
+        // branch-free DMA of that size serves both (an unfolded tile moves 2 KB of feature_linear's second half it does not read).
+        gemm_stage<8, 4, G>(buf0, acc, lane, hhi, [&]() {
+            if constexpr (SAVE) slab_dma_c<HALF>(buf1, packed + L.feat, wave, lane);
+            else if constexpr (!ALPHA_ONLY) slab_dma_c<(int)seg_floats(VIEW_STEPS, 2)>(buf1, packed + (fold ? fold_views_off(F) : L.feat), wave, lane);
+        });
 #pragma unroll
         for (int q = 0; q < 64; q += 2) {
             const f32x2 m2 = f32x2{acc[0][q >> 4][q & 15], acc[0][q >> 4][(q & 15) + 1]} * f32x2{bias[q], bias[q + 1]};   // v_pk_mul_f32
@@ -468,18 +545,8 @@ __device__ __forceinline__ void mlp_fwd_pipe_tile(
         if (live && half == 0) raw[p_raw] = sigma;
         return;
     }
-    // FUSED: the ray's direction and the reference rotation, loaded here so that they land under the feature_linear GEMM
-    float rdir[3] = {0.0f, 0.0f, 0.0f}, rot[11];
-    int64_t ray_of_p = 0;
-    if constexpr (FUSED) {
-        ray_of_p = p / S;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) rdir[c] = fa->rays_dir[ray_of_p * 3 + c];
-#pragma unroll
-        for (int i = 0; i < 11; ++i) rot[i] = fa->w2c[i];
-    }
-    // ---- feature_linear: slabs 13 (buf1), 14 (buf0)
-    {
+    // ---- feature_linear: slabs 13 (buf1), 14 (buf0).  Folded: skipped, the views GEMM below takes h5 and the folded segment already on its way
+    if (!fold) {
         f32x16 acc[G][4];
         slab_sync();
         init_acc<4, G>(acc, vec + V_FEAT + half * 64);
@@ -490,8 +557,15 @@ __device__ __forceinline__ void mlp_fwd_pipe_tile(
         for (int q = 0; q < 64; ++q) { h[q] = acc[0][q >> 4][q & 15]; save(S_FE + q, h[q]); }
     }
     stamp();                                                                                // [12] feature_linear done
-    // ---- views_linears[0] + rgb head: slab 15 (buf1)
+    // ---- views_linears[0] + rgb head: slab 15 (buf1; folded: slab 13)
     {
+        // the point's index again, from the lane number: opaque to the compiler, so that the 64-bit values of the prologue are not carried in
+        // registers (or spilled) through every GEMM for the few uses below
+        int lane_o = lane;
+        asm("" : "+v"(lane_o));
+        const int64_t p_raw = ((int64_t)tile * 4 + wave) * 32 + (lane_o & 31);
+        const bool live = p_raw < P;
+        const int64_t p = live ? p_raw : P - 1;
         // compositing in the tile: its 128 z values are one contiguous block, loaded here so that they land under the views GEMM
         float z_pre = 0.0f;
         if constexpr (FUSED && NR > 0)
@@ -500,7 +574,11 @@ __device__ __forceinline__ void mlp_fwd_pipe_tile(
         if constexpr (FUSED) {
             // the ray's view direction in registers: with S > 128 a ray spans tiles, so dirs_tmp is written (by the tile holding the ray's
             // first sample) and never read back
-            const int64_t ray = ray_of_p;
+            const int64_t ray = (unsigned)p / (unsigned)S;
+            const float rdir[3] = {rdir_lds[lane & 31], rdir_lds[32 + (lane & 31)], rdir_lds[64 + (lane & 31)]};
+            float rot[11];
+#pragma unroll
+            for (int i = 0; i < 11; ++i) rot[i] = fa->w2c[i];
             float d[3];
             dir_feature_of(rdir, rot, 1, d);
             d0 = d[0]; d1 = d[1]; d2 = d[2];
@@ -535,7 +613,7 @@ __device__ __forceinline__ void mlp_fwd_pipe_tile(
         if constexpr (FUSED && NR > 0) {
             // the tile holds whole rays (128 % S == 0): raw and z staged in buf0 (free since the barrier in front of the views GEMM), then
             // composite_kernel<NR>'s lane ownership - wave w composites the tile's rays w, w + 4, ...
-            if (half == 0) reinterpret_cast<f32x4*>(buf0)[wave * 32 + (lane & 31)] = f32x4{rgb[0], rgb[1], rgb[2], sigma};
+            if (half == 0) reinterpret_cast<f32x4*>(buf0)[wave * 32 + (lane_o & 31)] = f32x4{rgb[0], rgb[1], rgb[2], sigma};
             float* zs = buf0 + 4 * 128;
             if (tid < 128) zs[tid] = z_pre;
             __syncthreads();

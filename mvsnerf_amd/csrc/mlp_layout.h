@@ -64,6 +64,7 @@ constexpr int V_FEAT = 128 * 7;         // feature_linear bias
 constexpr int V_VIEWS = 128 * 8;        // [2][32] views_linears.0 bias
 constexpr int V_WA = V_VIEWS + 64;      // [2][64] alpha_linear weight
 constexpr int V_BA = V_WA + 128;        // alpha bias (+3 pad)
+constexpr int V_FOLD = V_BA + 1;        // first pad float: 0.0f = standard buffer, 1.0f = a fold tail follows the buffer (below)
 constexpr int V_WR = V_BA + 4;          // [3][2][32] rgb_linear weight
 constexpr int V_BR = V_WR + 192;        // rgb bias (3, +1 pad)
 constexpr int V_TOTAL = V_BR + 4;       // 1416
@@ -87,6 +88,15 @@ __host__ __device__ inline Layout layout(int F)
     L.total = o;
     return L;
 }
+
+// Fold tail (mvsnerf_mlp_pack_fold): feature_linear and views_linears.0 have no activation between them (models.py:209-215), so for a
+// no-grad forward they are one affine map W' = Wv[:, :128] * Wf, b' = bv + Wv[:, :128] * bf.  A buffer whose V_FOLD is 1.0f carries, behind
+// the standard layout (which is complete and unchanged), the views segment built from [W' | Wv[:, 128:131]] in the fragment order of
+// `views` (K_VIEWS), then b' as [2][32] in act_n order like V_VIEWS.  The fp32 no-grad kernels skip the feature_linear GEMM on such a
+// buffer; the training forward, the backward and the 16-bit kernels read the standard part only.
+__host__ __device__ inline size_t fold_views_off(int F) { return (layout(F).total + 3) & ~(size_t)3; }
+__host__ __device__ inline size_t fold_bias_off(int F) { return fold_views_off(F) + seg_floats(VIEW_STEPS, 2); }
+__host__ __device__ inline size_t fold_total(int F) { return fold_bias_off(F) + 64; }
 
 // ------------------------------------------------------------------------------------------------
 // Training: activations saved by the forward pass / gradients written by the dgrad kernel, in "slot" format.

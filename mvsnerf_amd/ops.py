@@ -323,8 +323,9 @@ MLP_ORDER = [f"pts_linears.{i}" for i in range(6)] + ["pts_bias", "feature_linea
 
 
 def mlp_pack(weights, biases, F):
-    """weights/biases: 11 contiguous fp32 GPU tensors in MLP_ORDER -> packed fragment-ordered buffer."""
-    n = _lib.lib().mvsnerf_mlp_packed_floats(F)
+    """weights/biases: 11 contiguous fp32 GPU tensors in MLP_ORDER -> packed fragment-ordered buffer: the standard layout plus the fold tail
+    (feature_linear folded into views_linears.0 for the fp32 no-grad kernels; include/mvsnerf_hip_internal.h)."""
+    n = _lib.lib().mvsnerf_mlp_packed_fold_floats(F)
     if n == 0:
         raise RuntimeError(f"mlp_pack: feat_dim {F} unsupported (must be even, <= 40)")
     expect = [(128, 63)] + [(128, 128)] * 4 + [(128, 191), (128, F), (128, 128), (1, 128), (64, 131), (3, 64)]
@@ -335,7 +336,7 @@ def mlp_pack(weights, biases, F):
     packed = torch.empty(n, device=weights[0].device, dtype=torch.float32)
     wp = (ctypes.c_void_p * 11)(*[dev_f32(w, "weight") for w in weights])
     bp = (ctypes.c_void_p * 11)(*[dev_f32(b, "bias") for b in biases])
-    check(_lib.lib().mvsnerf_mlp_pack(wp, bp, F, packed.data_ptr(), stream_ptr()), "mlp_pack")
+    check(_lib.lib().mvsnerf_mlp_pack_fold(wp, bp, F, packed.data_ptr(), stream_ptr()), "mlp_pack")
     return packed
 
 
