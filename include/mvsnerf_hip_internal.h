@@ -194,6 +194,18 @@ int mvsnerf_mlp_fwd_census(const float* packed, int F,
  * memory that held a folded buffer before. */
 size_t mvsnerf_mlp_packed_fold_floats(int F);
 int mvsnerf_mlp_pack_fold(const float* const w[11], const float* const b[11], int F, float* packed, void* stream);
+/* Network variant.  The reference has two radiance MLPs with the same layers and state_dict keys: Renderer_ours (net_type v0),
+ * h_i = relu(pts_linears.i(h) * bias), and Renderer_linear (net_type v2), h_i = relu(pts_linears.i(h) + bias), bias = pts_bias(feat); v2's
+ * forward_alpha also returns alpha_linear(h) without the ReLU.  The packed buffer carries the variant like the fold: the vector block is
+ * [.. | alpha bias (V_BA) | fold flag (V_BA + 1) | variant flag (V_BA + 2) | pad | rgb_linear ..] and variant = 1 writes 1.0f to the variant
+ * flag; everything else is mvsnerf_mlp_pack_fold's output bit for bit (mvsnerf_mlp_packed_fold_floats(F) floats).  mvsnerf_mlp_pack and
+ * mvsnerf_mlp_pack_fold always write 0.0f there.  Every fp32 kernel handed the buffer reads the flag: mvsnerf_mlp_fwd (alpha_only = 1 on a
+ * v2 buffer writes the un-clamped sigma, which can be negative; the full forward clamps), mvsnerf_mlp_fwd_guarded's fp32 half,
+ * mvsnerf_raymarch_fwd*, mvsnerf_render_*, mvsnerf_mlp_fwd_train / mvsnerf_raymarch_train_fwd and mvsnerf_mlp_bwd / mvsnerf_raymarch_bwd with
+ * bf16 = 0.  The 16-bit kernels (bf16, split, fp16x3, the bf16 backward) do NOT read it and compute the v0 network from any buffer: their
+ * scaling assumes the multiplicative form.  A v2 network must therefore stay on the fp32 kernels (the Python layer enforces it).
+ * variant: 0 = v0 (multiplicative), 1 = v2 (additive); anything else is MVSNERF_EINVAL. */
+int mvsnerf_mlp_pack_fold_variant(const float* const w[11], const float* const b[11], int F, int variant, float* packed, void* stream);
 /* (described in mvsnerf_hip.h: "---- Guarded 16-bit sequences (ABI v10) ---- ...") */
 typedef struct {
     const float* feats_cl; const float* imgs_cl;   /* [V][H][W][32], [V][H][W][4] as for mvsnerf_planesweep_costvar_fwd (with_img = 1) */

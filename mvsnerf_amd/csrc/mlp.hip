@@ -8,6 +8,8 @@
 // memory.  MFMA-bound: 251 392 FLOP per point (the reference network's count; 1 976 MFMAs per wave of 32 points) against 12 B + 4*F B read
 // and 16 B written.  With a folded buffer (mvsnerf_mlp_pack_fold, mlp_layout.h) the no-grad kernels run feature_linear and views_linears.0 as one
 // affine map: 1 720 MFMAs per wave, 218 624 FLOP per point issued for the same result.
+// Renderer_linear (net_type v2, models.py:464-538) is the same network with h = relu(p + bias) for relu(p * bias) and an un-clamped forward_alpha:
+// a buffer whose V_ADD is 1.0f (mvsnerf_mlp_pack_fold_variant, mlp_layout.h) selects it in every kernel of this file, the matrix work is identical.
 #include "common.h"
 #include "mlp_layout.h"
 #include "lds_dma.h"
@@ -24,6 +26,7 @@ struct PackArgs {
     const float* w[11];
     const float* b[11];
     int F;
+    float add;      // V_ADD: 0.0f = h = relu(p * bias) (Renderer_ours), 1.0f = h = relu(p + bias) (Renderer_linear)
 };
 // order of w/b: 0..5 pts_linears, 6 pts_bias, 7 feature_linear, 8 alpha_linear, 9 views_linears.0, 10 rgb_linear
 
@@ -73,7 +76,7 @@ __global__ __launch_bounds__(256) void mlp_pack_kernel(PackArgs a, float* __rest
             const int k = i - V_WA;
             x = a.w[8][act_n(k & 63, k >> 6)];
         } else if (i < V_WR) {
-            x = (i == V_BA) ? a.b[8][0] : (FOLD && i == V_FOLD) ? 1.0f : 0.0f;
+            x = (i == V_BA) ? a.b[8][0] : (FOLD && i == V_FOLD) ? 1.0f : (i == V_ADD) ? a.add : 0.0f;
         } else if (i < V_BR) {                   // rgb weight [3][2][32]
             const int k = i - V_WR, c = k >> 6, h = (k >> 5) & 1, q = k & 31;
             x = a.w[10][c * 64 + act_n(q, h)];
@@ -129,7 +132,7 @@ extern "C" size_t mvsnerf_mlp_packed_fold_floats(int F)
 }
 
 template <bool FOLD>
-static int mlp_pack_impl(const float* const w[11], const float* const b[11], int F, float* packed, void* stream)
+static int mlp_pack_impl(const float* const w[11], const float* const b[11], int F, float* packed, void* stream, float add = 0.0f)
 {
     if (!w || !b || !packed) return MVSNERF_EINVAL;
     if (F < 2 || F > MAX_F || (F & 1)) return MVSNERF_EUNSUPPORTED;
@@ -140,6 +143,7 @@ static int mlp_pack_impl(const float* const w[11], const float* const b[11], int
         a.w[i] = w[i]; a.b[i] = b[i];
     }
     a.F = F;
+    a.add = add;
     mlp_pack_kernel<FOLD><<<64, 256, 0, (hipStream_t)stream>>>(a, packed);
     MVS_LAUNCH_CHECK();
     return MVSNERF_OK;
@@ -153,6 +157,14 @@ extern "C" int mvsnerf_mlp_pack(const float* const w[11], const float* const b[1
 extern "C" int mvsnerf_mlp_pack_fold(const float* const w[11], const float* const b[11], int F, float* packed, void* stream)
 {
     return mlp_pack_impl<true>(w, b, F, packed, stream);
+}
+
+// The folded buffer of a given network variant: 0 = Renderer_ours (what the two entries above write), 1 = Renderer_linear (V_ADD = 1.0f,
+// mlp_layout.h).  Same size and, but for that one float, the same bits as mvsnerf_mlp_pack_fold.
+extern "C" int mvsnerf_mlp_pack_fold_variant(const float* const w[11], const float* const b[11], int F, int variant, float* packed, void* stream)
+{
+    if (variant != 0 && variant != 1) return MVSNERF_EINVAL;
+    return mlp_pack_impl<true>(w, b, F, packed, stream, variant ? 1.0f : 0.0f);
 }
 
 // ------------------------------------------------------------------------------------------ compute
@@ -446,6 +458,10 @@ __device__ __forceinline__ void mlp_fwd_pipe_tile(
         fold = __builtin_amdgcn_readfirstlane(__float_as_int(vec[V_FOLD])) != 0;
         if (fold && wave == 0) lds_dma_dword(packed + fold_bias_off(F), lds_byte_addr(vec + V_VIEWS), lane * 4);
     }
+    // Additive network (V_ADD, mlp_layout.h: Renderer_linear, h = relu(p + bias)): the same kind of self-description, read by every form of
+    // this tile - the training forward included, its backward reads the same flag.  Wave-uniform; the multiplicative branch below is the
+    // code this kernel always had.
+    const bool add = __builtin_amdgcn_readfirstlane(__float_as_int(vec[V_ADD])) != 0;
     stamp();                                                                                // [4] startup done
     {
         f32x16 acc[G][4];
@@ -484,11 +500,22 @@ __device__ __forceinline__ void mlp_fwd_pipe_tile(
         f32x16 acc[G][4];
         init_acc<4, G>(acc, vec + V_L0 + half * 64);
         gemm_stage<PE_STEPS / 4, 4, G>(buf1, acc, lane, pe);
+        if (add) {
 #pragma unroll
-        for (int q = 0; q < 64; q += 2) {
-            const f32x2 m2 = f32x2{acc[0][q >> 4][q & 15], acc[0][q >> 4][(q & 15) + 1]} * f32x2{bias[q], bias[q + 1]};   // v_pk_mul_f32
-            h[q] = fmaxf(m2[0], 0.0f); h[q + 1] = fmaxf(m2[1], 0.0f);
-            save(S_H + q, h[q]); save(S_H + q + 1, h[q + 1]);
+            for (int q = 0; q < 64; q += 2) {
+                const f32x2 m2 = f32x2{acc[0][q >> 4][q & 15], acc[0][q >> 4][(q & 15) + 1]} + f32x2{bias[q], bias[q + 1]};   // v_pk_add_f32
+                h[q] = fmaxf(m2[0], 0.0f); h[q + 1] = fmaxf(m2[1], 0.0f);
+            }
+        } else {
+#pragma unroll
+            for (int q = 0; q < 64; q += 2) {
+                const f32x2 m2 = f32x2{acc[0][q >> 4][q & 15], acc[0][q >> 4][(q & 15) + 1]} * f32x2{bias[q], bias[q + 1]};   // v_pk_mul_f32
+                h[q] = fmaxf(m2[0], 0.0f); h[q + 1] = fmaxf(m2[1], 0.0f);
+            }
+        }
+        if constexpr (SAVE) {
+#pragma unroll
+            for (int q = 0; q < 64; ++q) save(S_H + q, h[q]);
         }
     }
     stamp();                                                                                // [6] layer 0 done
@@ -503,11 +530,22 @@ __device__ __forceinline__ void mlp_fwd_pipe_tile(
         slab_sync();
         // next slab: first half of the next layer, or the positional-encoding part of layer 5
         gemm_stage<8, 4, G>(buf1, acc, lane, hhi, [&]() { slab_dma_c<HALF>(buf0, layer < 4 ? wl + 2 * HALF : packed + L.l5a, wave, lane); });
+        if (add) {
 #pragma unroll
-        for (int q = 0; q < 64; q += 2) {
-            const f32x2 m2 = f32x2{acc[0][q >> 4][q & 15], acc[0][q >> 4][(q & 15) + 1]} * f32x2{bias[q], bias[q + 1]};   // v_pk_mul_f32
-            h[q] = fmaxf(m2[0], 0.0f); h[q + 1] = fmaxf(m2[1], 0.0f);
-            save(S_H + layer * 64 + q, h[q]); save(S_H + layer * 64 + q + 1, h[q + 1]);
+            for (int q = 0; q < 64; q += 2) {
+                const f32x2 m2 = f32x2{acc[0][q >> 4][q & 15], acc[0][q >> 4][(q & 15) + 1]} + f32x2{bias[q], bias[q + 1]};   // v_pk_add_f32
+                h[q] = fmaxf(m2[0], 0.0f); h[q + 1] = fmaxf(m2[1], 0.0f);
+            }
+        } else {
+#pragma unroll
+            for (int q = 0; q < 64; q += 2) {
+                const f32x2 m2 = f32x2{acc[0][q >> 4][q & 15], acc[0][q >> 4][(q & 15) + 1]} * f32x2{bias[q], bias[q + 1]};   // v_pk_mul_f32
+                h[q] = fmaxf(m2[0], 0.0f); h[q + 1] = fmaxf(m2[1], 0.0f);
+            }
+        }
+        if constexpr (SAVE) {
+#pragma unroll
+            for (int q = 0; q < 64; ++q) save(S_H + layer * 64 + q, h[q]);
         }
         stamp();                                                                            // [7..10] layers 1..4 done
     }
@@ -527,18 +565,32 @@ __device__ __forceinline__ void mlp_fwd_pipe_tile(
             if constexpr (SAVE) slab_dma_c<HALF>(buf1, packed + L.feat, wave, lane);
             else if constexpr (!ALPHA_ONLY) slab_dma_c<(int)seg_floats(VIEW_STEPS, 2)>(buf1, packed + (fold ? fold_views_off(F) : L.feat), wave, lane);
         });
+        if (add) {
 #pragma unroll
-        for (int q = 0; q < 64; q += 2) {
-            const f32x2 m2 = f32x2{acc[0][q >> 4][q & 15], acc[0][q >> 4][(q & 15) + 1]} * f32x2{bias[q], bias[q + 1]};   // v_pk_mul_f32
-            h[q] = fmaxf(m2[0], 0.0f); h[q + 1] = fmaxf(m2[1], 0.0f);
-            save(S_H + 5 * 64 + q, h[q]); save(S_H + 5 * 64 + q + 1, h[q + 1]);
+            for (int q = 0; q < 64; q += 2) {
+                const f32x2 m2 = f32x2{acc[0][q >> 4][q & 15], acc[0][q >> 4][(q & 15) + 1]} + f32x2{bias[q], bias[q + 1]};   // v_pk_add_f32
+                h[q] = fmaxf(m2[0], 0.0f); h[q + 1] = fmaxf(m2[1], 0.0f);
+            }
+        } else {
+#pragma unroll
+            for (int q = 0; q < 64; q += 2) {
+                const f32x2 m2 = f32x2{acc[0][q >> 4][q & 15], acc[0][q >> 4][(q & 15) + 1]} * f32x2{bias[q], bias[q + 1]};   // v_pk_mul_f32
+                h[q] = fmaxf(m2[0], 0.0f); h[q + 1] = fmaxf(m2[1], 0.0f);
+            }
+        }
+        if constexpr (SAVE) {
+#pragma unroll
+            for (int q = 0; q < 64; ++q) save(S_H + 5 * 64 + q, h[q]);
         }
         const float* wa = vec + V_WA + half * 64;
         float part = 0.0f;
 #pragma unroll
         for (int q = 0; q < 64; ++q) part = fmaf(wa[q], h[q], part);
         part += __shfl_xor(part, 32);
-        sigma = fmaxf(part + vec[V_BA], 0.0f);
+        sigma = part + vec[V_BA];
+        // Renderer_linear.forward_alpha returns alpha_linear(h) without the ReLU (its forward keeps it): only a sigma-only launch on an
+        // additive buffer writes the un-clamped value
+        if (!(ALPHA_ONLY && add)) sigma = fmaxf(sigma, 0.0f);
     }
     stamp();                                                                                // [11] layer 5 + sigma head done
     if (ALPHA_ONLY) {

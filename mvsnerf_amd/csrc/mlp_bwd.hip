@@ -278,17 +278,30 @@ __global__ __launch_bounds__(256, 1) void mlp_dgrad_kernel(
         for (int q = 0; q < 64; ++q) gh[q] = fmaf(wa[q], gsg, acc[q >> 4][q & 15]);
     }
     // pts_linears 5..0:  h_i = relu(p_i * b)  =>  gq = gh*[h_i>0], gp_i = gq*b, gb += gq*p_i = gq*h_i/b
+    // An additive buffer (V_ADD of the forward vector block, mlp_layout.h; fp32 only - the bf16 path keeps the multiplicative form) takes the
+    // wave-uniform branch below instead.
+    bool add = false;
+    if constexpr (!BF) add = __builtin_amdgcn_readfirstlane(__float_as_int(vec[V_ADD])) != 0;
     float bm[64], gbm[64];
 #pragma unroll
     for (int q = 0; q < 64; ++q) { bm[q] = (float)sv[(S_BM + q) * 64]; gbm[q] = 0.0f; }
 #pragma unroll 1
     for (int layer = 5; layer >= 0; --layer) {
+        if (add) {                           // h_i = relu(p_i + b): gp_i = gq, gb += gq
 #pragma unroll
-        for (int q = 0; q < 64; ++q) {
-            const bool on = hq[q] > 0.0f;
-            const float gq = on ? gh[q] : 0.0f;
-            gbm[q] += on ? gq * (hq[q] / bm[q]) : 0.0f;
-            gh[q] = gq * bm[q];
+            for (int q = 0; q < 64; ++q) {
+                const float gq = hq[q] > 0.0f ? gh[q] : 0.0f;
+                gbm[q] += gq;
+                gh[q] = gq;
+            }
+        } else {
+#pragma unroll
+            for (int q = 0; q < 64; ++q) {
+                const bool on = hq[q] > 0.0f;
+                const float gq = on ? gh[q] : 0.0f;
+                gbm[q] += on ? gq * (hq[q] / bm[q]) : 0.0f;
+                gh[q] = gq * bm[q];
+            }
         }
         // segment (7 - layer) for this layer's transposed GEMM sits in buf[(layer + 1) & 1]: l5 -> buf0, l4 -> buf1, ...
         float* cur = (layer & 1) ? buf0 : buf1;

@@ -1,4 +1,4 @@
-// Packed-weight layout of the fused Renderer_ours MLP kernel (shared by the pack kernel, the
+// Packed-weight layout of the fused Renderer_ours / Renderer_linear MLP kernel (shared by the pack kernel, the
 // compute kernel and the host-side size query).
 //
 // The kernel computes every layer TRANSPOSED: out^T[n][m] = sum_k W[n][k] * act[k][m] with the weights
@@ -65,6 +65,7 @@ constexpr int V_VIEWS = 128 * 8;        // [2][32] views_linears.0 bias
 constexpr int V_WA = V_VIEWS + 64;      // [2][64] alpha_linear weight
 constexpr int V_BA = V_WA + 128;        // alpha bias (+3 pad)
 constexpr int V_FOLD = V_BA + 1;        // first pad float: 0.0f = standard buffer, 1.0f = a fold tail follows the buffer (below)
+constexpr int V_ADD = V_BA + 2;         // second pad float: 0.0f = h_i = relu(pts_linears.i(h) * bias) (Renderer_ours, net_type v0), 1.0f = relu(.. + bias) (Renderer_linear, v2)
 constexpr int V_WR = V_BA + 4;          // [3][2][32] rgb_linear weight
 constexpr int V_BR = V_WR + 192;        // rgb bias (3, +1 pad)
 constexpr int V_TOTAL = V_BR + 4;       // 1416
@@ -112,7 +113,7 @@ constexpr int S_HV = 560;         // 32 slots: relu(views_linears[0])
 constexpr int S_DR = 592;         // 16 slots: slot 0 = (d0,d1), slot 1 = (d2,0); rest unused
 constexpr int SLOTS_SAVED = 608;
 // written by the dgrad kernel
-constexpr int G_GP = 0;           // 6 x 64 slots: grad wrt the pre-activation of pts_linears[i] (already x bias)
+constexpr int G_GP = 0;           // 6 x 64 slots: grad wrt the output of pts_linears[i] (multiplicative network: already x bias; additive, V_ADD: the masked gradient itself)
 constexpr int G_GBM = 384;        // 64 slots: grad wrt pts_bias output
 constexpr int G_GF = 448;         // 64 slots: grad wrt feature_linear output
 constexpr int G_GPV = 512;        // 32 slots: grad wrt views_linears[0] pre-activation

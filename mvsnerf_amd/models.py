@@ -54,17 +54,22 @@ def get_embedder(multires, i=0, input_dims=3):
 
 
 # ------------------------------------------------------------------ radiance MLP
-class Renderer_ours(nn.Module):
-    """reference models.py:145-222 (net_type 'v0', the architecture of the shipped checkpoint).
+class _RendererMLP(nn.Module):
+    """What the reference's two radiance MLPs share: every layer shape and state_dict key, the packed-weight caches and the queries.
+    A subclass names the network variant the kernels run (`_variant`, the `variant` argument of mvsnerf_mlp_pack_fold_variant):
+        0  h_i = relu(pts_linears.i(h) * bias)   Renderer_ours   (net_type 'v0')
+        1  h_i = relu(pts_linears.i(h) + bias)   Renderer_linear (net_type 'v2'; forward_alpha without the ReLU)
+    with bias = pts_bias(feat).
     forward(x) / forward_alpha(x) take the reference's concatenated rows
         x = [embed(pts)(63) | feat(F) | dir(3)]      (forward_alpha: no dir)
     and run the fused HIP kernel on them in place: the kernel reads pts from x[..., :3] (the embedding's
     leading copy of the input, models.py:50) and re-derives the sin/cos terms in registers."""
 
-    def __init__(self, D=8, W=256, input_ch=3, input_ch_views=3, output_ch=4, input_ch_feat=8, skips=[4], use_viewdirs=False):
-        super().__init__()
+    _variant = 0
+
+    def _build(self, D, W, input_ch, input_ch_views, output_ch, input_ch_feat, skips, use_viewdirs):
         if not use_viewdirs:
-            raise NotImplementedError("Renderer_ours(use_viewdirs=False) cannot even be constructed in the reference (models.py:172)")
+            raise NotImplementedError(f"{type(self).__name__}(use_viewdirs=False) cannot even be constructed in the reference (models.py:172, 491)")
         self.D, self.W, self.skips = D, W, list(skips)
         self.input_ch, self.input_ch_views, self.use_viewdirs = input_ch, input_ch_views, use_viewdirs
         self.in_ch_pts, self.in_ch_views, self.in_ch_feat = input_ch, input_ch_views, input_ch_feat
@@ -94,12 +99,21 @@ class Renderer_ours(nn.Module):
             raise NotImplementedError(
                 "the HIP MLP kernel is specialised for netdepth=6, netwidth=128, skips=[4], multires=10, raw view dirs "
                 f"(got D={self.D}, W={self.W}, skips={self.skips}, in_ch_pts={self.in_ch_pts}, in_ch_views={self.in_ch_views})")
+        self.need_fp32_mode(ops.MLP_PRECISION)
         key = self._weights_key()
         if self._packed is None or key != self._packed_key:
             lins = self._linears()
-            self._packed = ops.mlp_pack([l.weight.detach() for l in lins], [l.bias.detach() for l in lins], F)
+            self._packed = ops.mlp_pack([l.weight.detach() for l in lins], [l.bias.detach() for l in lins], F, variant=self._variant)
             self._packed_key = key
         return self._packed
+
+    def need_fp32_mode(self, mode):
+        """The additive network runs on the fp32 kernels only (the 16-bit kernels' exponent management assumes the multiplicative form): under
+        "auto" it resolves to them, an explicit 16-bit mode - what use_amp sets - is refused before anything is packed or launched."""
+        if self._variant and mode not in ("auto", "fp32"):
+            raise NotImplementedError(
+                f"net_type v2 ({type(self).__name__}) runs on the fp32 MLP kernels only: mlp precision {mode!r} (use_amp sets 'bf16') is built "
+                "for net_type v0; use ops.set_mlp_precision('fp32') or 'auto'")
 
     def _weights_key(self):
         """(optimizer-step epoch, data_ptr and _version of the 22 tensors).  The Parameter objects are looked up through nn.Module.__getattr__
@@ -156,6 +170,9 @@ class Renderer_ours(nn.Module):
     def packed_alt(self, feat_dim=None, fresh=False):
         """Keyword arguments selecting the MLP kernel of ops.raymarch / ops.render_pixels / ops.mlp_forward for the current ops.MLP_PRECISION."""
         mode = ops.inference_mlp_mode()
+        if self._variant:            # net_type v2: "auto" resolves to the fp32 kernel, a 16-bit mode raises
+            self.need_fp32_mode(ops.MLP_PRECISION)
+            return {}
         if mode == "bf16":
             return {"packed_bf16": self.packed_bf16(feat_dim, fresh)}
         if mode == "guarded":        # the default: fp16x3 kernel + predicated fp32-MFMA kernel behind it (ops.set_mlp_precision)
@@ -167,7 +184,7 @@ class Renderer_ours(nn.Module):
     # -- queries ----------------------------------------------------------------------------
     def query(self, pts, feat, viewdirs, N, S):
         """pts (N,S,3) NDC, feat (N,S,F), viewdirs (N,3) per ray or None (sigma only) -> (N*S, 4|1)."""
-        ops._need_no_grad(pts, feat, viewdirs, *self.parameters(), op="Renderer_ours")
+        ops._need_no_grad(pts, feat, viewdirs, *self.parameters(), op=type(self).__name__)
         pts, feat = pts.contiguous(), feat.contiguous()
         alpha_only = viewdirs is None
         F = feat.shape[-1]
@@ -177,7 +194,7 @@ class Renderer_ours(nn.Module):
                                **self.packed_alt(F))
 
     def _rows(self, x, alpha_only):
-        ops._need_no_grad(x, *self.parameters(), op="Renderer_ours")
+        ops._need_no_grad(x, *self.parameters(), op=type(self).__name__)
         width = x.shape[-1]
         F = width - self.in_ch_pts - (0 if alpha_only else self.in_ch_views)
         x2 = x.reshape(-1, width).contiguous()
@@ -194,17 +211,40 @@ class Renderer_ours(nn.Module):
         return self._rows(x, False)
 
 
+class Renderer_ours(_RendererMLP):
+    """reference models.py:145-222 (net_type 'v0', the architecture of the shipped checkpoint): h_i = relu(pts_linears.i(h) * pts_bias(feat))."""
+    _variant = 0
+
+    def __init__(self, D=8, W=256, input_ch=3, input_ch_views=3, output_ch=4, input_ch_feat=8, skips=[4], use_viewdirs=False):
+        super().__init__()
+        self._build(D, W, input_ch, input_ch_views, output_ch, input_ch_feat, skips, use_viewdirs)
+
+
+class Renderer_linear(_RendererMLP):
+    """reference models.py:464-538 (net_type 'v2', MVSNeRF's class default): h_i = relu(pts_linears.i(h) + pts_bias(feat)); forward_alpha
+    returns alpha_linear(h) WITHOUT the ReLU (models.py:507) - sigma-only queries (render_density, the density volume of importance sampling)
+    see negative values, as in the reference - while forward keeps it (models.py:525).  fp32 kernels only (need_fp32_mode)."""
+    _variant = 1
+
+    def __init__(self, D=8, W=256, input_ch=3, input_ch_views=3, output_ch=4, input_ch_feat=8, skips=[4], use_viewdirs=False):
+        super().__init__()
+        self._build(D, W, input_ch, input_ch_views, output_ch, input_ch_feat, skips, use_viewdirs)
+
+
+_NET_TYPES = {"v0": Renderer_ours, "v2": Renderer_linear}
+
+
 class MVSNeRF(nn.Module):
     """reference models.py:540-567: wrapper holding the renderer as `.nerf` (checkpoint keys `nerf.*`)."""
 
     def __init__(self, D=8, W=256, input_ch_pts=3, input_ch_views=3, input_ch_feat=8, skips=[4], net_type="v2"):
         super().__init__()
         self.in_ch_pts, self.in_ch_views, self.in_ch_feat = input_ch_pts, input_ch_views, input_ch_feat
-        if net_type != "v0":
+        if net_type not in _NET_TYPES:
             raise NotImplementedError(
-                f"net_type {net_type!r}: only 'v0' (Renderer_ours, the shipped checkpoint) is on the hot path; "
-                "v1/v2 have no weights in the reference and v1 is dead code (SURVEY.md 2)")
-        self.nerf = Renderer_ours(D=D, W=W, input_ch_feat=input_ch_feat, input_ch=input_ch_pts, output_ch=4, skips=skips,
+                f"net_type {net_type!r}: 'v0' (Renderer_ours, the shipped checkpoint) and 'v2' (Renderer_linear) are on the hot path; "
+                "v1 (Renderer_attention) is dead code in the reference (SURVEY.md 2)")
+        self.nerf = _NET_TYPES[net_type](D=D, W=W, input_ch_feat=input_ch_feat, input_ch=input_ch_pts, output_ch=4, skips=skips,
                                   input_ch_views=input_ch_views, use_viewdirs=True)
 
     def packed(self, feat_dim=None):

@@ -322,9 +322,13 @@ def ray_marcher_fine_z(density_volume, rays_ndc, z_vals, u):
 MLP_ORDER = [f"pts_linears.{i}" for i in range(6)] + ["pts_bias", "feature_linear", "alpha_linear", "views_linears.0", "rgb_linear"]
 
 
-def mlp_pack(weights, biases, F):
+def mlp_pack(weights, biases, F, variant=0):
     """weights/biases: 11 contiguous fp32 GPU tensors in MLP_ORDER -> packed fragment-ordered buffer: the standard layout plus the fold tail
-    (feature_linear folded into views_linears.0 for the fp32 no-grad kernels; include/mvsnerf_hip_internal.h)."""
+    (feature_linear folded into views_linears.0 for the fp32 no-grad kernels; include/mvsnerf_hip_internal.h).
+    variant: 0 = Renderer_ours (h = relu(p * bias)), 1 = Renderer_linear (h = relu(p + bias), un-clamped sigma-only output); the buffer carries
+    it and every fp32 kernel handed the buffer follows it - the 16-bit kernels do not (models.Renderer_linear keeps v2 off them)."""
+    if variant not in (0, 1):
+        raise ValueError(f"mlp_pack: variant must be 0 (Renderer_ours) or 1 (Renderer_linear), got {variant!r}")
     n = _lib.lib().mvsnerf_mlp_packed_fold_floats(F)
     if n == 0:
         raise RuntimeError(f"mlp_pack: feat_dim {F} unsupported (must be even, <= 40)")
@@ -336,7 +340,10 @@ def mlp_pack(weights, biases, F):
     packed = torch.empty(n, device=weights[0].device, dtype=torch.float32)
     wp = (ctypes.c_void_p * 11)(*[dev_f32(w, "weight") for w in weights])
     bp = (ctypes.c_void_p * 11)(*[dev_f32(b, "bias") for b in biases])
-    check(_lib.lib().mvsnerf_mlp_pack_fold(wp, bp, F, packed.data_ptr(), stream_ptr()), "mlp_pack")
+    if variant:
+        check(_lib.lib().mvsnerf_mlp_pack_fold_variant(wp, bp, F, int(variant), packed.data_ptr(), stream_ptr()), "mlp_pack")
+    else:
+        check(_lib.lib().mvsnerf_mlp_pack_fold(wp, bp, F, packed.data_ptr(), stream_ptr()), "mlp_pack")
     return packed
 
 

@@ -52,8 +52,8 @@ def run_network_mvs(pts, viewdirs, alpha_feat, fn, embed_fn, embeddirs_fn, netch
                 and embeddirs_fn is None and alpha_feat is not None)
     if not fused_ok:
         raise NotImplementedError(
-            "run_network_mvs: only the configuration the reference ships is built as a HIP kernel "
-            "(MVSNeRF net_type v0, pts embedder multires=10, no dir embedder, alpha_feat given)")
+            "run_network_mvs: only the configurations the reference trains are built as a HIP kernel "
+            "(MVSNeRF net_type v0 or v2, pts embedder multires=10, no dir embedder, alpha_feat given)")
     if viewdirs is not None and viewdirs.dim() == 3:
         raise NotImplementedError("run_network_mvs: per-sample view directions are not on the hot path")
     N, S = pts.shape[:2]
