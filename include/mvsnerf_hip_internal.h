@@ -204,7 +204,10 @@ int mvsnerf_mlp_pack_fold(const float* const w[11], const float* const b[11], in
  * mvsnerf_raymarch_fwd*, mvsnerf_render_*, mvsnerf_mlp_fwd_train / mvsnerf_raymarch_train_fwd and mvsnerf_mlp_bwd / mvsnerf_raymarch_bwd with
  * bf16 = 0.  The 16-bit kernels (bf16, split, fp16x3, the bf16 backward) do NOT read it and compute the v0 network from any buffer: their
  * scaling assumes the multiplicative form.  A v2 network must therefore stay on the fp32 kernels (the Python layer enforces it).
- * variant: 0 = v0 (multiplicative), 1 = v2 (additive); anything else is MVSNERF_EINVAL. */
+ * variant: 0 = v0 (multiplicative), 1 = v2 (additive); anything else is MVSNERF_EINVAL.
+ * F: even, 2 <= F <= 40 for every entry above and for the training entries that consume these buffers (mvsnerf_mlp_fwd_train, mvsnerf_mlp_bwd:
+ * v0 and v2 alike; the saved-activation format keeps feature operands 16..19 of an F > 32 row in slots 2..5 of its direction block,
+ * csrc/mlp_layout.h S_FV_HI). */
 int mvsnerf_mlp_pack_fold_variant(const float* const w[11], const float* const b[11], int F, int variant, float* packed, void* stream);
 /* (described in mvsnerf_hip.h: "---- Guarded 16-bit sequences (ABI v10) ---- ...") */
 typedef struct {

@@ -479,6 +479,10 @@ __device__ __forceinline__ void mlp_fwd_pipe_tile(
         if (SAVE) {
 #pragma unroll
             for (int t = 0; t < 16; ++t) save(S_FV + t, fv[t]);
+            if (F > 32) {                          // kernel argument: uniform.  Feature operands 16..19 (zero from F/2 on) go to S_FV_HI (mlp_layout.h)
+#pragma unroll
+                for (int t = 16; t < MAX_F / 2; ++t) save(S_FV_HI + t - 16, fv[t]);
+            }
 #pragma unroll
             for (int t = 0; t < PE_STEPS; ++t) save(S_E + t, pe_operand(t, half, px, py, pz));
         }
@@ -836,7 +840,7 @@ extern "C" int mvsnerf_mlp_fwd_train(const float* packed, int F, const float* nd
                                      const float* dirs, int dirs_stride, int64_t N, int S, float* raw, float* saved, void* stream)
 {
     if (!packed || !ndc || !feat || !dirs || !raw || !saved || N < 0 || S < 1 || feat_stride < F || ndc_stride < 3 || dirs_stride < 3) return MVSNERF_EINVAL;
-    if (F < 2 || F > 32 || (F & 1)) return MVSNERF_EUNSUPPORTED;
+    if (F < 2 || F > MAX_F || (F & 1)) return MVSNERF_EUNSUPPORTED;
     if (!mvs_aligned16(packed) || !mvs_aligned16(raw) || !mvs_aligned16(saved)) return MVSNERF_EALIGN;
     const int64_t P = N * S;
     if (P == 0) return MVSNERF_OK;

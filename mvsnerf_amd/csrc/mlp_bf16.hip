@@ -169,7 +169,7 @@ __global__ __launch_bounds__(256, 2) void mlp_fwd_bf16_kernel(
     slabb_dma(buf0, wq + L.featw, L.l1 - L.featw, wave, lane);
     for (int i = tid; i < V_TOTAL; i += 256) vec[i] = packed_f32[LF.vec + i];
     const float px = ndc[p * ndc_stride + 0], py = ndc[p * ndc_stride + 1], pz = ndc[p * ndc_stride + 2];
-    float fv[24];                                 // F/2 <= 20 feature operands of this lane half (the store keeps the first 16: F <= 32 when training)
+    float fv[24];                                 // F/2 <= 20 feature operands of this lane half (the store keeps all of them: 16 at S_FV, 16..19 at S_FV_HI when F > 32)
     {
         const float* fp = feat + p * feat_stride + half * (F / 2);
         // (the compiler turns this into one scalar branch + one load per element; issuing all 24 unconditionally - padding slots re-reading element 0 - measured
@@ -191,6 +191,10 @@ __global__ __launch_bounds__(256, 2) void mlp_fwd_bf16_kernel(
     if (SAVE) {
 #pragma unroll
         for (int t = 0; t < 16; ++t) save(S_FV + t, fv[t]);
+        if (F > 32) {                              // kernel argument: uniform
+#pragma unroll
+            for (int t = 16; t < 20; ++t) save(S_FV_HI + t - 16, fv[t]);
+        }
     }
     float bias[64];
     bf16x8 hb[8];                                 // the current activations as bf16 B operands (k-step s = values 8s .. 8s+7 of the lane)
@@ -1034,7 +1038,7 @@ extern "C" int mvsnerf_mlp_fwd_bf16_train(const void* packed_bf16, const float* 
                                           int64_t N, int S, float* raw, float* saved, void* stream)
 {
     if (!packed_bf16 || !packed_f32 || !ndc || !feat || !dirs || !raw || !saved || N < 0 || S < 1 || feat_stride < F || ndc_stride < 3 || dirs_stride < 3) return MVSNERF_EINVAL;
-    if (F < 2 || F > 32 || (F & 1)) return MVSNERF_EUNSUPPORTED;
+    if (F < 2 || F > MAX_F || (F & 1)) return MVSNERF_EUNSUPPORTED;
     if (!mvs_aligned16(packed_bf16) || !mvs_aligned16(raw) || !mvs_aligned16(saved)) return MVSNERF_EALIGN;
     const int64_t P = N * S;
     if (P == 0) return MVSNERF_OK;

@@ -43,7 +43,8 @@ __global__ __launch_bounds__(256) void mlp_pack_bwd_kernel(PackBwdArgs a, float*
     pack_t_segment(packed + L.l3, a.w[3], WIDTH, 0, WIDTH, ACT_STEPS, 4, tid, nt);
     pack_t_segment(packed + L.l2, a.w[2], WIDTH, 0, WIDTH, ACT_STEPS, 4, tid, nt);
     pack_t_segment(packed + L.l1, a.w[1], WIDTH, 0, WIDTH, ACT_STEPS, 4, tid, nt);
-    pack_t_segment(packed + L.bias, a.w[6], a.F, 0, a.F, ACT_STEPS, 1, tid, nt);            // pts_bias^T (F <= 32 columns)
+    pack_t_segment(packed + L.bias, a.w[6], a.F, 0, a.F, ACT_STEPS, 1, tid, nt);            // pts_bias^T, feature columns [0, 32)
+    pack_t_segment(packed + L.bias + seg_floats(ACT_STEPS, 1), a.w[6], a.F, 32, a.F - 32, ACT_STEPS, 1, tid, nt);   // columns [32, F); zeros for F <= 32
 }
 
 extern "C" size_t mvsnerf_mlp_packed_bwd_floats(void) { return layout_bwd().total; }
@@ -51,7 +52,7 @@ extern "C" size_t mvsnerf_mlp_packed_bwd_floats(void) { return layout_bwd().tota
 extern "C" int mvsnerf_mlp_pack_bwd(const float* const w[11], int F, float* packed_bwd, void* stream)
 {
     if (!w || !packed_bwd) return MVSNERF_EINVAL;
-    if (F < 2 || F > 32 || (F & 1)) return MVSNERF_EUNSUPPORTED;
+    if (F < 2 || F > MAX_F || (F & 1)) return MVSNERF_EUNSUPPORTED;
     PackBwdArgs a;
     for (int i = 0; i < 11; ++i) { if (!w[i]) return MVSNERF_EINVAL; a.w[i] = w[i]; }
     a.F = F;
@@ -76,7 +77,7 @@ __host__ __device__ inline LayoutBwdB layout_bwd_b()
     L.l3 = o;    o += segb(8, 4);
     L.l2 = o;    o += segb(8, 4);
     L.l1 = o;    o += segb(8, 4);
-    L.bias = o;  o += segb(8, 1);
+    L.bias = o;  o += 2 * segb(8, 1);       // feature columns [0, 32), then [32, 64) (zeros for F <= 32)
     L.total = o;
     return L;
 }
@@ -106,6 +107,7 @@ __global__ __launch_bounds__(256) void mlp_pack_bwd_bf16_kernel(PackBwdArgs a, _
     pack_tb_segment(packed + L.l2, a.w[2], WIDTH, 0, WIDTH, 8, 4, tid, nt);
     pack_tb_segment(packed + L.l1, a.w[1], WIDTH, 0, WIDTH, 8, 4, tid, nt);
     pack_tb_segment(packed + L.bias, a.w[6], a.F, 0, a.F, 8, 1, tid, nt);
+    pack_tb_segment(packed + L.bias + segb(8, 1), a.w[6], a.F, 32, a.F - 32, 8, 1, tid, nt);
 }
 
 extern "C" size_t mvsnerf_mlp_packed_bwd_bf16_elems(void) { return layout_bwd_b().total; }
@@ -113,7 +115,7 @@ extern "C" size_t mvsnerf_mlp_packed_bwd_bf16_elems(void) { return layout_bwd_b(
 extern "C" int mvsnerf_mlp_pack_bwd_bf16(const float* const w[11], int F, void* packed_bwd_bf16, void* stream)
 {
     if (!w || !packed_bwd_bf16) return MVSNERF_EINVAL;
-    if (F < 2 || F > 32 || (F & 1)) return MVSNERF_EUNSUPPORTED;
+    if (F < 2 || F > MAX_F || (F & 1)) return MVSNERF_EUNSUPPORTED;
     PackBwdArgs a;
     for (int i = 0; i < 11; ++i) { if (!w[i]) return MVSNERF_EINVAL; a.w[i] = w[i]; }
     a.F = F;
@@ -219,6 +221,7 @@ __global__ __launch_bounds__(256, 1) void mlp_dgrad_kernel(
     const int64_t tile = (int64_t)blockIdx.x * 4 + wave;
     const int64_t p_raw = tile * 32 + (lane & 31);
     const bool live = p_raw < P;
+    const bool wide = F > 32;                  // kernel argument: uniform.  pts_bias^T then has a second block of 32 feature columns
     // BF: both slot buffers hold bf16 elements (what mvsnerf_mlp_fwd_bf16_train stored; what the bf16 weight-gradient GEMMs read)
     using slot_t = typename SlotType<BF>::type;
     const slot_t* sv = reinterpret_cast<const slot_t*>(saved) + tile * (SLOTS_SAVED * 64) + lane;
@@ -308,7 +311,7 @@ __global__ __launch_bounds__(256, 1) void mlp_dgrad_kernel(
         float* nxt = (layer & 1) ? buf1 : buf0;
         wsync();                                                                       // this layer's segment landed; the other buffer is free
         if (layer >= 2) wdma(nxt, packed_bwd + L.l5 + (size_t)(6 - layer) * L.n_act, L.n_act, wave, lane);
-        else if (layer == 1) wdma(nxt, packed_bwd + L.bias, L.n_bias, wave, lane);
+        else if (layer == 1) wdma(nxt, packed_bwd + L.bias, wide ? 2 * L.n_bias : L.n_bias, wave, lane);
 #pragma unroll
         for (int q = 0; q < 64; ++q) gs[(G_GP + layer * 64 + q) * 64] = (slot_t)gh[q];
         if (layer == 0) break;
@@ -337,6 +340,22 @@ __global__ __launch_bounds__(256, 1) void mlp_dgrad_kernel(
             for (int q = 0; q < 4; ++q)
                 if (8 * q + 4 * half < n_feat_out)
                     *reinterpret_cast<f32x4*>(d_feat + p_raw * n_feat_out + 8 * q + 4 * half) =
+                        f32x4{acc[0][4 * q], acc[0][4 * q + 1], acc[0][4 * q + 2], acc[0][4 * q + 3]};
+        }
+    }
+    // F > 32 with more than 32 columns wanted (a 36- / 40-channel colour volume): the same product on the second block of pts_bias^T, which
+    // sits behind the first in buf1, gives feature columns 32 + 8q + 4*half + (0..3).  Both conditions are kernel arguments: a uniform branch
+    // that the F <= 32 stream only tests.
+    if (wide && n_feat_out > 32) {
+        f32x16 acc[1];
+        zero_acc<1>(acc);
+        if (BF) gemm_tb<8, 1>(buf1 + L.n_bias, acc, lane, gbm);
+        else gemm_t<16, 1>(buf1 + L.n_bias, acc, lane, [&](int t) { return gbm[t]; });
+        if (live) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                if (32 + 8 * q + 4 * half < n_feat_out)
+                    *reinterpret_cast<f32x4*>(d_feat + p_raw * n_feat_out + 32 + 8 * q + 4 * half) =
                         f32x4{acc[0][4 * q], acc[0][4 * q + 1], acc[0][4 * q + 2], acc[0][4 * q + 3]};
         }
     }
@@ -502,8 +521,9 @@ static int launch_wgrad(int ra_blocks, int nbb, const WgradJobs& w, int n_jobs, 
 }
 
 // ten weight-gradient GEMMs, each leaving `grid` <= 256 partial results of RA * (RB + 1) floats, reduced together at the end:
-// sum of RA * (RB + 1) = 128*65 + 4*128*129 + 128*193 + 128*33 + 128*129 + 64*161 + 32*193
-constexpr size_t WG_NOUT_SUM = 128 * 65 + 4 * 128 * 129 + 128 * 193 + 128 * 33 + 128 * 129 + 64 * 161 + 32 * 193;
+// sum of RA * (RB + 1) = 128*65 + 4*128*129 + 128*193 + 128*65 + 128*129 + 64*161 + 32*193
+// (pts_bias, the fourth term: 128*33 for F <= 32, 128*65 above - the workspace is sized for the larger one)
+constexpr size_t WG_NOUT_SUM = 128 * 65 + 4 * 128 * 129 + 128 * 193 + 128 * 65 + 128 * 129 + 64 * 161 + 32 * 193;
 extern "C" size_t mvsnerf_mlp_bwd_workspace_floats(void) { return (size_t)(256 + MVS_RED_SLICES + 1) * WG_NOUT_SUM + 1024; }
 
 // maps: device int array of 8 consecutive tables (see mvsnerf_amd/ops.py:_mlp_bwd_maps):
@@ -511,6 +531,8 @@ extern "C" size_t mvsnerf_mlp_bwd_workspace_floats(void) { return (size_t)(256 +
 //   [2] pe (64): r=2t+h -> embedding column or -1          [3] pe_l5 (64): same (columns 0..62 of the 191-wide layer 5)
 //   [4] feat (32): r=2t+h -> feature column or -1          [5] h_l5 (128): 63 + n(q,h)
 //   [6] dir (32): r -> 128 + {0,1,2} or -1                 [7] g4_rgb (32): 0,1,2 -> rgb row, else -1   [8] g4_alpha (32): 3 -> 0
+//   then four concatenated column tables (192, 160, 192, 192 entries, see below) and, from entry 1312, feat_wide (64), read when F > 32 only:
+//   r < 32 as [4]; r = 32 + 2s + h -> h F/2 + 16 + (s - 2) for slots 2 <= s < 6 of the S_DR block with 16 + (s - 2) < F/2, else -1
 static int mlp_bwd_impl(bool bf, const float* packed_fwd, const float* packed_bwd, int F,
                         const float* raw, const float* d_raw, const float* saved, int64_t N, int S,
                         float* gslots, float* d_feat, int n_feat_out, float* const gw[11], float* const gb[11],
@@ -544,7 +566,7 @@ static int mlp_bwd_impl(bool bf, const float* packed_fwd, const float* packed_bw
 {
     if (!packed_fwd || !packed_bwd || !raw || !d_raw || !saved || !gslots || !d_feat || !gw || !gb || !maps || !workspace) return MVSNERF_EINVAL;
     if (n_feat_out < 4 || n_feat_out > F || (n_feat_out & 3) || !mvs_aligned16(d_feat)) return MVSNERF_EINVAL;
-    if (F < 2 || F > 32 || (F & 1) || N < 0 || S < 1) return MVSNERF_EUNSUPPORTED;
+    if (F < 2 || F > MAX_F || (F & 1) || N < 0 || S < 1) return MVSNERF_EUNSUPPORTED;
     const int64_t P = N * S;
     if (P == 0) return MVSNERF_OK;
     hipStream_t st = (hipStream_t)stream;
@@ -613,9 +635,15 @@ static int mlp_bwd_impl(bool bf, const float* packed_fwd, const float* packed_bw
     // pts_linears.5 on cat([pts, h4]): B = [E | H4]; the 192-entry column table [pe (64) | 63 + act (128)] follows the 9 tables
     if ((rc = gemm(G_GP + 5 * 64, 4, S_E, 2, S_H + 4 * 64, 6, 128, 192))) return rc;
     scatter(128, 192, M_ACT128, maps + 576, gw[5], WIDTH + PE_DIM, gb[5]);
-    // pts_bias: dWb = GBM x Fv^T
-    if ((rc = gemm(G_GBM, 4, S_FV, 1, 0, 1, 128, 32))) return rc;
-    scatter(128, 32, M_ACT128, M_FEAT, gw[6], F, gb[6]);
+    // pts_bias: dWb = GBM x Fv^T.  F > 32: B = [S_FV | the S_DR block], whose slots 2..5 are feature operands 16..19 (S_FV_HI); the 64-entry
+    // column table behind the others sends rows 2t + h of the first block and 4 + 2(t - 16) + h of the second to h F/2 + t and drops the rest
+    if (F <= 32) {
+        if ((rc = gemm(G_GBM, 4, S_FV, 1, 0, 1, 128, 32))) return rc;
+        scatter(128, 32, M_ACT128, M_FEAT, gw[6], F, gb[6]);
+    } else {
+        if ((rc = gemm(G_GBM, 4, S_FV, 1, S_DR, 2, 128, 64))) return rc;
+        scatter(128, 64, M_ACT128, maps + 1312, gw[6], F, gb[6]);
+    }
     // feature_linear: dWf = GF x H5^T
     if ((rc = gemm(G_GF, 4, S_H + 5 * 64, 4, 0, 4, 128, 128))) return rc;
     scatter(128, 128, M_ACT128, M_ACT128, gw[7], WIDTH, gb[7]);

@@ -105,12 +105,14 @@ __host__ __device__ inline size_t fold_total(int F) { return fold_bias_off(F) + 
 // and 1) of 32 points each: address = ((tile * SLOTS + slot) * 64 + lane).  A row is the 32-point vector of one
 // feature, which is exactly the 128-byte operand row the weight-gradient MFMAs contract over.
 constexpr int S_E = 0;            // 32 slots: positional-encoding operands, slot t = (kmap PE column (t,0), (t,1))
-constexpr int S_FV = 32;          // 16 slots: feature operands, slot t = feat columns (t, F/2+t)           (F <= 32)
+constexpr int S_FV = 32;          // 16 slots: feature operands, slot t = feat columns (t, F/2+t), t < 16; F > 32: slots 16..19 at S_FV_HI
 constexpr int S_BM = 48;          // 64 slots: pts_bias output b, slot q = features n(q,0), n(q,1)
 constexpr int S_H = 112;          // 6 x 64 slots: h_0..h_5 (post-ReLU)
 constexpr int S_FE = 496;         // 64 slots: feature_linear output
 constexpr int S_HV = 560;         // 32 slots: relu(views_linears[0])
-constexpr int S_DR = 592;         // 16 slots: slot 0 = (d0,d1), slot 1 = (d2,0); rest unused
+constexpr int S_DR = 592;         // 16 slots: slot 0 = (d0,d1), slot 1 = (d2,0); slots 2..5 = S_FV_HI; rest unused
+constexpr int S_FV_HI = S_DR + 2; // 4 slots, written when F > 32 only: feature operands 16..19 (zero from F/2 on).  They live in the direction block so that
+                                  // every other offset and SLOTS_SAVED stay what they were; the weight-gradient GEMMs that read the S_DR block drop these rows
 constexpr int SLOTS_SAVED = 608;
 // written by the dgrad kernel
 constexpr int G_GP = 0;           // 6 x 64 slots: grad wrt the output of pts_linears[i] (multiplicative network: already x bias; additive, V_ADD: the masked gradient itself)
@@ -121,8 +123,9 @@ constexpr int G_G4 = 544;         // 16 slots: slot 0 = (d rgb_r pre-sigmoid, d 
 constexpr int SLOTS_GRAD = 560;
 
 // Transposed (dgrad) weight segments: A operand = W^T, i.e. fragment(t, kb, lane(i,h)) = W[n(t,h)][col_off + kb*32 + i]
+// pts_bias^T: two consecutive 64 x 1 segments, feature columns [0, 32) at `bias` and [32, 64) behind it (all zero for F <= 32, never read then)
 struct LayoutBwd {
-    size_t views, feat, l5, l4, l3, l2, l1, bias, total;   // views: 32 steps x 4 blocks; feat, l1..l5: 64 x 4; bias: 64 x 1
+    size_t views, feat, l5, l4, l3, l2, l1, bias, total;   // views: 32 steps x 4 blocks; feat, l1..l5: 64 x 4; bias: 2 x (64 x 1)
 };
 __host__ __device__ inline LayoutBwd layout_bwd()
 {
@@ -135,7 +138,7 @@ __host__ __device__ inline LayoutBwd layout_bwd()
     L.l3 = o;    o += seg_floats(ACT_STEPS, 4);
     L.l2 = o;    o += seg_floats(ACT_STEPS, 4);
     L.l1 = o;    o += seg_floats(ACT_STEPS, 4);
-    L.bias = o;  o += seg_floats(ACT_STEPS, 1);
+    L.bias = o;  o += 2 * seg_floats(ACT_STEPS, 1);
     L.total = o;
     return L;
 }

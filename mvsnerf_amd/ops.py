@@ -685,7 +685,7 @@ def _mlp_bwd_maps(F, device):
     if key in _maps_cache:
         return _maps_cache[key]
     import numpy as np
-    t = -np.ones(1312, dtype=np.int32)
+    t = -np.ones(1376, dtype=np.int32)
     act128 = np.array([_act_n(r >> 1, r & 1) for r in range(128)], dtype=np.int32)
     act64 = act128[:64].copy()
     pe = np.array([(r & 1) if (r >> 1) == 0 else ((2 if (r & 1) == 0 else -1) if (r >> 1) == 1 else 3 + ((r >> 1) - 2) + 30 * (r & 1))
@@ -699,6 +699,9 @@ def _mlp_bwd_maps(F, device):
     t[896:899] = [128, 129, 130]
     t[928:992] = act64
     t[1184:1312] = act128
+    # F > 32: the pts_bias weight gradient contracts over [S_FV (16 slots) | the S_DR block, whose slots 2..5 hold feature operands 16..19]
+    t[1312:1344] = feat
+    t[1344:1376] = [((r & 1) * (F // 2) + 14 + (r >> 1)) if 2 <= (r >> 1) < 6 and 14 + (r >> 1) < F // 2 else -1 for r in range(32)]
     out = torch.from_numpy(t).to(device)
     _maps_cache[key] = out
     return out
