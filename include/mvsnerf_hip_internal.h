@@ -287,6 +287,28 @@ typedef struct {
 } mvsnerf_render_rays_args;
 size_t mvsnerf_render_rays_workspace_floats(int batch_rays, int S, int n_importance, int F);
 int mvsnerf_render_rays_fwd(const mvsnerf_render_rays_args* a, void* stream);
+/* ---- frame metrics (renderer.ipynb cells 8 and 16; mvsnerf_amd/evaluate.py is the host statement of the same protocol) ----
+ * The evaluation record of K finished frames in two launches (csrc/metrics.hip), no atomics, bit-reproducible and independent of K.
+ *   pred, gt: [K][H][W][3] fp32 (HWC, what render_view / render_rays return); depth_pred, depth_gt: [K][H][W] or both NULL.
+ *   out: [K][MVSNERF_METRICS_ROW] doubles, every entry written:
+ *      0 sum of squared error over all pixels and channels      1 pixel count H*W
+ *      2 the same over the centre crop (H/10 rows, W/10 columns off every side: psnr_center_crop)      3 its pixel count (0 when H/10 or W/10 is 0)
+ *      4 the same over depth_gt != 0 (psnr_masked)              5 its pixel count          (both 0 without depth)
+ *      6..8 sum of the SSIM map of channel 0..2 over the valid region (window wholly inside the image)    9 its pixel count (H-win+1)(W-win+1)
+ *      10 sum of |depth_pred - depth_gt * gt_scale| over depth_gt > 0     11..13 how many of those errors are below thresholds[0..2]     14 pixel count of depth_gt > 0
+ *      A mean squared error is entry / (3 * count); counts are whole numbers.
+ *   SSIM: structural_similarity of skimage 0.19 with multichannel defaults - uniform win_size x win_size window (odd, 3..11), sample covariance,
+ *      C1 = (K1 data_range)^2, C2 = (K2 data_range)^2.  Window sums are fp32 and centred (a constant image has variance exactly 0); squared errors are
+ *      fp32 per pixel and channel; depth errors and every sum across pixels are double.
+ *   thresholds: HOST array of three doubles.  workspace: mvsnerf_frame_metrics_workspace_bytes(K, H, W, win_size) bytes (one row per frame and tile;
+ *      0 for arguments the entry refuses), 8-byte aligned like out; the images need 4-byte alignment only (a frame of a batch is a valid input).
+ *   Returns MVSNERF_EINVAL for a NULL pred / gt / out / workspace / thresholds, one depth pointer without the other, K < 1, H or W < 1, an even
+ *   win_size or one outside 3..11; MVSNERF_EUNSUPPORTED for min(H, W) < win_size; MVSNERF_EALIGN; all before the first launch. */
+#define MVSNERF_METRICS_ROW 15
+size_t mvsnerf_frame_metrics_workspace_bytes(int K, int H, int W, int win_size);
+int mvsnerf_frame_metrics_fwd(const float* pred, const float* gt, const float* depth_pred, const float* depth_gt, int K, int H, int W,
+                              int win_size, double data_range, double K1, double K2, double gt_scale, const double* thresholds,
+                              double* out, void* workspace, void* stream);
 
 #ifdef __cplusplus
 }

@@ -254,6 +254,8 @@ SIGNATURES = {
     "mvsnerf_raymarch_colorvol_fwd_batched": (_c_i, [ctypes.POINTER(RaymarchArgs), _c_i, _c_i, _c_fp]),
     "mvsnerf_render_rays_workspace_floats": (ctypes.c_size_t, [_c_i] * 4),
     "mvsnerf_render_rays_fwd": (_c_i, [ctypes.POINTER(RenderRaysArgs), _c_fp]),
+    "mvsnerf_frame_metrics_workspace_bytes": (ctypes.c_size_t, [_c_i] * 4),
+    "mvsnerf_frame_metrics_fwd": (_c_i, [_c_fp] * 4 + [_c_i] * 4 + [ctypes.c_double] * 4 + [ctypes.POINTER(ctypes.c_double), _c_fp, _c_fp, _c_fp]),
 }
 
 _lib = None

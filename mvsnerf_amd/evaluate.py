@@ -89,3 +89,38 @@ def ssim(rgb, img, win_size=7, data_range=None, K1=0.01, K2=0.03):
         S = ((2 * ux * uy + C1) * (2 * vxy + C2)) / ((ux * ux + uy * uy + C1) * (vx + vy + C2))
         vals.append(S[pad:-pad, pad:-pad].astype(np.float64).mean())
     return float(np.mean(vals))
+
+
+# ---- the same protocol on the GPU (csrc/metrics.hip through ops.frame_metrics): frames stay on the device, nothing synchronises the host
+
+def _psnr_of_sums(sse, n):
+    """mse2psnr's formula on a sum of squared errors over n pixels of 3 channels, per frame, in float64; n == 0 gives NaN."""
+    return -10.0 * torch.log(sse / (3.0 * n)) / float(np.log(10.0))
+
+
+def frame_metrics(rgb, img, depth_pred=None, depth_gt=None, win_size=7, data_range=None, K1=0.01, K2=0.03, thresholds=(0.01, 0.05, 0.1),
+                  gt_scale=1.0 / 200.0):
+    """psnr, psnr_center_crop, psnr_masked, ssim, abs_err and acc_l_<t> of K frames in one library call.  rgb, img: (H,W,3) or (K,H,W,3) fp32
+    tensors on the GPU, depth_pred / depth_gt (H,W) or (K,H,W) or both None.  Returns a dict of (K,) float64 tensors on the GPU and does not
+    synchronise the host: collect the dicts of a validation loop and copy once.  data_range=None is 2.0, as in `ssim`.  A key whose pixel
+    count is zero (psnr_masked / abs_err / acc_l_* without depth or under an all-zero depth_gt) is NaN for that frame."""
+    from . import ops
+    if torch.is_tensor(rgb) and rgb.dim() in (3, 4) and (rgb.shape[-3] // 10 == 0 or rgb.shape[-2] // 10 == 0):
+        raise ValueError("psnr_center_crop: the reference's [H_crop:-H_crop] slicing is empty for images smaller than 10 pixels")
+    row = ops.frame_metrics(rgb, img, depth_pred, depth_gt, win_size=win_size, data_range=2.0 if data_range is None else float(data_range),
+                            K1=K1, K2=K2, gt_scale=gt_scale, thresholds=thresholds)
+    out = {"psnr": _psnr_of_sums(row[:, ops.M_SSE], row[:, ops.M_N]),
+           "psnr_center_crop": _psnr_of_sums(row[:, ops.M_SSE_CROP], row[:, ops.M_N_CROP]),
+           "psnr_masked": _psnr_of_sums(row[:, ops.M_SSE_MASK], row[:, ops.M_N_MASK]),
+           "ssim": row[:, ops.M_SSIM0:ops.M_SSIM2 + 1].sum(1) / (3.0 * row[:, ops.M_N_SSIM]),
+           "abs_err": row[:, ops.M_ABS_ERR] / row[:, ops.M_N_DEPTH]}
+    for i, t in enumerate(thresholds):
+        out[f"acc_l_{t}"] = row[:, ops.M_ACC0 + i] / row[:, ops.M_N_DEPTH]
+    return out
+
+
+def ssim_hip(rgb, img, win_size=7, data_range=None, K1=0.01, K2=0.03):
+    """`ssim` of K frames on the GPU: (H,W,3) or (K,H,W,3) fp32 tensors -> (K,) float64 tensor on the GPU, no host synchronisation."""
+    from . import ops
+    row = ops.frame_metrics(rgb, img, win_size=win_size, data_range=2.0 if data_range is None else float(data_range), K1=K1, K2=K2)
+    return row[:, ops.M_SSIM0:ops.M_SSIM2 + 1].sum(1) / (3.0 * row[:, ops.M_N_SSIM])

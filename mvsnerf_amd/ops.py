@@ -886,3 +886,48 @@ def raymarch_train(volume, imgs, w2cs, intrinsics, net, rays_pts, rays_ndc, z_va
     rgb, feat, weights, depth, alpha, raw = RayMarchFunction.apply(
         volume, imgs, w2cs, intrinsics, rays_pts, rays_ndc, z_vals, rays_dir, white_bkgd, packed, dp_samples, *params)
     return {"rgb_map": rgb, "input_feat": feat, "weights": weights, "depth": depth, "alpha": alpha, "raw": raw}
+
+
+# ------------------------------------------------------------------ frame metrics
+METRICS_ROW = 15                 # MVSNERF_METRICS_ROW of include/mvsnerf_hip_internal.h; the entries of a row:
+(M_SSE, M_N, M_SSE_CROP, M_N_CROP, M_SSE_MASK, M_N_MASK, M_SSIM0, M_SSIM1, M_SSIM2, M_N_SSIM, M_ABS_ERR, M_ACC0, M_ACC1, M_ACC2, M_N_DEPTH) = range(METRICS_ROW)
+
+
+def frame_metrics_workspace_bytes(K, H, W, win_size=7):
+    return int(_lib.lib().mvsnerf_frame_metrics_workspace_bytes(K, H, W, win_size))
+
+
+def frame_metrics(pred, gt, depth_pred=None, depth_gt=None, win_size=7, data_range=2.0, K1=0.01, K2=0.03, gt_scale=1.0 / 200.0,
+                  thresholds=(0.01, 0.05, 0.1), out=None, workspace=None):
+    """The evaluation record of K frames (mvsnerf_frame_metrics_fwd): pred, gt (K,H,W,3) or (H,W,3) on the GPU (fp32; contiguous, or copied to
+    that on the device), depth_pred / depth_gt (K,H,W) or (H,W) or both None -> (K, METRICS_ROW) float64 on the GPU: sums and counts, see the M_* indices (a mean squared error is
+    row[M_SSE] / (3 row[M_N])).  Two launches on the current stream, no host synchronisation.  out / workspace: caller-owned buffers of a loop
+    ((K, METRICS_ROW) float64; at least frame_metrics_workspace_bytes(K, H, W, win_size) bytes of float64)."""
+    _need_no_grad(pred, gt, depth_pred, depth_gt, op="frame_metrics")
+    if not (torch.is_tensor(pred) and torch.is_tensor(gt)) or pred.shape != gt.shape or pred.dim() not in (3, 4) or pred.shape[-1] != 3:
+        raise RuntimeError(f"frame_metrics: pred and gt must both be (K,H,W,3) or (H,W,3), got {tuple(getattr(pred, 'shape', ()))} and {tuple(getattr(gt, 'shape', ()))}")
+    K = 1 if pred.dim() == 3 else int(pred.shape[0])
+    H, W = int(pred.shape[-3]), int(pred.shape[-2])
+    if (depth_pred is None) != (depth_gt is None):
+        raise RuntimeError("frame_metrics: depth_pred and depth_gt come together")
+    if depth_gt is not None and not (tuple(depth_pred.shape) == tuple(depth_gt.shape) == tuple(pred.shape[:-1])):
+        raise RuntimeError(f"frame_metrics: depth_pred and depth_gt must be {tuple(pred.shape[:-1])}, got {tuple(depth_pred.shape)} and {tuple(depth_gt.shape)}")
+    if len(thresholds) != 3:
+        raise RuntimeError("frame_metrics: three depth thresholds")
+    keep = _Keep()        # render_view's frame is a strided view of its (N,4) rgb + depth rows: such inputs are made contiguous on the device first
+    ptrs = [keep(pred, "frame_metrics: pred"), keep(gt, "frame_metrics: gt")]
+    ptrs += [0, 0] if depth_gt is None else [keep(depth_pred, "frame_metrics: depth_pred"), keep(depth_gt, "frame_metrics: depth_gt")]
+    need = frame_metrics_workspace_bytes(K, H, W, win_size)
+    if out is None:
+        out = torch.empty((K, METRICS_ROW), device=pred.device, dtype=torch.float64)
+    elif not (out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and tuple(out.shape) == (K, METRICS_ROW) and out.device == pred.device):
+        raise RuntimeError(f"frame_metrics: out must be a contiguous ({K},{METRICS_ROW}) float64 tensor on {pred.device}")
+    if workspace is None:
+        workspace = torch.empty((max(need, 8) // 8,), device=pred.device, dtype=torch.float64)
+    elif not (workspace.is_cuda and workspace.dtype == torch.float64 and workspace.is_contiguous() and workspace.numel() * 8 >= need
+              and workspace.device == pred.device):
+        raise RuntimeError(f"frame_metrics: workspace must be a contiguous float64 tensor of at least {need} bytes on {pred.device}")
+    thr = (ctypes.c_double * 3)(*[float(t) for t in thresholds])
+    check(_lib.lib().mvsnerf_frame_metrics_fwd(*ptrs, K, H, W, int(win_size), float(data_range), float(K1), float(K2), float(gt_scale), thr,
+                                               out.data_ptr(), workspace.data_ptr(), stream_ptr()), "frame_metrics_fwd")
+    return out
