@@ -530,6 +530,7 @@ extern "C" int mvsnerf_posenc_fwd(const float* x, int64_t P, int d, int L, float
 __global__ __launch_bounds__(256) void volume_sample_c8_bwd_kernel(
     int D, int H, int W, const float* __restrict__ ndc, int64_t P, const float* __restrict__ g, int g_stride, float* __restrict__ gvol)
 {
+#pragma clang fp contract(off)      // the forward lookups' weights, bit for bit: contracted, (ix - fx) becomes fma(t, size - 1, -fx) and skips the rounding of ix
     const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int q = (int)(tid & 3);
     const int xc = q >> 1, ch = (q & 1) * 4;
@@ -554,7 +555,9 @@ __global__ __launch_bounds__(256) void volume_sample_c8_bwd_kernel(
         for (int yc = 0; yc < 2; ++yc) c[zc][yc] = gv * (wx * wy[yc] * wz[zc]);
     // neighbours along the ray: lane - 4 (previous sample, same (xc, channel half)) and lane + 4, inside the 16-lane row
     constexpr int NONE = -(1 << 30);
-    const int my_cell = x_ok ? (fyi * 4096 + cxi) : NONE + 1;     // W, H < 4096 (the volumes are a few hundred voxels wide)
+    // one key per (fy, cx) cell: cxi is clamped to [-4, W + 4], so the key is unique while W + 4 <= 4095, and fyi <= H + 4 keeps it inside an int
+    // for H < 2^18 - the launcher sends wider or taller volumes to volume_sample_bwd_kernel
+    const int my_cell = x_ok ? (fyi * 4096 + cxi) : NONE + 1;
     const int prev_cell = __builtin_amdgcn_update_dpp(NONE, my_cell, 0x114, 0xf, 0xf, false);      // row_shr:4
     const int prev_fz = __builtin_amdgcn_update_dpp(NONE, fzi, 0x114, 0xf, 0xf, false);
     const int next_cell = __builtin_amdgcn_update_dpp(NONE, my_cell, 0x104, 0xf, 0xf, false);      // row_shl:4
@@ -587,6 +590,7 @@ __global__ __launch_bounds__(256) void volume_sample_c8_bwd_kernel(
 __global__ __launch_bounds__(256) void volume_sample_bwd_kernel(
     int D, int H, int W, int C, const float* __restrict__ ndc, int64_t P, const float* __restrict__ g, int g_stride, float* __restrict__ gvol)
 {
+#pragma clang fp contract(off)      // the forward lookups' weights, bit for bit: contracted, (ix - fx) becomes fma(t, size - 1, -fx) and skips the rounding of ix
     const int Q = C >> 2;
     const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t p = tid / Q;
@@ -615,7 +619,8 @@ extern "C" int mvsnerf_volume_sample_bwd(int D, int H, int W, int C, const float
     if (C < 4 || (C & 3)) return MVSNERF_EUNSUPPORTED;
     if ((g_stride & 3) || !mvs_aligned16(g)) return MVSNERF_EALIGN;
     if (P == 0) return MVSNERF_OK;
-    if (C == 8) volume_sample_c8_bwd_kernel<<<mvs_cdiv(P * 4, 256), 256, 0, (hipStream_t)stream>>>(D, H, W, ndc, P, g, g_stride, gvol);
+    if (C == 8 && W <= 4091 && H < (1 << 18))     // the hand-off kernel's cell key (fy * 4096 + cx) is unique only inside these sizes
+        volume_sample_c8_bwd_kernel<<<mvs_cdiv(P * 4, 256), 256, 0, (hipStream_t)stream>>>(D, H, W, ndc, P, g, g_stride, gvol);
     else volume_sample_bwd_kernel<<<mvs_cdiv(P * (C >> 2), 256), 256, 0, (hipStream_t)stream>>>(D, H, W, C, ndc, P, g, g_stride, gvol);
     MVS_LAUNCH_CHECK();
     return MVSNERF_OK;
@@ -649,6 +654,7 @@ __global__ __launch_bounds__(256) void volume_sample_bwd_det_scatter_kernel(
     int D, int H, int W, int C, const float* __restrict__ ndc, int64_t P, const float* __restrict__ g, int g_stride,
     const unsigned* __restrict__ max_bits, unsigned long long* __restrict__ acc)
 {
+#pragma clang fp contract(off)      // the forward lookups' weights, bit for bit: contracted, (ix - fx) becomes fma(t, size - 1, -fx) and skips the rounding of ix
     const unsigned mb = *max_bits;
     if (mb == 0 || mb >= 0x7f800000u) return;                       // all-zero gradient; a non-finite one is left to the float path's semantics (finish reports nothing)
     const double scale = ldexp(1.0, 40 - det_exponent(mb));

@@ -474,7 +474,10 @@ def _mlp_fields(packed_bf16, packed_split, guard):
 
 # ------------------------------------------------------------------ compositing
 def composite(raw, z_vals, white_bkgd=False):
-    """raw (N,S,4), z (N,S) -> rgb_map, disp, acc, weights, depth, alpha  (renderer.py:65-92)."""
+    """raw (N,S,4), z (N,S) -> rgb_map, disp, acc, weights, depth, alpha  (renderer.py:65-92).
+    One deviation from the reference: a ray whose densities are all zero has depth / acc = 0/0; renderer.py:87 (torch.max) returns disp = NaN there, the kernels'
+    fmaxf(1e-10f, NaN) is 1e-10 and they return the finite disp = 1e10 (rgb = 0, or 1 with white_bkgd; acc = depth = weights = alpha = 0 exactly).  The compositing
+    epilogue of ops.raymarch does the same."""
     _need_no_grad(raw, z_vals, op="composite")
     N, S = z_vals.shape
     dev = raw.device
