@@ -51,3 +51,14 @@ __device__ __forceinline__ void lds_dma_c(void* __restrict__ dst, const void* __
     for (int k = 0; k < (PIECES + WAVES - 1) / WAVES; ++k)
         if ((k + 1) * WAVES <= PIECES || wave + k * WAVES < PIECES) lds_dma_1k(s + k * WAVES * 1024, l + k * WAVES * 1024, lb);
 }
+
+// piece k of this wave's share of the same transfer, on its own: lds_dma_piece<W, P>(.., k) for k = 0 .. lds_dma_steps(W, P) - 1 moves what lds_dma_c<W, P> moves,
+// for a caller that spreads the pieces over its instruction stream instead of issuing them back to back
+constexpr int lds_dma_steps(int waves, int pieces) { return (pieces + waves - 1) / waves; }
+template <int WAVES, int PIECES>
+__device__ __forceinline__ void lds_dma_piece(void* __restrict__ dst, const void* __restrict__ src, int wave, int lane, int k)
+{
+    const char* s = reinterpret_cast<const char*>(src) + wave * 1024;
+    const unsigned l = lds_byte_addr(dst) + wave * 1024;
+    if ((k + 1) * WAVES <= PIECES || wave + k * WAVES < PIECES) lds_dma_1k(s + k * WAVES * 1024, l + k * WAVES * 1024, lane * 16);
+}

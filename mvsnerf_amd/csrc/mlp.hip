@@ -183,20 +183,27 @@ __device__ __forceinline__ void stage_weights(float* __restrict__ wbuf, const fl
 
 // acc[g][b] += W_frag(t, b) * bfn(g, t) for t in [0, 4*STEPS4); G = 32-point groups per wave
 // (one A fragment read from LDS feeds G MFMAs).
-struct NoHook { __device__ __forceinline__ void operator()() const {} };
+struct NoHook {
+    static constexpr int STEPS = 0;
+    __device__ __forceinline__ void operator()(int) const {}
+};
 
-// `after_first_reads` runs once, between the LDS reads of the first fragment group and its MFMAs: the pipelined kernel
-// issues the next slab's DMA there, so that the DMA instructions fill the LDS latency instead of preceding the reads.
+// `under(i)` issues piece i of what the hook spreads under this GEMM, i < HOOK::STEPS: the pipelined kernel's DMA of the next slab (SlabUnder below).
+// A wave issues in order: eight pieces back to back are a stretch of its stream without an MFMA, one piece between two k-steps sits behind the MFMA
+// in flight.  The pieces go behind k-steps 0, 1, 2 of every group of four; k-step 3 keeps none, the compiler requests the next group's A fragments
+// around its MFMAs and a piece there would put the LDS latency behind the piece instead of under the MFMAs (measured, CHANGELOG.md).  Eight pieces
+// are out after k-step 9, nine after k-step 10.  sched_barrier(0) pins each piece between its two k-steps: nothing crosses, the inline asm included
+// (a barrier with a mask lets it through).
 template <int STEPS4, int NBLK, int G, typename BFN, typename HOOK = NoHook>
-__device__ __forceinline__ void gemm_stage(const float* __restrict__ w, f32x16 (&acc)[G][NBLK], int lane, BFN bfn, HOOK after_first_reads = HOOK())
+__device__ __forceinline__ void gemm_stage(const float* __restrict__ w, f32x16 (&acc)[G][NBLK], int lane, BFN bfn, HOOK under = HOOK())
 {
+    static_assert(HOOK::STEPS <= 3 * STEPS4, "the hook's pieces must fit under the GEMM's k-steps");
 #pragma unroll
     for (int t4 = 0; t4 < STEPS4; ++t4) {
         f32x4 a[NBLK];
 #pragma unroll
         for (int b = 0; b < NBLK; ++b)
             a[b] = *reinterpret_cast<const f32x4*>(w + ((t4 * NBLK + b) * 64 + lane) * 4);
-        if (t4 == 0) after_first_reads();
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             float bv[G];
@@ -207,6 +214,11 @@ __device__ __forceinline__ void gemm_stage(const float* __restrict__ w, f32x16 (
 #pragma unroll
                 for (int g = 0; g < G; ++g)
                     acc[g][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[b][j], bv[g], acc[g][b], 0, 0, 0);
+            if (j < 3 && t4 * 3 + j < HOOK::STEPS) {
+                __builtin_amdgcn_sched_barrier(0);
+                under(t4 * 3 + j);
+                __builtin_amdgcn_sched_barrier(0);
+            }
         }
     }
 }
@@ -263,10 +275,10 @@ __device__ __forceinline__ float pe_operand(int t, int half, float px, float py,
 
 // ------------------------------------------------------------------------------------------ pipelined forward
 // Measured on MI355X: 0.237 ms per 1024x128 batch = 139 TFLOP/s = 88 % of the 157.3 TFLOP/s fp32-MFMA peak; PMC:
-// matrix pipes busy 85 % of the kernel's duration.  What the rest is: VALU instructions cost matrix-pipe issue time on this
-// chip whichever wave issues them (scratch/mfma_mix.hip: one v_fma per MFMA takes 12 % off the MFMA rate), ~1 950 of them per
-// 1 976 MFMAs here (folded: ~1 880 per 1 720 - the 64 register moves and one accumulator initialisation of feature_linear go with its
-// 256 MFMAs); launch ramp / tail of a two-round grid.  Negative results kept out of the code: (i) staggering /
+// matrix pipes busy 85 % of the kernel's duration (folded: 1 720 MFMAs per wave, 83-85 % busy).  What the rest is: DESIGN.md section 4, "Where the fp32 tile's
+// idle matrix-pipe time is" - stretches of a wave's own stream without an MFMA that the partner wave of its SIMD is not there to fill (layer boundaries, the
+// start, the lone tail of the two-round grid), not the VALU instruction count: the positional encoding is evaluated once per point and stays in registers across
+// the layer loop.  Negative results kept out of the code: (i) staggering /
 // prioritising the two co-resident workgroups of a CU: no change; (ii) reading A fragments straight from L2 (no LDS stage, no
 // barriers): 114 TFLOP/s; (iii) 64 points per wave at one wave per SIMD: 114 TFLOP/s.
 // Same arithmetic as mlp_fwd_kernel<.., G=1, ..>, different weight logistics: the packed weights are cut into 16 slabs (folded: 14 - feature_linear's two are not
@@ -285,6 +297,15 @@ __device__ __forceinline__ void slab_dma_c(float* __restrict__ dst, const float*
 {
     lds_dma_c<4, N_FLOATS / 256>(dst, src, wave, lane);
 }
+
+// The same slab as slab_dma_c<N_FLOATS>, as a gemm_stage hook: this wave's share goes out piece by piece under the first k-steps of the GEMM that runs
+// meanwhile (8 pieces for half a layer, 9 in waves 0 and 1 for the views segment), the rest of the GEMM - 21 k-steps or more - covers the fetch.
+template <int N_FLOATS>
+struct SlabUnder {
+    static constexpr int STEPS = lds_dma_steps(4, N_FLOATS / 256);
+    float* dst; const float* src; int wave, lane;
+    __device__ __forceinline__ void operator()(int k) const { lds_dma_piece<4, N_FLOATS / 256>(dst, src, wave, lane, k); }
+};
 
 __device__ __forceinline__ void slab_sync()
 {
@@ -490,7 +511,6 @@ __device__ __forceinline__ void mlp_fwd_pipe_tile(
     stamp();                                                                                // [5] bias gemm done
     // ---- slab 1: layer 0
     slab_sync();
-    slab_dma_c<HALF>(buf0, packed + L.l1, wave, lane);                                      // slab 2
     // FUSED: the rays' directions, wanted by the views GEMM, fetched here - where h is not live yet - by LDS-DMA into the 2 KB of buf0 that no
     // slab from here on reaches (none is longer than HALF in buf0; the staged rows were last read in front of the barrier above): they hold no
     // register meanwhile.  Lane (m, half) fetches component `half` of point m's ray, then component 2: [3][32] (+ 32 unused) per wave.
@@ -503,7 +523,7 @@ __device__ __forceinline__ void mlp_fwd_pipe_tile(
     {
         f32x16 acc[G][4];
         init_acc<4, G>(acc, vec + V_L0 + half * 64);
-        gemm_stage<PE_STEPS / 4, 4, G>(buf1, acc, lane, pe);
+        gemm_stage<PE_STEPS / 4, 4, G>(buf1, acc, lane, pe, SlabUnder<HALF>{buf0, packed + L.l1, wave, lane});        // slab 2
         if (add) {
 #pragma unroll
             for (int q = 0; q < 64; q += 2) {
@@ -530,10 +550,10 @@ __device__ __forceinline__ void mlp_fwd_pipe_tile(
         f32x16 acc[G][4];
         slab_sync();
         init_acc<4, G>(acc, vec + V_L0 + 128 * layer + half * 64);
-        gemm_stage<8, 4, G>(buf0, acc, lane, hlo, [&]() { slab_dma_c<HALF>(buf1, wl + HALF, wave, lane); });
+        gemm_stage<8, 4, G>(buf0, acc, lane, hlo, SlabUnder<HALF>{buf1, wl + HALF, wave, lane});
         slab_sync();
         // next slab: first half of the next layer, or the positional-encoding part of layer 5
-        gemm_stage<8, 4, G>(buf1, acc, lane, hhi, [&]() { slab_dma_c<HALF>(buf0, layer < 4 ? wl + 2 * HALF : packed + L.l5a, wave, lane); });
+        gemm_stage<8, 4, G>(buf1, acc, lane, hhi, SlabUnder<HALF>{buf0, layer < 4 ? wl + 2 * HALF : packed + L.l5a, wave, lane});
         if (add) {
 #pragma unroll
             for (int q = 0; q < 64; q += 2) {
@@ -559,16 +579,15 @@ __device__ __forceinline__ void mlp_fwd_pipe_tile(
         f32x16 acc[G][4];
         slab_sync();
         init_acc<4, G>(acc, vec + V_L0 + 128 * 5 + half * 64);
-        gemm_stage<PE_STEPS / 4, 4, G>(buf0, acc, lane, pe, [&]() { slab_dma_c<HALF>(buf1, packed + L.l5b, wave, lane); });
+        gemm_stage<PE_STEPS / 4, 4, G>(buf0, acc, lane, pe, SlabUnder<HALF>{buf1, packed + L.l5b, wave, lane});
         slab_sync();
-        gemm_stage<8, 4, G>(buf1, acc, lane, hlo, [&]() { slab_dma_c<HALF>(buf0, packed + L.l5b + HALF, wave, lane); });
+        gemm_stage<8, 4, G>(buf1, acc, lane, hlo, SlabUnder<HALF>{buf0, packed + L.l5b + HALF, wave, lane});
         slab_sync();
         // next slab: the first half of feature_linear, or - folded - the folded views segment, which fills the buffer (SLAB_FLOATS).  One
         // branch-free DMA of that size serves both (an unfolded tile moves 2 KB of feature_linear's second half it does not read).
-        gemm_stage<8, 4, G>(buf0, acc, lane, hhi, [&]() {
-            if constexpr (SAVE) slab_dma_c<HALF>(buf1, packed + L.feat, wave, lane);
-            else if constexpr (!ALPHA_ONLY) slab_dma_c<(int)seg_floats(VIEW_STEPS, 2)>(buf1, packed + (fold ? fold_views_off(F) : L.feat), wave, lane);
-        });
+        if constexpr (SAVE) gemm_stage<8, 4, G>(buf0, acc, lane, hhi, SlabUnder<HALF>{buf1, packed + L.feat, wave, lane});
+        else if constexpr (!ALPHA_ONLY) gemm_stage<8, 4, G>(buf0, acc, lane, hhi, SlabUnder<(int)seg_floats(VIEW_STEPS, 2)>{buf1, packed + (fold ? fold_views_off(F) : L.feat), wave, lane});
+        else gemm_stage<8, 4, G>(buf0, acc, lane, hhi);
         if (add) {
 #pragma unroll
             for (int q = 0; q < 64; q += 2) {
@@ -606,9 +625,9 @@ __device__ __forceinline__ void mlp_fwd_pipe_tile(
         f32x16 acc[G][4];
         slab_sync();
         init_acc<4, G>(acc, vec + V_FEAT + half * 64);
-        gemm_stage<8, 4, G>(buf1, acc, lane, hlo, [&]() { slab_dma_c<HALF>(buf0, packed + L.feat + HALF, wave, lane); });
+        gemm_stage<8, 4, G>(buf1, acc, lane, hlo, SlabUnder<HALF>{buf0, packed + L.feat + HALF, wave, lane});
         slab_sync();
-        gemm_stage<8, 4, G>(buf0, acc, lane, hhi, [&]() { slab_dma_c<(int)seg_floats(VIEW_STEPS, 2)>(buf1, packed + L.views, wave, lane); });
+        gemm_stage<8, 4, G>(buf0, acc, lane, hhi, SlabUnder<(int)seg_floats(VIEW_STEPS, 2)>{buf1, packed + L.views, wave, lane});
 #pragma unroll
         for (int q = 0; q < 64; ++q) { h[q] = acc[0][q >> 4][q & 15]; save(S_FE + q, h[q]); }
     }
