@@ -8,7 +8,9 @@ Internally every 3-D tensor is channel-last in HBM; the tensors handed back to c
 NCDHW views of that memory (no copies), e.g. the neural volume is (1,8,D,h,w) with channels_last_3d
 strides and feeds the ray-march kernels without a transpose.
 """
+import contextlib
 import ctypes
+import threading
 import time
 
 import torch
@@ -115,7 +117,6 @@ class _PackBatch:
 
     @staticmethod
     def launch(jobs):
-        import ctypes
         lib = _lib.lib()
         for i in range(0, len(jobs), 64):
             part = jobs[i:i + 64]
@@ -144,64 +145,68 @@ def _log_pack(pk, method, *args):
             log.append(entry)
 
 
-class _PackedConv2d:
-    """Caches the [k*k][cin_pad][cout] re-layouts of a Conv2d weight (re-packed when it changes); get_bf16: the bf16 fragments (_get_bf16_2d).
+class _Packed:
+    """What _PackedConv2d and _PackedConv share: the layer, its cached re-layouts and the log MVSNet.prepack replays."""
+    log = None          # MVSNet.__init__ attaches the network's shared list
+
+    def __init__(self, conv):
+        self.conv, self.cache = conv, {}
+
+    def _lookup(self, name, make, extra=(), log=None):
+        """cache[name], made again by make() when the weight changed.  The one place that knows the key: the weight's address and `_version`, and the
+        optimizer epoch - a fused optimizer steps without bumping `_version` (_lib.py, "weight-cache epoch"); `extra`: what else selects the contents
+        of a slot.  log = (method, *args): the getter call MVSNet.prepack replays in its batch."""
+        w = self.conv.weight
+        key = (w.data_ptr(), w._version, _lib.weights_epoch()) + extra
+        hit = self.cache.get(name)
+        if hit is not None and hit[0] == key:
+            return hit[1]
+        buf = make()
+        if log is not None:
+            _log_pack(self, *log)
+        self.cache[name] = (key, buf)
+        return buf
+
+    def _weight_ptr(self):
+        return dev_f32(self.conv.weight.detach().contiguous(), "conv weight")
+
+    def _relayout(self, mode, kind, n=None, dtype=torch.float32):
+        """Layout `kind` of mvsnerf_pack_weights_multi for the convolution _params(mode): n elements ([taps][ci_pad][co_pad] when not given)."""
+        p = self._params(mode)
+        buf = torch.empty(self.taps * p[2] * p[3] if n is None else n, device=self.conv.weight.device, dtype=dtype)
+        return _pack(self._weight_ptr(), buf, kind, self.taps, *p)
+
+
+class _PackedConv2d(_Packed):
+    """Caches the [k*k][cin_pad][cout] re-layouts of a Conv2d weight (re-packed when it changes); get_bf16: the bf16 fragments.
     mode 'fwd': the layer itself; mode 'dgrad': the convolution computing its data gradient (channel roles swapped,
     taps mirrored for stride 1; the stride-2 layers use the gather-form kernel with un-mirrored taps)."""
 
     def __init__(self, conv):
-        self.conv, self.cache = conv, {}
+        super().__init__(conv)
         self.cout, self.cin, self.k = conv.weight.shape[0], conv.weight.shape[1], conv.weight.shape[2]
         self.cin_pad = (self.cin + 3) // 4 * 4
+        self.taps = self.k * self.k
 
-    def get_bf16(self, mode="fwd"):
-        return _get_bf16_2d(self, mode)
+    def _params(self, mode):
+        """(ci_real, co_real, ci_pad, co_pad, s_ci, s_co, flip) of the convolution kernel that runs this layer ("fwd") or its data gradient ("dgrad")."""
+        kk = self.taps
+        if mode == "fwd":
+            return self.cin, self.cout, self.cin_pad, self.cout, kk, self.cin * kk, 0
+        return self.cout, self.cin, self.cout, self.cin_pad, self.cin * kk, kk, (1 if self.conv.stride[0] == 1 else 0)
 
     def get(self, mode="fwd"):
-        w = self.conv.weight
-        key = (w.data_ptr(), w._version, _lib.weights_epoch())
-        hit = self.cache.get(mode)
-        if hit is not None and hit[0] == key:
-            return hit[1]
-        kk = self.k * self.k
-        if mode == "fwd":
-            args = (self.cin, self.cout, self.cin_pad, self.cout, kk, self.cin * kk, self.k, 0)
-        else:
-            args = (self.cout, self.cin, self.cout, self.cin_pad, self.cin * kk, kk, self.k, 1 if self.conv.stride[0] == 1 else 0)
-        buf = torch.empty(kk * args[2] * args[3], device=w.device, dtype=torch.float32)
-        ci_real, co_real, ci_pad, co_pad, s_ci, s_co, _, flip = args
-        _pack(dev_f32(w.detach().contiguous(), "conv weight"), buf, 0, kk, ci_real, co_real, ci_pad, co_pad, s_ci, s_co, flip)
-        _log_pack(self, "get", mode)
-        self.cache[mode] = (key, buf)
-        return buf
+        return self._lookup(mode, lambda: self._relayout(mode, 0), log=("get", mode))
 
-
-def _get_bf16_2d(pk, mode="fwd"):
-    """bf16 B fragments of a Conv2d (or of its stride-1 data gradient) for mvsnerf_conv2d_bf16_fwd; None when that shape has no such kernel."""
-    w = pk.conv.weight
-    kk = pk.k * pk.k
-    if mode == "fwd":
-        ci_real, co_real, ci_pad, co_pad, s_ci, s_co, flip = pk.cin, pk.cout, pk.cin_pad, pk.cout, kk, pk.cin * kk, 0
-    else:
-        if pk.conv.stride[0] != 1:
+    def get_bf16(self, mode="fwd"):
+        """bf16 B fragments of the layer (or of its stride-1 data gradient) for mvsnerf_conv2d_bf16_fwd; None when that shape has no such kernel."""
+        _, _, ci_pad, co_pad, _, _, _ = self._params(mode)
+        if (mode != "fwd" and self.conv.stride[0] != 1) or co_pad < 8:      # (the data gradient towards the 3-channel images is never needed)
             return None
-        ci_real, co_real, ci_pad, co_pad, s_ci, s_co, flip = pk.cout, pk.cin, pk.cout, pk.cin_pad, pk.cin * kk, kk, 1
-    lib = _lib.lib()
-    if co_pad < 8:                       # the data gradient towards the 3-channel images is never needed
-        return None
-    n = lib.mvsnerf_conv2d_bf16_packed_elems(ci_pad, co_pad, pk.k)
-    if n == 0:
-        return None
-    key = (w.data_ptr(), w._version, _lib.weights_epoch())
-    name = mode + "_bf16"
-    hit = pk.cache.get(name)
-    if hit is not None and hit[0] == key:
-        return hit[1]
-    buf = torch.empty(n, device=w.device, dtype=torch.bfloat16)
-    _pack(dev_f32(w.detach().contiguous(), "conv weight"), buf, 3, kk, ci_real, co_real, ci_pad, co_pad, s_ci, s_co, flip)
-    _log_pack(pk, "get_bf16", mode)
-    pk.cache[name] = (key, buf)
-    return buf
+        n = _lib.lib().mvsnerf_conv2d_bf16_packed_elems(ci_pad, co_pad, self.k)
+        if n == 0:
+            return None
+        return self._lookup(mode + "_bf16", lambda: self._relayout(mode, 3, n, torch.bfloat16), log=("get_bf16", mode))
 
 
 class _Nchw3:
@@ -211,41 +216,48 @@ class _Nchw3:
         self.x = x
 
 
+def _stats_part(want, floats_per_block, dev, tiles, *shape):
+    """The InPlaceABN partial sums a producing kernel leaves from its own launch, when wanted and tiles(*shape) (the library's count of blocks that
+    write a slot) is not 0: (their address for the C ABI, (buffer, n_blocks) for _abn_stats), else (0, None)."""
+    nblk = tiles(*shape) if want else 0
+    if nblk <= 0:
+        return 0, None
+    part = torch.empty(nblk * floats_per_block, device=dev, dtype=torch.float32)
+    return part.data_ptr(), (part, nblk)
+
+
 def _conv2d(src, dims_in, cin_ld, wbuf, cin_k, cout_k, ksize, stride, bias=None, want_stats=False, packed=None, mode="fwd"):
     """2-D convolution kernel launch (padding k//2): input (N,H,W) with channel stride cin_ld -> raw (N,Ho,Wo,cout_k).
     want_stats: returns (raw, InPlaceABN partial sums | None) - the matrix-core layers leave them from their own launch."""
     N, H, W, _ = dims_in
     P = ksize // 2
     Ho, Wo = (H + 2 * P - ksize) // stride + 1, (W + 2 * P - ksize) // stride + 1
+    nchw = isinstance(src, _Nchw3)
     dev = (src.x if isinstance(src, (_Lazy, _Nchw3)) else src).device
     out = torch.empty((N, Ho, Wo, cout_k), device=dev, dtype=torch.float32)
     lib = _lib.lib()
-    wq = _get_bf16_2d(packed, mode) if (_LAYER_BF16[0] and packed is not None and not isinstance(src, _Nchw3)) else None
+    want = want_stats and bias is None and FUSED_ABN_STATS
+    b_ptr = 0 if bias is None else bias.data_ptr()
+    wq = packed.get_bf16(mode) if (_LAYER_BF16[0] and packed is not None and not nchw) else None
     if wq is not None:               # use_amp: FeatureNet on the bf16 matrix cores (csrc/conv3d_bf16.hip), statistics from the same launch
-        part, nblk = None, 0
-        if want_stats and bias is None and FUSED_ABN_STATS:
-            nblk = lib.mvsnerf_conv2d_bf16_tiles(N, H, W, ksize, stride)
-            part = torch.empty(nblk * 2 * cout_k, device=dev, dtype=torch.float32)
-        check(lib.mvsnerf_conv2d_bf16_fwd(*_ptrs(src), cin_k, cin_ld, N, H, W, wq.data_ptr(), 0 if bias is None else bias.data_ptr(), cout_k, ksize, stride,
-                                          out.data_ptr(), 0 if part is None else part.data_ptr(), stream_ptr()), "conv2d_bf16_fwd")
-        return (out, None if part is None else (part, nblk)) if want_stats else out
-    if callable(wbuf):
-        wbuf = wbuf()
-    if isinstance(src, _Nchw3):      # FeatureNet's first layer of a no-grad encode: straight from the (N,3,H,W) images (csrc/featnet.hip conv2d_c8_lds_kernel)
-        nblk = lib.mvsnerf_conv2d_mfma_tiles(4, 8, N, H, W, 3, 1)
-        part = torch.empty(nblk * 2 * cout_k, device=out.device, dtype=torch.float32)
-        check(lib.mvsnerf_conv2d_c3_nchw_fwd_stats(src.x.data_ptr(), N, H, W, wbuf.data_ptr(), out.data_ptr(), part.data_ptr(), stream_ptr()), "conv2d_c3_nchw_fwd_stats")
-        return out, (part, nblk)
-    if want_stats and bias is None and FUSED_ABN_STATS:
-        nblk = lib.mvsnerf_conv2d_mfma_tiles(cin_k, cout_k, N, H, W, ksize, stride)
-        if nblk > 0:
-            part = torch.empty(nblk * 2 * cout_k, device=out.device, dtype=torch.float32)
-            check(lib.mvsnerf_conv2d_fwd_stats(*_ptrs(src), cin_k, cin_ld, N, H, W, wbuf.data_ptr(), cout_k, ksize, stride, out.data_ptr(),
-                                               part.data_ptr(), stream_ptr()), "conv2d_fwd_stats")
-            return out, (part, nblk)
-    check(lib.mvsnerf_conv2d_fwd(*_ptrs(src), cin_k, cin_ld, N, H, W, wbuf.data_ptr(), 0 if bias is None else bias.data_ptr(), cout_k,
-                                 ksize, stride, out.data_ptr(), stream_ptr()), "conv2d_fwd")
-    return (out, None) if want_stats else out
+        pp, partials = _stats_part(want, 2 * cout_k, dev, lib.mvsnerf_conv2d_bf16_tiles, N, H, W, ksize, stride)
+        check(lib.mvsnerf_conv2d_bf16_fwd(*_ptrs(src), cin_k, cin_ld, N, H, W, wq.data_ptr(), b_ptr, cout_k, ksize, stride,
+                                          out.data_ptr(), pp, stream_ptr()), "conv2d_bf16_fwd")
+    else:
+        if callable(wbuf):
+            wbuf = wbuf()
+        if nchw:                     # FeatureNet's first layer of a no-grad encode: straight from the (N,3,H,W) images (csrc/featnet.hip conv2d_c8_lds_kernel)
+            pp, partials = _stats_part(True, 2 * cout_k, dev, lib.mvsnerf_conv2d_mfma_tiles, 4, 8, N, H, W, 3, 1)
+            check(lib.mvsnerf_conv2d_c3_nchw_fwd_stats(src.x.data_ptr(), N, H, W, wbuf.data_ptr(), out.data_ptr(), pp, stream_ptr()), "conv2d_c3_nchw_fwd_stats")
+        else:
+            pp, partials = _stats_part(want, 2 * cout_k, dev, lib.mvsnerf_conv2d_mfma_tiles, cin_k, cout_k, N, H, W, ksize, stride)
+            if partials is not None:
+                check(lib.mvsnerf_conv2d_fwd_stats(*_ptrs(src), cin_k, cin_ld, N, H, W, wbuf.data_ptr(), cout_k, ksize, stride, out.data_ptr(),
+                                                   pp, stream_ptr()), "conv2d_fwd_stats")
+            else:
+                check(lib.mvsnerf_conv2d_fwd(*_ptrs(src), cin_k, cin_ld, N, H, W, wbuf.data_ptr(), b_ptr, cout_k, ksize, stride,
+                                             out.data_ptr(), stream_ptr()), "conv2d_fwd")
+    return (out, partials) if (want_stats or nchw) else out        # (the image-reading first layer always leaves its statistics)
 
 
 class ConvBnReLU(nn.Module):
@@ -263,10 +275,7 @@ class ConvBnReLU(nn.Module):
     def lazy(self, src, dims_in, cin_ld):
         pk = self._packed
         raw, partials = _conv2d(src, dims_in, cin_ld, pk.get, pk.cin_pad, pk.cout, self.k, self.stride, want_stats=True, packed=pk)
-        N, H, W, C = raw.shape
-        scale, shift, mean, invstd = _abn_stats(raw, N * H * W, self.bn, update_running=self.bn.training,
-                                                partials=partials if self.bn.training else None)
-        return _Lazy(raw, scale, shift, (N, H, W, C), mean, invstd)
+        return _lazy_abn(raw, self.bn, partials if self.bn.training else None)
 
     def forward(self, x):
         """Stand-alone call on (N,Cin,H,W) -> activated (N,Cout,H',W') (channel-last memory)."""
@@ -314,7 +323,7 @@ class FeatureNet(nn.Module):
         if x.dim() != 4 or x.shape[1] != 3:
             raise RuntimeError(f"FeatureNet: expected (N,3,H,W) images, got {tuple(x.shape)}")
         N, _, H, W = x.shape
-        bf16 = ENCODER_PRECISION == "bf16" and BF16_LAYERS
+        bf16 = ENCODER_PRECISION == "bf16"
         if (not keep_input and not bf16 and FUSED_ABN_STATS and x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()
                 and x.data_ptr() % 4 == 0 and self.conv0[0].bn.training):
             img, ld = None, 4
@@ -360,7 +369,6 @@ class _PartialSums:
         self.jobs.append((ws, int(n_part), gw))
 
     def flush(self):
-        import ctypes
         lib = _lib.lib()
         for i in range(0, len(self.jobs), 32):
             jobs = self.jobs[i:i + 32]
@@ -378,7 +386,7 @@ def _wgrad2d(gx, A, X, B, ldx, g_dims, x_dims, ksize, stride, shape, sums=None):
     """gW[a][b][tap] = sum_o G[o][a] X[o*stride - k//2 + tap][b]  (mvsnerf_conv2d_wgrad).  sums: a _PartialSums that finishes gw later."""
     lib = _lib.lib()
     gw = torch.empty(shape, device=gx.device, dtype=torch.float32)
-    if _LAYER_BF16[0] and BF16_WGRAD:
+    if _LAYER_BF16[0]:
         n_parts = lib.mvsnerf_conv_wgrad_bf16_parts(A, B, g_dims[0], g_dims[1], g_dims[2], 1, ksize, stride)
         if n_parts > 0:             # use_amp: bf16 operands, v_mfma_f32_16x16x32_bf16 (csrc/wgrad_bf16.hip)
             ws = torch.empty(lib.mvsnerf_conv_wgrad_bf16_workspace_floats(A, B, 1, ksize) if sums is None else n_parts * gw.numel(), device=gx.device, dtype=torch.float32)
@@ -404,7 +412,7 @@ class _FeatureNetFunction(torch.autograd.Function):
     def forward(ctx, x, net, *params):
         (img, ld), lz, top = net._run(x)
         ctx.net, ctx.img, ctx.ld, ctx.lz = net, img, ld, lz
-        ctx.layers_bf16 = ENCODER_PRECISION == "bf16" and BF16_LAYERS
+        ctx.layers_bf16 = ENCODER_PRECISION == "bf16"
         return top.permute(0, 3, 1, 2)
 
     @staticmethod
@@ -489,14 +497,16 @@ def _as_channel_last(x, cin_pad):
     return dst, cin_pad
 
 
-class _PackedConv:
+class _PackedConv(_Packed):
     """Caches the [27][cin_pad][cout_pad] re-layouts of a Conv3d / ConvTranspose3d weight (re-packed when it changes).
     mode 'fwd': the layer itself.  mode 'dgrad': the convolution that computes its data gradient -
       Conv3d s1 -> Conv3d s1 with mirrored taps and swapped channel roles; Conv3d s2 -> ConvTranspose3d s2;
       ConvTranspose3d s2 -> Conv3d s2."""
+    taps = 27
 
     def __init__(self, conv, transposed):
-        self.conv, self.transposed, self.cache = conv, transposed, {}
+        super().__init__(conv)
+        self.transposed = transposed
         w = conv.weight
         self.cin, self.cout = (w.shape[0], w.shape[1]) if transposed else (w.shape[1], w.shape[0])
         self.cin_pad = (self.cin + 3) // 4 * 4
@@ -511,123 +521,80 @@ class _PackedConv:
         s_ci, s_co = (27, cout * 27) if self.transposed else (cin * 27, 27)
         return cout, cin, cout, self.cin_pad, s_ci, s_co, (1 if (not self.transposed and self.conv.stride[0] == 1) else 0)
 
-    def _cached(self, name, kind, mode, method, *args):
-        w = self.conv.weight
-        key = (w.data_ptr(), w._version, _lib.weights_epoch())
-        hit = self.cache.get(name)
-        if hit is not None and hit[0] == key:
-            return hit[1]
-        ci_real, co_real, ci_pad, co_pad, s_ci, s_co, flip = self._params(mode)
-        buf = torch.empty(27 * ci_pad * co_pad, device=w.device, dtype=torch.float32)
-        _pack(dev_f32(w.detach().contiguous(), "conv weight"), buf, kind, 27, ci_real, co_real, ci_pad, co_pad, s_ci, s_co, flip)
-        _log_pack(self, method, *args)
-        self.cache[name] = (key, buf)
-        return buf
+    def _need_conv0(self, what):
+        if self.transposed or self.conv.stride[0] != 1 or self.cout != 8:
+            raise RuntimeError(f"{what}: stride-1 Conv3d with 8 output channels (conv0)")
 
     def get(self, mode="fwd"):
-        return self._cached(mode, 0, mode, "get", mode)
+        return self._lookup(mode, lambda: self._relayout(mode, 0), log=("get", mode))
 
     def get_c8(self, mode="fwd"):
         """[ci/4][tap][co][4] layout of get(mode)'s weights: the DMA-staged matrix-core conv0 and the 16 -> 8 transposed layer."""
-        return self._cached(mode + "_c8", 1, mode, "get_c8", mode)
+        return self._lookup(mode + "_c8", lambda: self._relayout(mode, 1), log=("get_c8", mode))
+
+    def get_mfma(self, mode="fwd"):
+        """[tap][ci/8][co][8] layout of get(mode)'s weights for the matrix-core kernels of the 32/64-channel layers."""
+        return self._lookup(mode + "_m32", lambda: self._relayout(mode, 2), log=("get_mfma", mode))
 
     def get_dgrad_slice(self, c0, n):
         """get("dgrad") restricted to the layer inputs c0 .. c0+n-1 (stride-1 Conv3d): [27][cout][n], mirrored taps.  The plane sweep's
         backward needs the gradient of the variance channels only (the warped thumbnails carry no parameters)."""
-        w = self.conv.weight
-        key = (w.data_ptr(), w._version, _lib.weights_epoch(), c0, n)
-        hit = self.cache.get("dgrad_slice")
-        if hit is not None and hit[0] == key:
-            return hit[1]
         if self.transposed or self.conv.stride[0] != 1 or n % 4 or c0 < 0 or c0 + n > self.cin:
             raise RuntimeError("get_dgrad_slice: stride-1 Conv3d and a channel range inside the layer's inputs (multiple of 4 wide)")
-        wc = dev_f32(w.detach().contiguous(), "conv weight")
-        buf = torch.empty(27 * self.cout * n, device=w.device, dtype=torch.float32)
-        _pack(wc + c0 * 27 * 4, buf, 0, 27, self.cout, n, self.cout, n, self.cin * 27, 27, 1)
-        _log_pack(self, "get_dgrad_slice", c0, n)
-        self.cache["dgrad_slice"] = (key, buf)
-        return buf
+
+        def make():
+            buf = torch.empty(27 * self.cout * n, device=self.conv.weight.device, dtype=torch.float32)
+            return _pack(self._weight_ptr() + c0 * 27 * 4, buf, 0, 27, self.cout, n, self.cout, n, self.cin * 27, 27, 1)
+        return self._lookup("dgrad_slice", make, (c0, n), log=("get_dgrad_slice", c0, n))
 
     def get_f16x3(self):
         """Two-piece fp16 B fragments of the layer's own weights for csrc/conv_f16x3_tiled.hip (conv1 / conv2 of a no-grad encode):
         mvsnerf_conv3d_f16x3_pack, cached like every other layout."""
-        w = self.conv.weight
-        key = (w.data_ptr(), w._version, _lib.weights_epoch())
-        hit = self.cache.get("f16x3t")
-        if hit is not None and hit[0] == key:
-            return hit[1]
-        lib = _lib.lib()
-        buf = torch.empty(lib.mvsnerf_conv3d_f16x3_packed_elems(self.cin), device=w.device, dtype=torch.float16)
-        check(lib.mvsnerf_conv3d_f16x3_pack(dev_f32(w.detach().contiguous(), "conv weight"), self.cin, self.cout, buf.data_ptr(), stream_ptr()), "conv3d_f16x3_pack")
-        self.cache["f16x3t"] = (key, buf)
-        return buf
-
-    def get_mfma(self, mode="fwd"):
-        """[tap][ci/8][co][8] layout of get(mode)'s weights for the matrix-core kernels of the 32/64-channel layers."""
-        return self._cached(mode + "_m32", 2, mode, "get_mfma", mode)
+        def make():
+            lib = _lib.lib()
+            buf = torch.empty(lib.mvsnerf_conv3d_f16x3_packed_elems(self.cin), device=self.conv.weight.device, dtype=torch.float16)
+            check(lib.mvsnerf_conv3d_f16x3_pack(self._weight_ptr(), self.cin, self.cout, buf.data_ptr(), stream_ptr()), "conv3d_f16x3_pack")
+            return buf
+        return self._lookup("f16x3t", make)
 
     def get_bf16(self, mode="fwd"):
         """bf16 B fragments of get(mode)'s convolution for the generic bf16 kernels (csrc/conv3d_bf16.hip); None when the shape has no such kernel.
         The KERNEL that runs `mode` is transposed when exactly one of (layer is transposed, mode is its data gradient of a strided layer) holds:
         a stride-2 Conv3d's data gradient is a transposed convolution and vice versa."""
-        w = self.conv.weight
-        ci_real, co_real, ci_pad, co_pad, _, _, _ = self._params(mode)
-        strided = self.conv.stride[0] == 2
-        kernel_t = (self.transposed != (mode == "dgrad")) if strided else False
-        lib = _lib.lib()
-        n = lib.mvsnerf_conv3d_bf16_packed_elems(ci_pad, co_pad, int(kernel_t))
+        ci_real, _, ci_pad, co_pad, _, _, _ = self._params(mode)
+        kernel_t = self.conv.stride[0] == 2 and self.transposed != (mode == "dgrad")
+        n = _lib.lib().mvsnerf_conv3d_bf16_packed_elems(ci_pad, co_pad, int(kernel_t))
         if n == 0 or ci_real != ci_pad:
             return None
-        key = (w.data_ptr(), w._version, _lib.weights_epoch())
-        name = mode + "_bf16"
-        hit = self.cache.get(name)
-        if hit is not None and hit[0] == key:
-            return hit[1]
-        _, _, _, _, s_ci, s_co, flip = self._params(mode)
-        buf = torch.empty(n, device=w.device, dtype=torch.bfloat16)
         # straight from the nn weights (kinds 3 / 4 of mvsnerf_pack_weights_multi): batched with the step's other re-layouts by MVSNet.prepack
-        _pack(dev_f32(w.detach().contiguous(), "conv weight"), buf, 4 if kernel_t else 3, 27, ci_real, co_real, ci_pad, co_pad, s_ci, s_co, flip)
-        _log_pack(self, "get_bf16", mode)
-        self.cache[name] = (key, buf)
-        return buf
+        return self._lookup(mode + "_bf16", lambda: self._relayout(mode, 4 if kernel_t else 3, n, torch.bfloat16), log=("get_bf16", mode))
 
     def get_bf16_conv0(self, dgrad=None):
         """bf16 B fragments of the 8-output-channel stride-1 layer (csrc/conv_bf16.hip): dgrad None -> forward; (c_first, n_ci) -> the
         data gradient w.r.t. input channels c_first .. c_first + n_ci - 1."""
-        w = self.conv.weight
-        key = (w.data_ptr(), w._version, _lib.weights_epoch(), dgrad)
-        name = "bf16_fwd" if dgrad is None else "bf16_dgrad"
-        hit = self.cache.get(name)
-        if hit is not None and hit[0] == key:
-            return hit[1]
-        if self.transposed or self.conv.stride[0] != 1 or self.cout != 8:
-            raise RuntimeError("get_bf16_conv0: stride-1 Conv3d with 8 output channels (conv0)")
-        lib = _lib.lib()
-        wc = dev_f32(w.detach().contiguous(), "conv weight")
-        if dgrad is None:
-            buf = torch.empty(lib.mvsnerf_conv0_bf16_packed_elems(self.cin), device=w.device, dtype=torch.bfloat16)
-            check(lib.mvsnerf_conv0_bf16_pack(wc, self.cin, buf.data_ptr(), stream_ptr()), "conv0_bf16_pack")
-        else:
-            buf = torch.empty(lib.mvsnerf_conv0_bf16_dgrad_packed_elems(dgrad[1]), device=w.device, dtype=torch.bfloat16)
-            check(lib.mvsnerf_conv0_bf16_dgrad_pack(wc, self.cin, dgrad[0], dgrad[1], buf.data_ptr(), stream_ptr()), "conv0_bf16_dgrad_pack")
-        self.cache[name] = (key, buf)
-        return buf
+        self._need_conv0("get_bf16_conv0")
 
+        def make():
+            lib, dev = _lib.lib(), self.conv.weight.device
+            if dgrad is None:
+                buf = torch.empty(lib.mvsnerf_conv0_bf16_packed_elems(self.cin), device=dev, dtype=torch.bfloat16)
+                check(lib.mvsnerf_conv0_bf16_pack(self._weight_ptr(), self.cin, buf.data_ptr(), stream_ptr()), "conv0_bf16_pack")
+            else:
+                buf = torch.empty(lib.mvsnerf_conv0_bf16_dgrad_packed_elems(dgrad[1]), device=dev, dtype=torch.bfloat16)
+                check(lib.mvsnerf_conv0_bf16_dgrad_pack(self._weight_ptr(), self.cin, dgrad[0], dgrad[1], buf.data_ptr(), stream_ptr()), "conv0_bf16_dgrad_pack")
+            return buf
+        return self._lookup("bf16_fwd" if dgrad is None else "bf16_dgrad", make, (dgrad,))
 
-def _get_f16x3_conv0(pk):
-    """fp16 hi / lo B fragments of conv0 (csrc/conv_f16x3.hip), cached like the other layouts of _PackedConv."""
-    w = pk.conv.weight
-    key = (w.data_ptr(), w._version, _lib.weights_epoch())
-    hit = pk.cache.get("f16x3_fwd")
-    if hit is not None and hit[0] == key:
-        return hit[1]
-    if pk.transposed or pk.conv.stride[0] != 1 or pk.cout != 8:
-        raise RuntimeError("fp16x3 conv0: stride-1 Conv3d with 8 output channels (conv0)")
-    lib = _lib.lib()
-    buf = torch.empty(lib.mvsnerf_conv0_f16x3_packed_elems(pk.cin), device=w.device, dtype=torch.float16)
-    check(lib.mvsnerf_conv0_f16x3_pack(dev_f32(w.detach().contiguous(), "conv weight"), pk.cin, buf.data_ptr(), stream_ptr()), "conv0_f16x3_pack")
-    pk.cache["f16x3_fwd"] = (key, buf)
-    return buf
+    def get_f16x3_conv0(self):
+        """fp16 hi / lo B fragments of conv0 (csrc/conv_f16x3.hip), cached like the other layouts."""
+        self._need_conv0("fp16x3 conv0")
+
+        def make():
+            lib = _lib.lib()
+            buf = torch.empty(lib.mvsnerf_conv0_f16x3_packed_elems(self.cin), device=self.conv.weight.device, dtype=torch.float16)
+            check(lib.mvsnerf_conv0_f16x3_pack(self._weight_ptr(), self.cin, buf.data_ptr(), stream_ptr()), "conv0_f16x3_pack")
+            return buf
+        return self._lookup("f16x3_fwd", make)
 
 
 def _abn_stats(raw, n_vox, bn, update_running=True, partials=None):
@@ -651,28 +618,55 @@ def _abn_stats(raw, n_vox, bn, update_running=True, partials=None):
         check(_lib.lib().mvsnerf_abn_finalize(partials[0].data_ptr(), partials[1], C, n_vox, dev_f32(bn.weight.detach(), "bn.weight"),
                                               dev_f32(bn.bias.detach(), "bn.bias"), rm, rv, bn.momentum, bn.eps, out[0].data_ptr(), out[1].data_ptr(),
                                               out[2].data_ptr(), out[3].data_ptr(), stream_ptr()), "abn_finalize")
-        if update_running:
-            _NBT_PENDING.append(bn.num_batches_tracked)
-        return out[0], out[1], out[2], out[3]
-    ws = torch.empty(_lib.lib().mvsnerf_abn_workspace_floats(C), device=dev, dtype=torch.float32)
-    check(_lib.lib().mvsnerf_abn_stats(raw.data_ptr(), n_vox, C, dev_f32(bn.weight.detach(), "bn.weight"), dev_f32(bn.bias.detach(), "bn.bias"),
-                                       rm, rv, bn.momentum, bn.eps, out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), out[3].data_ptr(),
-                                       ws.data_ptr(), stream_ptr()), "abn_stats")
+    else:
+        ws = torch.empty(_lib.lib().mvsnerf_abn_workspace_floats(C), device=dev, dtype=torch.float32)
+        check(_lib.lib().mvsnerf_abn_stats(raw.data_ptr(), n_vox, C, dev_f32(bn.weight.detach(), "bn.weight"), dev_f32(bn.bias.detach(), "bn.bias"),
+                                           rm, rv, bn.momentum, bn.eps, out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), out[3].data_ptr(),
+                                           ws.data_ptr(), stream_ptr()), "abn_stats")
     if update_running:
-        _NBT_PENDING.append(bn.num_batches_tracked)
+        _note_nbt(bn.num_batches_tracked)
     return out[0], out[1], out[2], out[3]
 
 
-_NBT_PENDING = []
-_NBT_DEFER = [0]           # > 0: MVSNet.forward is running FeatureNet - its layers' counters wait for the flush behind CostRegNet (one launch per encode, not two)
+def _lazy_abn(raw, bn, partials=None):
+    """A layer's raw channel-last output -> the _Lazy that carries its pending InPlaceABN (statistics of this batch in train mode; partials as in _abn_stats)."""
+    dims = tuple(raw.shape)
+    scale, shift, mean, invstd = _abn_stats(raw, dims[0] * dims[1] * dims[2], bn, update_running=bn.training, partials=partials)
+    return _Lazy(raw, scale, shift, dims, mean, invstd)
+
+
+class _Nbt(threading.local):
+    """This host thread's `num_batches_tracked` counters that wait for their increment, and how deep it is inside _defer_nbt().  Per thread like the
+    precision switches below (_ThreadCell): a second thread's flush must neither take these counters along nor be held back by this thread's deferral."""
+
+    def __init__(self):
+        self.pending, self.defer = [], 0
+
+
+_NBT = _Nbt()
+
+
+def _note_nbt(counter):
+    _NBT.pending.append(counter)
+
+
+@contextlib.contextmanager
+def _defer_nbt():
+    """MVSNet.forward around FeatureNet: its layers' counters wait for the flush behind CostRegNet (one launch per encode, not two)."""
+    _NBT.defer += 1
+    try:
+        yield
+    finally:
+        _NBT.defer -= 1
 
 
 def _flush_nbt():
-    """`num_batches_tracked += 1` of every layer that ran, as ONE foreach launch per network pass instead of one tiny ATen
+    """`num_batches_tracked += 1` of every layer that ran on this thread, as ONE foreach launch per network pass instead of one tiny ATen
     kernel per layer (18 of them per scene encode)."""
-    if _NBT_PENDING and not _NBT_DEFER[0]:
-        torch._foreach_add_(list(_NBT_PENDING), 1)
-        _NBT_PENDING.clear()
+    nbt = _NBT
+    if nbt.pending and not nbt.defer:
+        torch._foreach_add_(nbt.pending, 1)
+        nbt.pending = []
 
 
 def _ptrs(src):
@@ -690,7 +684,6 @@ class _ThreadCell:
     words and workspaces are per stream) must not see each other's (thread A's `_F16X3_CONSUME[0] = 0` leaking into thread B's conv2 launch)."""
 
     def __init__(self, default):
-        import threading
         self._tls, self._default = threading.local(), default
 
     def __getitem__(self, i):
@@ -700,13 +693,12 @@ class _ThreadCell:
         self._tls.v = value
 
 
-BF16_WGRAD = True          # A/B switch: the weight gradients of those layers on the bf16 kernel as well (csrc/wgrad_bf16.hip)
-BF16_LAYERS = True         # A/B switch (scratch/r4): False keeps conv1 ... conv11 on the fp32 kernels under use_amp (round 3's behaviour)
-_LAYER_BF16 = _ThreadCell(False)      # conv1 ... conv11 on the bf16 matrix cores (csrc/conv3d_bf16.hip): set for the extent of a forward / backward by _layer_precision
+# conv1 ... conv11 and their weight gradients on the bf16 matrix cores (csrc/conv3d_bf16.hip, csrc/wgrad_bf16.hip): set for the extent of a forward / backward by _layer_precision
+_LAYER_BF16 = _ThreadCell(False)
 
-
-F16X3_LAYERS = True        # A/B switch: conv1 / conv2 of a no-grad "auto" encode on the guarded fp16x3 LDS-tiled kernel (csrc/conv_f16x3_tiled.hip)
-F16X3_MIN_VOXELS = 262144  # ... from this many OUTPUT voxels on (below, the layer is a few microseconds on any kernel and the persistent grid of 512 workgroups is mostly idle)
+# conv1 / conv2 of a no-grad encode run on the fp16x3 LDS-tiled kernel (csrc/conv_f16x3_tiled.hip) from this many OUTPUT voxels on (below, the layer is
+# a few microseconds on any kernel and the persistent grid of 512 workgroups is mostly idle)
+F16X3_MIN_VOXELS = 262144
 _LAYER_F16X3 = _ThreadCell(None)      # None, or "guarded" / "plain" for the extent of CostRegNet._run (set by _layers_f16x3)
 _F16X3_CONSUME = _ThreadCell(1)       # 0 while conv1 runs inside CostRegNet._run: conv2 (same output size, hence guarded as well) counts / re-arms for both
 
@@ -716,7 +708,7 @@ class _layers_f16x3:
     behind it, predicated on the guard word) or "plain" (encoder_precision("fp16x3"): the kernel alone; NaNs where an operand left fp16's range)."""
 
     def __init__(self, how):
-        self.how = how if F16X3_LAYERS else None
+        self.how = how
 
     def __enter__(self):
         self.prev, _LAYER_F16X3[0] = _LAYER_F16X3[0], self.how
@@ -747,57 +739,46 @@ def _conv(src1, src2, dims_in, cin_ld, wbuf, cin_k, cout_k, stride, packed=None,
     Do, Ho, Wo = (D - 1) // stride + 1, (H - 1) // stride + 1, (W - 1) // stride + 1
     dev = (src1.x if isinstance(src1, _Lazy) else src1).device
     out = torch.empty((Do, Ho, Wo, cout_k), device=dev, dtype=torch.float32)
+    lib = _lib.lib()
+    want = want_stats and FUSED_ABN_STATS
+    how = _LAYER_F16X3[0]
     wq = packed.get_bf16(mode) if (_LAYER_BF16[0] and packed is not None) else None
     if wq is not None:               # use_amp: bf16 operands on v_mfma_f32_16x16x32_bf16, fp32 accumulation, statistics from the same launch
-        lib = _lib.lib()
-        part, nblk = None, 0
-        if want_stats and FUSED_ABN_STATS:
-            nblk = lib.mvsnerf_conv3d_bf16_tiles(D, H, W, stride)
-            part = torch.empty(nblk * 2 * cout_k, device=out.device, dtype=torch.float32)
+        pp, partials = _stats_part(want, 2 * cout_k, dev, lib.mvsnerf_conv3d_bf16_tiles, D, H, W, stride)
         check(lib.mvsnerf_conv3d_bf16_fwd(*_ptrs(src1), *_ptrs(src2), cin_k, cin_ld, D, H, W, wq.data_ptr(), cout_k, stride, out.data_ptr(),
-                                          0 if part is None else part.data_ptr(), stream_ptr()), "conv3d_bf16_fwd")
-        return out if want_stats is None else (out, None if part is None else (part, nblk))
-    how = _LAYER_F16X3[0]
-    if (how is not None and packed is not None and src2 is None and mode == "fwd" and want_stats and FUSED_ABN_STATS and cout_k == 16
+                                          pp, stream_ptr()), "conv3d_bf16_fwd")
+    elif (how is not None and packed is not None and src2 is None and mode == "fwd" and want and cout_k == 16
             and (cin_k, stride) in ((8, 2), (16, 1)) and Do * Ho * Wo >= F16X3_MIN_VOXELS):
         # conv1 / conv2 of a no-grad encode: fp32-grade results from the fp16 matrix cores (52 / 43 us instead of 107 / 120 at config 2)
-        lib = _lib.lib()
         x, sc, sh = _ptrs(src1)
-        nblk = lib.mvsnerf_conv3d_f16x3_slots()
-        part = torch.empty(nblk * 2 * cout_k, device=out.device, dtype=torch.float32)
+        pp, partials = _stats_part(True, 2 * cout_k, dev, lib.mvsnerf_conv3d_f16x3_slots)
         if how == "guarded":
             w32 = packed.get_mfma("fwd") if cin_k == 8 else (wbuf() if callable(wbuf) else wbuf)      # the layouts of the layer's fp32 kernels
             check(lib.mvsnerf_conv3d_f16x3_guarded_fwd(x, sc, sh, cin_k, cin_ld, D, H, W, packed.get_f16x3().data_ptr(), w32.data_ptr(), cout_k, stride,
-                                                       out.data_ptr(), part.data_ptr(), ops.guard_words(out.device).data_ptr(), _F16X3_CONSUME[0], stream_ptr()),
+                                                       out.data_ptr(), pp, ops.guard_words(dev).data_ptr(), _F16X3_CONSUME[0], stream_ptr()),
                   "conv3d_f16x3_guarded_fwd")
         else:
             check(lib.mvsnerf_conv3d_f16x3_fwd(x, sc, sh, cin_k, cin_ld, D, H, W, packed.get_f16x3().data_ptr(), cout_k, stride, out.data_ptr(),
-                                               part.data_ptr(), stream_ptr()), "conv3d_f16x3_fwd")
-        return out, (part, nblk)
-    if packed is not None and src2 is None and _lib.lib().mvsnerf_conv3d_mfma_supported(cin_k, cout_k, stride):
-        lib = _lib.lib()
+                                               pp, stream_ptr()), "conv3d_f16x3_fwd")
+    elif packed is not None and src2 is None and lib.mvsnerf_conv3d_mfma_supported(cin_k, cout_k, stride):
         x, sc, sh = _ptrs(src1)
-        part, nblk = None, 0
-        if want_stats and FUSED_ABN_STATS:
-            nblk = lib.mvsnerf_conv3d_mfma_tiles(D, H, W, stride)
-            part = torch.empty(nblk * 2 * cout_k, device=out.device, dtype=torch.float32)
+        pp, partials = _stats_part(want, 2 * cout_k, dev, lib.mvsnerf_conv3d_mfma_tiles, D, H, W, stride)
         check(lib.mvsnerf_conv3d_mfma_fwd(x, sc, sh, cin_k, cin_ld, D, H, W, packed.get_mfma(mode).data_ptr(), cout_k, stride,
-                                          out.data_ptr(), 0 if part is None else part.data_ptr(), stream_ptr()), "conv3d_mfma_fwd")
-        return out if want_stats is None else (out, None if part is None else (part, nblk))
-    if callable(wbuf):
-        wbuf = wbuf()               # the VALU layout is only packed when this branch runs (no eager pk.get() per step)
-    if want_stats and FUSED_ABN_STATS and src2 is None and (cin_k, cout_k, stride) == (16, 16, 1):
-        nblk = _lib.lib().mvsnerf_conv3d_tiled_tiles(D, H, W)          # conv2: statistics from the convolution's own launch
-        part = torch.empty(nblk * 2 * cout_k, device=out.device, dtype=torch.float32)
-        rc = _lib.lib().mvsnerf_conv3d_fwd_stats(*_ptrs(src1), cin_k, cin_ld, D, H, W, wbuf.data_ptr(), cout_k, stride, out.data_ptr(),
-                                                 part.data_ptr(), stream_ptr())
-        if rc == 0:
-            return out, (part, nblk)
-        if rc != -2:                                                   # MVSNERF_EUNSUPPORTED: fall through to the plain launch
+                                          out.data_ptr(), pp, stream_ptr()), "conv3d_mfma_fwd")
+    else:
+        if callable(wbuf):
+            wbuf = wbuf()               # the VALU layout is only packed when this branch runs (no eager pk.get() per step)
+        conv2 = src2 is None and (cin_k, cout_k, stride) == (16, 16, 1)          # statistics from the convolution's own launch
+        pp, partials = _stats_part(want and conv2, 2 * cout_k, dev, lib.mvsnerf_conv3d_tiled_tiles, D, H, W)
+        rc = -2 if partials is None else lib.mvsnerf_conv3d_fwd_stats(*_ptrs(src1), cin_k, cin_ld, D, H, W, wbuf.data_ptr(), cout_k, stride,
+                                                                      out.data_ptr(), pp, stream_ptr())
+        if rc != -2:
             check(rc, "conv3d_fwd_stats")
-    check(_lib.lib().mvsnerf_conv3d_fwd(*_ptrs(src1), *_ptrs(src2), cin_k, cin_ld, D, H, W, wbuf.data_ptr(), cout_k, stride,
-                                        out.data_ptr(), stream_ptr()), "conv3d_fwd")
-    return out if want_stats is None else (out, None)
+        else:                            # no statistics kernel for this launch (MVSNERF_EUNSUPPORTED when it is the shape): the plain one
+            partials = None
+            check(lib.mvsnerf_conv3d_fwd(*_ptrs(src1), *_ptrs(src2), cin_k, cin_ld, D, H, W, wbuf.data_ptr(), cout_k, stride,
+                                         out.data_ptr(), stream_ptr()), "conv3d_fwd")
+    return out if want_stats is None else (out, partials)
 
 
 def _conv_t(src1, src2, dims_in, wbuf, cin_k, cout_k, packed=None, mode="fwd", want_stats=None):
@@ -808,41 +789,35 @@ def _conv_t(src1, src2, dims_in, wbuf, cin_k, cout_k, packed=None, mode="fwd", w
     D, H, W, _ = dims_in
     dev = (src1.x if isinstance(src1, _Lazy) else src1).device
     out = torch.empty((2 * D, 2 * H, 2 * W, cout_k), device=dev, dtype=torch.float32)
+    lib = _lib.lib()
+    want = want_stats and FUSED_ABN_STATS
     wq = packed.get_bf16(mode) if (_LAYER_BF16[0] and packed is not None) else None
     if wq is not None:               # use_amp: the eight parity classes as bf16 gather-form convolutions (csrc/conv3d_bf16.hip)
-        lib = _lib.lib()
-        part, nblk = None, 0
-        if want_stats and FUSED_ABN_STATS:
-            nblk = lib.mvsnerf_conv_transpose3d_bf16_tiles(D, H, W)
-            part = torch.empty(nblk * 2 * cout_k, device=out.device, dtype=torch.float32)
+        pp, partials = _stats_part(want, 2 * cout_k, dev, lib.mvsnerf_conv_transpose3d_bf16_tiles, D, H, W)
         check(lib.mvsnerf_conv_transpose3d_bf16_fwd(*_ptrs(src1), *_ptrs(src2), cin_k, D, H, W, wq.data_ptr(), cout_k, out.data_ptr(),
-                                                    0 if part is None else part.data_ptr(), stream_ptr()), "conv_transpose3d_bf16_fwd")
-        return out if want_stats is None else (out, None if part is None else (part, nblk))
-    if packed is not None and _lib.lib().mvsnerf_conv_transpose3d_c8_supported(cin_k, cout_k):
-        lib = _lib.lib()            # lazily-activated sources and the skip sum are applied while staging; statistics from the same launch
-        part, nblk = None, 0
-        if want_stats and FUSED_ABN_STATS:
-            nblk = lib.mvsnerf_conv_transpose3d_c8_tiles(D, H, W)
-            part = torch.empty(nblk * 16, device=out.device, dtype=torch.float32)
+                                                    pp, stream_ptr()), "conv_transpose3d_bf16_fwd")
+    elif packed is not None and lib.mvsnerf_conv_transpose3d_c8_supported(cin_k, cout_k):
+        # lazily-activated sources and the skip sum are applied while staging; statistics from the same launch
+        pp, partials = _stats_part(want, 16, dev, lib.mvsnerf_conv_transpose3d_c8_tiles, D, H, W)
         check(lib.mvsnerf_conv_transpose3d_c8_fwd(*_ptrs(src1), *_ptrs(src2), cin_k, D, H, W, packed.get_c8(mode).data_ptr(), out.data_ptr(),
-                                                  0 if part is None else part.data_ptr(), stream_ptr()), "conv_transpose3d_c8_fwd")
-        return out if want_stats is None else (out, None if part is None else (part, nblk))
-    if (packed is not None and src2 is None and torch.is_tensor(src1) and cin_k % 8 == 0
-            and _lib.lib().mvsnerf_conv_transpose3d_mfma_supported(cin_k, cout_k)):
-        if want_stats and FUSED_ABN_STATS:                             # conv7 / conv9: the statistics come from the accumulators
-            nblk = _lib.lib().mvsnerf_conv_transpose3d_mfma_tiles(cin_k, cout_k, D, H, W)
-            part = torch.empty(nblk * 2 * cout_k, device=out.device, dtype=torch.float32)
-            check(_lib.lib().mvsnerf_conv_transpose3d_mfma_fwd_stats(src1.data_ptr(), cin_k, D, H, W, packed.get_mfma(mode).data_ptr(), cout_k,
-                                                                     out.data_ptr(), part.data_ptr(), stream_ptr()), "conv_transpose3d_mfma_fwd_stats")
-            return out, (part, nblk)
-        check(_lib.lib().mvsnerf_conv_transpose3d_mfma_fwd(src1.data_ptr(), cin_k, D, H, W, packed.get_mfma(mode).data_ptr(), cout_k,
-                                                           out.data_ptr(), stream_ptr()), "conv_transpose3d_mfma_fwd")
-        return out if want_stats is None else (out, None)
-    if callable(wbuf):
-        wbuf = wbuf()
-    check(_lib.lib().mvsnerf_conv_transpose3d_fwd(*_ptrs(src1), *_ptrs(src2), cin_k, D, H, W, wbuf.data_ptr(), cout_k,
-                                                  out.data_ptr(), stream_ptr()), "conv_transpose3d_fwd")
-    return out if want_stats is None else (out, None)
+                                                  pp, stream_ptr()), "conv_transpose3d_c8_fwd")
+    elif (packed is not None and src2 is None and torch.is_tensor(src1) and cin_k % 8 == 0
+            and lib.mvsnerf_conv_transpose3d_mfma_supported(cin_k, cout_k)):
+        # conv7 / conv9: the statistics come from the accumulators
+        pp, partials = _stats_part(want, 2 * cout_k, dev, lib.mvsnerf_conv_transpose3d_mfma_tiles, cin_k, cout_k, D, H, W)
+        if partials is not None:
+            check(lib.mvsnerf_conv_transpose3d_mfma_fwd_stats(src1.data_ptr(), cin_k, D, H, W, packed.get_mfma(mode).data_ptr(), cout_k,
+                                                              out.data_ptr(), pp, stream_ptr()), "conv_transpose3d_mfma_fwd_stats")
+        else:
+            check(lib.mvsnerf_conv_transpose3d_mfma_fwd(src1.data_ptr(), cin_k, D, H, W, packed.get_mfma(mode).data_ptr(), cout_k,
+                                                        out.data_ptr(), stream_ptr()), "conv_transpose3d_mfma_fwd")
+    else:
+        partials = None
+        if callable(wbuf):
+            wbuf = wbuf()
+        check(lib.mvsnerf_conv_transpose3d_fwd(*_ptrs(src1), *_ptrs(src2), cin_k, D, H, W, wbuf.data_ptr(), cout_k,
+                                               out.data_ptr(), stream_ptr()), "conv_transpose3d_fwd")
+    return out if want_stats is None else (out, partials)
 
 
 def _apply_add(a, b=None):
@@ -882,9 +857,7 @@ class ConvBnReLU3D(nn.Module):
     def lazy(self, src1, dims_in, cin_ld, src2=None):
         pk = self._packed
         raw, partials = _conv(src1, src2, dims_in, cin_ld, pk.get, pk.cin_pad, pk.cout, self.stride, packed=pk, want_stats=self.bn.training)
-        D, H, W, C = raw.shape
-        scale, shift, mean, invstd = _abn_stats(raw, D * H * W, self.bn, update_running=self.bn.training, partials=partials)
-        return _Lazy(raw, scale, shift, (D, H, W, C), mean, invstd)
+        return _lazy_abn(raw, self.bn, partials)
 
     def forward(self, x):
         """Stand-alone call on a logical (1,Cin,D,H,W) tensor -> activated (1,Cout,D',H',W') (channel-last memory)."""
@@ -899,9 +872,7 @@ class ConvBnReLU3D(nn.Module):
         return self._packed.cin_pad
 
 
-MATERIALIZE_UP_INPUT = True     # A/B switch (scratch/enc_time.py)
 FUSED_ABN_STATS = True          # A/B switch: the 8-channel producers (conv0, conv11) leave their InPlaceABN partial sums themselves
-BLOCKED_COST = True             # A/B switch: MVSNet.forward hands conv0 a channel-blocked cost volume on the no-grad path
 _BLOCKED_CIN = (32, 36, 40, 44, 48, 52, 56)   # conv0 input widths the matrix-core kernel is instantiated for
 
 
@@ -914,14 +885,11 @@ class _UpBlock(nn.Sequential):
 
     def lazy(self, src1, dims_in, src2=None):
         pk = self._packed
-        if (MATERIALIZE_UP_INPUT and isinstance(src1, _Lazy)
-                and not _lib.lib().mvsnerf_conv_transpose3d_c8_supported(pk.cin_pad, pk.cout)):      # (that kernel activates while staging)
+        if isinstance(src1, _Lazy) and not _lib.lib().mvsnerf_conv_transpose3d_c8_supported(pk.cin_pad, pk.cout):      # (that kernel activates while staging)
             # every input voxel feeds 27/8 output voxels on average: activate (and sum the skip) once instead of per tap
             src1, src2 = _apply_add(src1, src2), None
         raw, partials = _conv_t(src1, src2, dims_in, pk.get, pk.cin_pad, pk.cout, packed=pk, want_stats=self[1].training)
-        D, H, W, C = raw.shape
-        scale, shift, mean, invstd = _abn_stats(raw, D * H * W, self[1], update_running=self[1].training, partials=partials)
-        return _Lazy(raw, scale, shift, (D, H, W, C), mean, invstd)
+        return _lazy_abn(raw, self[1], partials)
 
     def forward(self, x):
         ops._need_no_grad(x, *self.parameters(), op="ConvTranspose3d+ABN")
@@ -963,54 +931,39 @@ class CostRegNet(nn.Module):
             raise RuntimeError(f"CostRegNet needs D,h,w divisible by 8 (three stride-2 stages), got {(D, H, W)}")
         # the hand-off says which encode this is: _Conv0Done = the guarded no-grad default, two fp16 planes = encoder_precision("fp16x3")
         f16 = "guarded" if isinstance(x, _Conv0Done) else ("plain" if isinstance(x, _BlockedCostH2) else None)
-        if isinstance(x, _Conv0Done):          # conv0 already ran inside the guarded encode head (_plane_sweep, blocked="guarded")
-            raw = x.buf
-            scale, shift, mean, invstd = _abn_stats(raw, D * H * W, self.conv0.bn, update_running=self.conv0.bn.training,
-                                                    partials=None if x.part is None else (x.part, x.nblk))
-            c0 = _Lazy(raw, scale, shift, (D, H, W, 8), mean, invstd)
-            buf, ld = None, 0
-        elif isinstance(x, _BlockedCost16):
-            pk = self.conv0._packed
-            if x.n_ch != pk.cin:
-                raise RuntimeError(f"CostRegNet: 16-bit cost volume has {x.n_ch} channels, conv0 expects {pk.cin}")
-            raw = torch.empty((D, H, W, pk.cout), device=x.buf.device, dtype=torch.float32)
-            lib = _lib.lib()
-            want = self.conv0.bn.training and FUSED_ABN_STATS
-            nblk = lib.mvsnerf_conv0_bf16_tiles(D, H, W)                   # the fp16x3 kernel has the same tiles / statistics slots
-            part = torch.empty(nblk * 16, device=raw.device, dtype=torch.float32) if want else None
-            if isinstance(x, _BlockedCostH2):
-                check(lib.mvsnerf_conv0_f16x3_fwd(x.buf.data_ptr(), pk.cin, D, H, W, _get_f16x3_conv0(pk).data_ptr(), raw.data_ptr(),
-                                                  0 if part is None else part.data_ptr(), stream_ptr()), "conv0_f16x3_fwd")
-            else:
-                check(lib.mvsnerf_conv0_bf16_fwd(x.buf.data_ptr(), pk.cin, D, H, W, pk.get_bf16_conv0().data_ptr(), raw.data_ptr(),
-                                                 0 if part is None else part.data_ptr(), stream_ptr()), "conv0_bf16_fwd")
-            scale, shift, mean, invstd = _abn_stats(raw, D * H * W, self.conv0.bn, update_running=self.conv0.bn.training,
-                                                    partials=None if part is None else (part, nblk))
-            c0 = _Lazy(raw, scale, shift, (D, H, W, pk.cout), mean, invstd)
-            buf, ld = None, 0
-        elif isinstance(x, _BlockedCost):
-            pk = self.conv0._packed
-            if x.cin_pad != pk.cin_pad:
-                raise RuntimeError(f"CostRegNet: blocked cost volume has {x.cin_pad} channels, conv0 expects {pk.cin_pad}")
-            raw = torch.empty((D, H, W, pk.cout), device=x.buf.device, dtype=torch.float32)
-            lib = _lib.lib()
-            if self.conv0.bn.training and FUSED_ABN_STATS:
-                nblk = lib.mvsnerf_conv3d_c8_blocked_tiles(D, H, W)
-                part = torch.empty(nblk * 16, device=raw.device, dtype=torch.float32)
-                check(lib.mvsnerf_conv3d_c8_blocked_fwd_stats(x.buf.data_ptr(), pk.cin_pad, pk.cin, D, H, W, pk.get_c8().data_ptr(), raw.data_ptr(),
-                                                              part.data_ptr(), stream_ptr()), "conv3d_c8_blocked_fwd_stats")
-                partials = (part, nblk)
-            else:
-                check(lib.mvsnerf_conv3d_c8_blocked_fwd(x.buf.data_ptr(), pk.cin_pad, pk.cin, D, H, W, pk.get_c8().data_ptr(), raw.data_ptr(), stream_ptr()),
-                      "conv3d_c8_blocked_fwd")
-                partials = None
-            scale, shift, mean, invstd = _abn_stats(raw, D * H * W, self.conv0.bn, update_running=self.conv0.bn.training, partials=partials)
-            c0 = _Lazy(raw, scale, shift, (D, H, W, pk.cout), mean, invstd)
-            buf, ld = None, 0
-        else:
+        if not isinstance(x, _BlockedCost):
             buf, ld = _as_channel_last(x, self.conv0._packed_cin_pad())
             c0 = self.conv0.lazy(buf, (D, H, W, ld), ld)
-        with _layer_precision(ENCODER_PRECISION == "bf16" and BF16_LAYERS), _layers_f16x3(f16):     # use_amp: conv1 ... conv11 on the bf16 matrix cores as well (csrc/conv3d_bf16.hip)
+        else:
+            pk, bn, lib = self.conv0._packed, self.conv0.bn, _lib.lib()
+            want = bn.training and FUSED_ABN_STATS
+            if isinstance(x, _Conv0Done):          # conv0 already ran inside the guarded encode head (_plane_sweep, blocked="guarded")
+                raw, partials = x.buf, x.partials
+            elif isinstance(x, _BlockedCost16):
+                if x.n_ch != pk.cin:
+                    raise RuntimeError(f"CostRegNet: 16-bit cost volume has {x.n_ch} channels, conv0 expects {pk.cin}")
+                raw = torch.empty((D, H, W, pk.cout), device=x.buf.device, dtype=torch.float32)
+                pp, partials = _stats_part(want, 16, raw.device, lib.mvsnerf_conv0_bf16_tiles, D, H, W)      # the fp16x3 kernel has the same tiles / statistics slots
+                if isinstance(x, _BlockedCostH2):
+                    check(lib.mvsnerf_conv0_f16x3_fwd(x.buf.data_ptr(), pk.cin, D, H, W, pk.get_f16x3_conv0().data_ptr(), raw.data_ptr(), pp, stream_ptr()),
+                          "conv0_f16x3_fwd")
+                else:
+                    check(lib.mvsnerf_conv0_bf16_fwd(x.buf.data_ptr(), pk.cin, D, H, W, pk.get_bf16_conv0().data_ptr(), raw.data_ptr(), pp, stream_ptr()),
+                          "conv0_bf16_fwd")
+            else:
+                if x.cin_pad != pk.cin_pad:
+                    raise RuntimeError(f"CostRegNet: blocked cost volume has {x.cin_pad} channels, conv0 expects {pk.cin_pad}")
+                raw = torch.empty((D, H, W, pk.cout), device=x.buf.device, dtype=torch.float32)
+                pp, partials = _stats_part(want, 16, raw.device, lib.mvsnerf_conv3d_c8_blocked_tiles, D, H, W)
+                if partials is not None:
+                    check(lib.mvsnerf_conv3d_c8_blocked_fwd_stats(x.buf.data_ptr(), pk.cin_pad, pk.cin, D, H, W, pk.get_c8().data_ptr(), raw.data_ptr(),
+                                                                  pp, stream_ptr()), "conv3d_c8_blocked_fwd_stats")
+                else:
+                    check(lib.mvsnerf_conv3d_c8_blocked_fwd(x.buf.data_ptr(), pk.cin_pad, pk.cin, D, H, W, pk.get_c8().data_ptr(), raw.data_ptr(), stream_ptr()),
+                          "conv3d_c8_blocked_fwd")
+            c0 = _lazy_abn(raw, bn, partials)
+            buf, ld = None, 0
+        with _layer_precision(ENCODER_PRECISION == "bf16"), _layers_f16x3(f16):     # use_amp: conv1 ... conv11 on the bf16 matrix cores as well (csrc/conv3d_bf16.hip)
             # one guard_consume launch for the conv1 + conv2 pair when conv2 is sure to run guarded as well (same output size, both layers in batch-statistics
             # mode): a guard set by conv1 then also makes conv2 take its fp32 kernel, and conv2's sequence counts the event and re-arms
             _F16X3_CONSUME[0] = 0 if (f16 == "guarded" and self.conv1.bn.training and self.conv2.bn.training and FUSED_ABN_STATS) else 1
@@ -1070,7 +1023,7 @@ def _wgrad(G1, G2, A, X1, X2, B, ldx, g_dims, x_dims, stride, shape, sums=None):
     lib = _lib.lib()
     dev = (G1.x if isinstance(G1, _Lazy) else G1).device
     gw = torch.empty(shape, device=dev, dtype=torch.float32)
-    if _LAYER_BF16[0] and BF16_WGRAD:
+    if _LAYER_BF16[0]:
         n_parts = lib.mvsnerf_conv_wgrad_bf16_parts(A, B, g_dims[0], g_dims[1], g_dims[2], 3, 3, stride)
         if n_parts > 0:             # use_amp: bf16 operands, v_mfma_f32_16x16x32_bf16 (csrc/wgrad_bf16.hip)
             ws = torch.empty(lib.mvsnerf_conv_wgrad_bf16_workspace_floats(A, B, 3, 3) if sums is None else n_parts * gw.numel(), device=dev, dtype=torch.float32)
@@ -1151,7 +1104,7 @@ class _CostRegFunction(torch.autograd.Function):
     def forward(ctx, x, net, *params):
         (buf, ld), lz = net._run(x)
         ctx.net, ctx.buf, ctx.ld, ctx.lz, ctx.xshape = net, buf, ld, lz, tuple(x.shape)
-        ctx.layers_bf16 = ENCODER_PRECISION == "bf16" and BF16_LAYERS
+        ctx.layers_bf16 = ENCODER_PRECISION == "bf16"
         return _neural_volume(lz[0], lz[9])
 
     @staticmethod
@@ -1227,12 +1180,12 @@ class _BlockedCostH2(_BlockedCost16):
 
 class _Conv0Done(_BlockedCost):
     """Hand-off of the guarded encode head (mvsnerf_sweep_conv0_guarded_fwd): the plane sweep AND conv0 have run; `buf` is conv0's raw output
-    (D,H,W,8), `part` its InPlaceABN partial sums (or None in eval mode), `nblk` their slot count."""
-    __slots__ = ("part", "nblk")
+    (D,H,W,8), `partials` its InPlaceABN partial sums as _abn_stats takes them (None in eval mode)."""
+    __slots__ = ("partials",)
 
-    def __init__(self, raw, n_ch, dims, part, nblk):
+    def __init__(self, raw, n_ch, dims, partials):
         super().__init__(raw, n_ch, 0, dims)
-        self.part, self.nblk = part, nblk
+        self.partials = partials
 
 
 def _plane_sweep(imgs, feats, proj_mats, depth_values, pad, with_img, blocked=False, conv0=None):
@@ -1259,7 +1212,6 @@ def _plane_sweep(imgs, feats, proj_mats, depth_values, pad, with_img, blocked=Fa
     depth = depth_values[0].detach().contiguous()
     if blocked == "guarded":
         # no-grad default: two-piece fp16 sweep -> fp16x3 conv0 -> {fp32 sweep, fp32-MFMA conv0, statistics} predicated on the guard word, one call
-        from . import ops as _ops
         pk = conv0._packed
         if not with_img or pk.cin != n_ch or pk.cout != 8:
             raise RuntimeError(f"guarded encode head: conv0 expects {pk.cin} channels, the sweep produces {n_ch}")
@@ -1269,16 +1221,14 @@ def _plane_sweep(imgs, feats, proj_mats, depth_values, pad, with_img, blocked=Fa
         # planes (nb16 * 64 B per voxel), in stream order
         scratch = torch.empty(max(2 * nb16 * 16 * 2, CP * 4) * nvox, device=dev, dtype=torch.uint8)
         raw = torch.empty((D, Hp, Wp, 8), device=dev, dtype=torch.float32)
-        want = conv0.bn.training and FUSED_ABN_STATS
-        nblk = lib.mvsnerf_conv0_bf16_tiles(D, Hp, Wp)
-        part = torch.empty(nblk * 16, device=dev, dtype=torch.float32) if want else None
+        pp, partials = _stats_part(conv0.bn.training and FUSED_ABN_STATS, 16, dev, lib.mvsnerf_conv0_bf16_tiles, D, Hp, Wp)
         a = _lib.SweepConv0Args(
             feats_cl=feats_cl.data_ptr(), imgs_cl=imgs_cl_p, proj=dev_f32(proj, "proj_mats"), depth=dev_f32(depth, "depth_values"),
             V=V, H=H, W=W, D=D, pad=pad, CP=CP, masks=masks.data_ptr(), cost16x2=scratch.data_ptr(), cost32=scratch.data_ptr(),
-            w_f16x3=_get_f16x3_conv0(pk).data_ptr(), w_c8=pk.get_c8().data_ptr(), Cin=n_ch, out=raw.data_ptr(),
-            stats_part=0 if part is None else part.data_ptr(), guard=_ops.guard_words(dev).data_ptr())
+            w_f16x3=pk.get_f16x3_conv0().data_ptr(), w_c8=pk.get_c8().data_ptr(), Cin=n_ch, out=raw.data_ptr(),
+            stats_part=pp, guard=ops.guard_words(dev).data_ptr())
         check(lib.mvsnerf_sweep_conv0_guarded_fwd(ctypes.byref(a), stream_ptr()), "sweep_conv0_guarded_fwd")
-        return _Conv0Done(raw, n_ch, (D, Hp, Wp), part, nblk), masks.unsqueeze(0), (feats_cl, proj, depth, (V, C, H, W, D, pad, CP, n_ch))
+        return _Conv0Done(raw, n_ch, (D, Hp, Wp), partials), masks.unsqueeze(0), (feats_cl, proj, depth, (V, C, H, W, D, pad, CP, n_ch))
     if blocked == "fp16x2":
         nb16 = (n_ch + 15) // 16
         cost = torch.empty((2, nb16, D * Hp * Wp, 16), device=dev, dtype=torch.float16)
@@ -1354,7 +1304,7 @@ class _SweepRegFunction(torch.autograd.Function):
         cost, _, saved = _plane_sweep(imgs, feats, proj_mats, depth_values, pad, True, blocked="bf16" if ENCODER_PRECISION == "bf16" else True)
         _, lz = net._run(cost)
         ctx.net, ctx.cost, ctx.lz, ctx.saved = net, cost, lz, saved
-        ctx.layers_bf16 = ENCODER_PRECISION == "bf16" and BF16_LAYERS
+        ctx.layers_bf16 = ENCODER_PRECISION == "bf16"
         return _neural_volume(lz[0], lz[9])
 
     @staticmethod
@@ -1412,11 +1362,16 @@ class MVSNet(nn.Module):
         self.D = 128          # number of depth planes (hard-coded `D = 128` at models.py:914; settable here for config 1)
         self._t_vals = {}     # linspace(0, 1, D) per (device, dtype, D)
         self._pack_log = []   # weight re-layouts the last forward/backward asked for (see _PackBatch)
+        for pk in self._packed_convs():
+            pk.log = self._pack_log
+
+    def _packed_convs(self):
+        """The _PackedConv / _PackedConv2d of every layer."""
         for m in self.modules():
             for name in ("_packed", "_top_packed"):
                 pk = getattr(m, name, None)
                 if pk is not None:
-                    pk.log = self._pack_log
+                    yield pk
 
     def prepack(self):
         """Issue every weight re-layout the previous step needed (and that is stale now) in one launch."""
@@ -1427,13 +1382,8 @@ class MVSNet(nn.Module):
 
     def invalidate_packed(self):
         """Drop every re-packed convolution weight (see MVSNeRF.invalidate_packed: needed after writes through `.data`)."""
-        for m in self.modules():
-            pk = getattr(m, "_packed", None)
-            if pk is not None and hasattr(pk, "cache"):
-                pk.cache.clear()
-        tp = getattr(self.feature, "_top_packed", None)
-        if tp is not None:
-            tp.cache.clear()
+        for pk in self._packed_convs():
+            pk.cache.clear()
 
     def _depth_values(self, near_far, imgs, lindisp):
         """models.py:903-906.  The linear case with near_far on the device is ONE launch (mvsnerf_depth_values: the same four roundings as linspace / rsub / mul / mul /
@@ -1472,11 +1422,8 @@ class MVSNet(nn.Module):
         """reference models.py:895-932.  imgs (B,V,3,H,W) normalised; proj_mats (B,V,3,4); near_far (2,)."""
         B, V, _, H, W = imgs.shape
         self.prepack()
-        _NBT_DEFER[0] += 1
-        try:
+        with _defer_nbt():
             feats = self.feature(imgs.reshape(B * V, 3, H, W))
-        finally:
-            _NBT_DEFER[0] -= 1
         try:
             return self._forward_behind_features(imgs, feats, proj_mats, near_far, pad, return_color, lindisp)
         finally:
@@ -1487,13 +1434,13 @@ class MVSNet(nn.Module):
         feats_l = feats.view(B, V, *feats.shape[1:])
         depth_values = self._depth_values(near_far, imgs, lindisp).unsqueeze(0)
         # inference (no gradient anywhere): the cost volume goes to conv0 in channel blocks of 8 and never takes its NCDHW form
-        fast = (BLOCKED_COST and not return_color and not feats_l.requires_grad
+        fast = (not return_color and not feats_l.requires_grad
                 and not (torch.is_grad_enabled() and any(p.requires_grad for p in self.cost_reg_2.parameters()))
                 and (32 + 3 * V + 3) // 4 * 4 in _BLOCKED_CIN)
         if fast:
             cost, _ = self._sweep(imgs, feats_l, proj_mats, depth_values, pad, True, blocked=_inference_hand_off())
             return self.cost_reg_2(cost), feats_l, depth_values
-        if BLOCKED_COST and not return_color and torch.is_grad_enabled() and (32 + 3 * V + 3) // 4 * 4 in _BLOCKED_CIN and B == 1:
+        if not return_color and torch.is_grad_enabled() and (32 + 3 * V + 3) // 4 * 4 in _BLOCKED_CIN and B == 1:
             # training: the same blocked hand-off inside one autograd node
             vol = _SweepRegFunction.apply(feats_l, imgs, proj_mats, depth_values, pad, self.cost_reg_2, *_costreg_params(self.cost_reg_2))
             return vol, feats_l, depth_values
@@ -1526,10 +1473,7 @@ def bench_encode(rig, dev, pad, iters=6):
             torch.cuda.synchronize(); t1 = time.perf_counter()
             t_vals = torch.linspace(0.0, 1.0, steps=net.D, device=dev)
             dv = (nf[0] * (1.0 - t_vals) + nf[1] * t_vals).unsqueeze(0)
-            if BLOCKED_COST:
-                cost, _ = net._sweep(imgs, feats_l, proj, dv, pad, True, blocked=_inference_hand_off())   # what MVSNet.forward does without gradients
-            else:
-                cost, _ = net.build_volume_costvar_img(imgs, feats_l, proj, dv, pad=pad)
+            cost, _ = net._sweep(imgs, feats_l, proj, dv, pad, True, blocked=_inference_hand_off())   # what MVSNet.forward does without gradients
             torch.cuda.synchronize(); t2 = time.perf_counter()
             vol = net.cost_reg_2(cost)
             torch.cuda.synchronize(); t3 = time.perf_counter()
