@@ -309,6 +309,31 @@ size_t mvsnerf_frame_metrics_workspace_bytes(int K, int H, int W, int win_size);
 int mvsnerf_frame_metrics_fwd(const float* pred, const float* gt, const float* depth_pred, const float* depth_gt, int K, int H, int W,
                               int win_size, double data_range, double K1, double K2, double gt_scale, const double* thresholds,
                               double* out, void* workspace, void* stream);
+/* ---- fusing per-view volumes into one scene volume (train_mvs_nerf_fusion_finetuning_pl.py; csrc/fusion.hip) ----
+ * volume_fuse_splat: update_volume (:35-76) of P samples into a [D][H][W] voxel grid with every colliding write ACCUMULATED (the reference's
+ *   `vol[..., idx] += x` keeps one of them on a GPU): ndc[P][3] box coordinates (x -> W, y -> H, z -> D), feat[P][feat_stride] (C channels, C % 4 == 0,
+ *   4 <= C <= 40; other C: MVSNERF_EUNSUPPORTED), alpha[P].  Sums live in a caller-owned, caller-ZEROED int64 workspace of
+ *   volume_fuse_workspace_words(D, H, W, C) words (0: arguments refused), 16-byte aligned, that outlives the call:
+ *     [0] number of refused contributions   [1] log2 of the fixed-point scale (32, written by the first non-empty splat)   [2..7] unused
+ *     [8 + ((d H + h) W + w)(C + 4) ..] C feature sums, the alpha sum, the weight sum, 2 pad words.
+ *   Each contribution is the fp32 product rounded once to a multiple of 2^-32 (__double2ll_rn(prod * 2^32)) and added with a 64-bit integer atomic:
+ *   the words do not depend on the order of points, calls, views or ranks, and two workspaces add word by word.  A contribution with
+ *   |prod| >= 2^20, or not finite, is not added and counted in word 0 (2^11 maximal contributions fit a word); a caller must not use such sums.
+ *   The reference's arithmetic is kept: v = ndc / (1.0f / (dim - 1)), index truncated toward zero and kept when 0 <= idx < dim - 1 on all axes
+ *   (non-finite coordinates drop the point), local = v - floor(v), weight of shift (x, y, z) = (|local_x - x| |local_y - y|) |local_z - z| - the
+ *   OPPOSITE corner's - added at voxel (idx_z + x, idx_y + y, idx_x + z) - x and z swapped.  ray_weight of the reference's signature is unused there.
+ * volume_fuse_finish: :190-192 per voxel on the rounded sums - s = (float)(sum 2^-32), inv = 1.0f / ((float)(weight sum 2^-32) + 1e-6f), out = s * inv -
+ *   into feat_volume[C][D][H][W] and density_volume[D][H][W] (the reference's NCDHW order); untouched voxels are 0.  Word 0 is the caller's to check.
+ * ray_march_bbox: ray_marcher(bbox_3D=) (data/ray_utils.py:143-197) and the box coordinates of the fusion script (:263): rays[N][8], bbox[2][3],
+ *   t[S] = linspace(0, 1, S), jitter[N][S] = the caller's torch.rand draw (read when perturb > 0; NULL otherwise), -> z[N][S], pts[N][S][3] = o + d z,
+ *   ndc[N][S][3] = (pts - bbox[0]) / (bbox[1] - bbox[0]).  near / far = dda: inv = 1 / (d + 1e-6), max over axes of the slab minima, min of the maxima
+ *   (NaNs are handed on like torch.min / torch.max); a ray that misses the box keeps near > far. */
+size_t mvsnerf_volume_fuse_workspace_words(int D, int H, int W, int C);
+int mvsnerf_volume_fuse_splat(int D, int H, int W, int C, const float* ndc, int64_t P, const float* feat, int feat_stride,
+                              const float* alpha, void* workspace_zeroed, void* stream);
+int mvsnerf_volume_fuse_finish(int D, int H, int W, int C, const void* workspace, float* feat_volume, float* density_volume, void* stream);
+int mvsnerf_ray_march_bbox_fwd(const float* rays, const float* bbox, const float* t, const float* jitter, float perturb, int lindisp,
+                               int64_t N, int S, float* z, float* pts, float* ndc, void* stream);
 
 #ifdef __cplusplus
 }

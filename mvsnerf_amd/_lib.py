@@ -256,6 +256,10 @@ SIGNATURES = {
     "mvsnerf_render_rays_fwd": (_c_i, [ctypes.POINTER(RenderRaysArgs), _c_fp]),
     "mvsnerf_frame_metrics_workspace_bytes": (ctypes.c_size_t, [_c_i] * 4),
     "mvsnerf_frame_metrics_fwd": (_c_i, [_c_fp] * 4 + [_c_i] * 4 + [ctypes.c_double] * 4 + [ctypes.POINTER(ctypes.c_double), _c_fp, _c_fp, _c_fp]),
+    "mvsnerf_volume_fuse_workspace_words": (ctypes.c_size_t, [_c_i] * 4),
+    "mvsnerf_volume_fuse_splat": (_c_i, [_c_i] * 4 + [_c_fp, _c_l, _c_fp, _c_i, _c_fp, _c_fp, _c_fp]),
+    "mvsnerf_volume_fuse_finish": (_c_i, [_c_i] * 4 + [_c_fp] * 4),
+    "mvsnerf_ray_march_bbox_fwd": (_c_i, [_c_fp] * 4 + [ctypes.c_float, _c_i, _c_l, _c_i] + [_c_fp] * 4),
 }
 
 _lib = None

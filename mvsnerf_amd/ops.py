@@ -294,6 +294,30 @@ def ray_points(rays_o, rays_d, z_vals, w2c_ref=None, K_ref=None, near_far_ref=No
     return pts, ndc
 
 
+def ray_march_bbox(rays, bbox_3d, N_samples, lindisp=False, perturb=0.0, jitter=None, t=None):
+    """ray_marcher(rays, N_samples, lindisp, perturb, bbox_3D) (data/ray_utils.py:143-197) and the box coordinates of the fusion script
+    (train_mvs_nerf_fusion_finetuning_pl.py:263) in one launch: rays (N,8), bbox_3d (2,3) -> (pts (N,S,3), ndc (N,S,3), z (N,S)).
+    jitter: the (N,S) uniform draw of :190, required when perturb > 0; t: linspace(0, 1, N_samples) when the caller keeps one."""
+    _need_no_grad(rays, bbox_3d, op="ray_march_bbox")
+    if rays.dim() != 2 or rays.shape[1] != 8 or tuple(bbox_3d.shape) != (2, 3):
+        raise RuntimeError(f"ray_march_bbox: rays (N,8) and bbox_3d (2,3), got {tuple(rays.shape)} and {tuple(bbox_3d.shape)}")
+    N, S = rays.shape[0], int(N_samples)
+    dev = rays.device
+    if perturb > 0 and (jitter is None or tuple(jitter.shape) != (N, S)):
+        raise RuntimeError(f"ray_march_bbox: perturb > 0 needs the ({N}, {S}) uniform draw as jitter=")
+    if t is None:
+        t = torch.linspace(0, 1, S, device=dev)
+    if t.numel() != S:
+        raise RuntimeError(f"ray_march_bbox: t must hold {S} values")
+    c = _Keep()
+    z = torch.empty((N, S), device=dev, dtype=torch.float32)
+    pts, ndc = torch.empty((N, S, 3), device=dev, dtype=torch.float32), torch.empty((N, S, 3), device=dev, dtype=torch.float32)
+    check(_lib.lib().mvsnerf_ray_march_bbox_fwd(c(rays, "rays"), c(bbox_3d, "bbox_3d"), c(t, "t"), c(jitter, "jitter") if perturb > 0 else 0,
+                                                float(perturb), int(bool(lindisp)), N, S, z.data_ptr(), pts.data_ptr(), ndc.data_ptr(),
+                                                stream_ptr()), "ray_march_bbox_fwd")
+    return pts, ndc, z
+
+
 def sample_pdf(bins, weights, u):
     """data/ray_utils.py:96-139 with the uniform draws supplied: bins (N,nb), weights (N,nb-1), u (N,NI) -> (N,NI)."""
     _need_no_grad(bins, weights, u, op="sample_pdf")

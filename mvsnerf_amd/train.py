@@ -434,10 +434,25 @@ def default_args(**over):
 
 
 # ------------------------------------------------------------------ per-scene fine-tuning (reference train_mvs_nerf_finetuning_pl.py)
-def ray_marcher(rays, N_samples=64, lindisp=False, perturb=0):
-    """reference data/ray_utils.py:152-197 (bbox_3D=None): rays (N,8) = [o(3) | d(3) | near | far] -> z-sampled points.
-    Host-side torch like the reference (it owns the jitter draw)."""
+def dda(rays_o, rays_d, bbox_3D):
+    """reference data/ray_utils.py:143-150: entry and exit depth (N,1) of each ray against the axis-aligned box bbox_3D (2,3).  Host-side torch
+    (ops.ray_march_bbox holds the same arithmetic on the device)."""
+    inv = 1.0 / (rays_d + 1e-6)
+    t = torch.stack(((bbox_3D[:1] - rays_o) * inv, (bbox_3D[1:] - rays_o) * inv))
+    return (torch.max(torch.min(t, dim=0)[0], dim=-1, keepdim=True)[0],
+            torch.min(torch.max(t, dim=0)[0], dim=-1, keepdim=True)[0])
+
+
+def ray_marcher(rays, N_samples=64, lindisp=False, perturb=0, bbox_3D=None):
+    """reference data/ray_utils.py:152-197: rays (N,8) = [o(3) | d(3) | near | far] -> z-sampled points.
+    Host-side torch like the reference (it owns the jitter draw); with bbox_3D (2,3) near / far come from dda and the whole
+    march is one kernel behind the draw (ops.ray_march_bbox)."""
     n = rays.shape[0]
+    if bbox_3D is not None:
+        with torch.no_grad():
+            jitter = torch.rand((n, N_samples), device=rays.device) if perturb > 0 else None
+            pts, _, z = ops.ray_march_bbox(rays, bbox_3D, N_samples, lindisp=lindisp, perturb=perturb, jitter=jitter)
+        return pts, rays[:, 0:3], rays[:, 3:6], z
     rays_o, rays_d, near, far = rays[:, 0:3], rays[:, 3:6], rays[:, 6:7], rays[:, 7:8]
     steps = torch.linspace(0, 1, N_samples, device=rays.device)
     z = near * (1 - steps) + far * steps if not lindisp else 1 / (1 / near * (1 - steps) + 1 / far * steps)
@@ -710,3 +725,183 @@ class MVSSystemFinetune(_ModuleShim):
     def configure_optimizers(self):
         self.optimizer = _adam(self.grad_vars, self.args.lrate)
         return [self.optimizer], []
+
+
+# ------------------------------------------------------------------ fused-scene fine-tuning (reference train_mvs_nerf_fusion_finetuning_pl.py)
+def get_ray_directions(H, W, focal, center=None):
+    """reference data/ray_utils.py:12-29: camera-space directions (H,W,3) of every pixel, no half-pixel offset; focal = (fx, fy) or one number."""
+    f = torch.as_tensor(focal, dtype=torch.float32).reshape(-1)
+    fx, fy = (f[0], f[0]) if f.numel() == 1 else (f[0], f[1])
+    j, i = torch.meshgrid(torch.linspace(0, H - 1, H), torch.linspace(0, W - 1, W), indexing="ij")
+    cent = center if center is not None else [W / 2, H / 2]
+    return torch.stack([(i - cent[0]) / fx, (j - cent[1]) / fy, torch.ones_like(i)], -1)
+
+
+def get_rays(directions, c2w):
+    """reference data/ray_utils.py:32-53: (rays_o, rays_d), both (H*W, 3), un-normalised directions."""
+    rays_d = directions @ c2w[:3, :3].T
+    return c2w[:3, 3].expand(rays_d.shape).reshape(-1, 3), rays_d.reshape(-1, 3)
+
+
+class MVSSystemFusion(_ModuleShim):
+    """reference train_mvs_nerf_fusion_finetuning_pl.py:78-382: a scene that one triplet of source views cannot cover.  Every camera of the scene is
+    rendered at quarter resolution from its three nearest views and every sample's 20-channel feature row and alpha are splatted into ONE
+    canonical volume over a world-space box (`fuse_local_volumes`, fusion.VolumeFuser: colliding writes are accumulated, bit-reproducibly);
+    that volume becomes the learnable `RefVolume` (checkpoint key `volume.feat_volume`) which is fine-tuned and rendered with rays clipped to the
+    box, through the colour-volume ray march.
+    Left out: importance sampling (`args.N_importance > 0` raises - the reference's own calls, :259-260 and :312-313, hand `N_importance=` and
+    `density_volume=` to a ray_marcher without such parameters and raise TypeError as shipped) and `update_density_volume` with it."""
+
+    def __init__(self, args, views, bbox_3d, img_wh, focal, n_depth_planes=128):
+        """views: one entry per scene camera, (imgs (1,3,3,H,W) normalised, proj_mats (1,3,3,4), near_far (2,), pose_source dict, c2w (4,4) | (3,4)) -
+        what `dataset.read_source_views(pair_idx=...)` returns for the camera's three nearest views (:143), then the camera's own pose.
+        bbox_3d (2,3): the scene box; img_wh = (W, H) and focal of the full-resolution images (:130-132)."""
+        super().__init__()
+        if int(getattr(args, "N_importance", 0) or 0) > 0:
+            raise NotImplementedError("MVSSystemFusion: args.N_importance > 0 - the reference's fusion script cannot run it either (its ray_marcher "
+                                      "takes neither N_importance= nor density_volume=, data/ray_utils.py:152-156)")
+        if int(args.pad) % 4:
+            raise ValueError(f"MVSSystemFusion: args.pad must be a multiple of 4 (the quarter-resolution march pads by pad / 4), got {args.pad}")
+        self.args = args
+        self.args.feat_dim = 8 + 12                                       # :82
+        if not hasattr(args, "fusion_N_samples"):
+            args.fusion_N_samples = 128                                   # :159, a literal there
+        if not hasattr(args, "fusion_volume_dim"):
+            args.fusion_volume_dim = [128, 128, 128]                      # :101
+        self.volume_dim = [int(v) for v in args.fusion_volume_dim]
+        self.idx = 0
+        kw_train, _, _, self.grad_vars = create_nerf_mvs(args, use_mvs=True, dir_embedder=False, pts_embedder=True)      # :89
+        for k in ("N_samples", "ndc", "lindisp"):
+            kw_train.pop(k, None)
+        self.render_kwargs_train = kw_train
+        self.MVSNet = kw_train.pop("network_mvs")
+        self.MVSNet.D = n_depth_planes
+        self.network_fn = kw_train["network_fn"]
+        self.views = list(views)
+        self.img_wh, self.focal = (int(img_wh[0]), int(img_wh[1])), focal
+        self.register_buffer("bbox_3d", torch.as_tensor(bbox_3d, dtype=torch.float32).reshape(2, 3).clone(), persistent=False)
+        self.volume = None
+        self._allreduce = None
+
+    # -- fusion ------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def fuse_local_volumes(self):
+        """:117-203.  Call once the module is on its device and the weights are loaded.  With torch.distributed initialised the views are split over
+        the ranks in contiguous ranges and the integer accumulators are all-reduced: every rank ends with the same bits as one process."""
+        import copy
+        from .fusion import VolumeFuser
+        from .models import RefVolume
+        args = copy.copy(self.args)
+        args.use_color_volume = False                                     # :100
+        dev = self.bbox_3d.device
+        fuser = VolumeFuser(self.volume_dim, args.feat_dim, dev)
+        W, H = self.img_wh
+        H, W = H // 4, W // 4                                             # :131
+        directions = get_ray_directions(H, W, torch.as_tensor(self.focal, dtype=torch.float32) / 4.0).to(dev)      # :132
+        box_lo, box_size = self.bbox_3d[0].view(1, 1, 3), (self.bbox_3d[1] - self.bbox_3d[0]).view(1, 1, 3)
+        world, rank = D.world_rank()
+        lo, hi = D.shard_range(len(self.views), world, rank)
+        self.MVSNet.train()                                               # batch-statistics ABN, as every encode of the reference
+        for i, (imgs, proj_mats, near_far, pose, c2w) in enumerate(self.views):
+            if i == 0:
+                self.pose_source_ref = {k: v.to(dev) for k, v in pose.items()}       # :146-147
+                self.imgs_ref = MVSSystem.unpreprocess(imgs.to(dev))
+            if not lo <= i < hi:
+                continue
+            imgs, near_far = imgs.to(dev), near_far.to(dev, torch.float32)
+            pose = {k: v.to(dev) for k, v in pose.items()}
+            volume_feature, _, _ = self.MVSNet(imgs, proj_mats.to(dev), near_far, pad=args.pad)       # :144
+            imgs = MVSSystem.unpreprocess(imgs)
+            rays_o, rays_d = get_rays(directions, torch.as_tensor(c2w, dtype=torch.float32).to(dev))            # :149
+            rays = torch.cat([rays_o, rays_d, near_far[0] * torch.ones_like(rays_o[:, :1]), near_far[1] * torch.ones_like(rays_o[:, :1])], 1)
+            intrinsic_ref = pose["intrinsics"][0].clone()
+            intrinsic_ref[:2] *= 0.25                                     # :164
+            for c0 in range(0, rays.shape[0], args.chunk):                # :156
+                pts, ro, rd, z = ray_marcher(rays[c0:c0 + args.chunk], N_samples=args.fusion_N_samples)
+                pts, ndc = ops.ray_points(ro, rd, z, pose["w2cs"][0], intrinsic_ref, near_far, ref_hw=(H, W), pad=args.pad // 4)     # :162-168
+                _, ray_feat, _, _, ray_alpha, _ = rendering(args, pose, pts, ndc, z, ro, rd.contiguous(), volume_feature, imgs,
+                                                            **self.render_kwargs_train)                      # :171-174
+                fuser.add(ray_feat, (pts - box_lo) / box_size, ray_alpha)                                     # :176-177
+        fuser.all_reduce()
+        feat_volume, self.density_volume = fuser.finish()                 # :190-192, :199
+        self.volume = RefVolume(feat_volume).to(dev)                      # :200
+        self.grad_vars = [p for p in self.network_fn.parameters()] + list(self.volume.parameters())      # :105 (MVSNet is not stepped: no gradient reaches it)
+        self.args.use_color_volume = True                                 # :106
+        return fuser
+
+    def _need_volume(self):
+        if self.volume is None:
+            raise RuntimeError("MVSSystemFusion: call fuse_local_volumes() first (after .to(device) and loading the weights)")
+
+    # -- the step ----------------------------------------------------------------------------------
+    def training_step(self, batch, batch_nb):
+        """:251-291.  batch = {'rays': (1,B,8), 'rgbs': (1,B,3)}."""
+        self._need_volume()
+        args = self.args
+        if int(getattr(args, "N_importance", 0) or 0) > 0:
+            raise NotImplementedError("MVSSystemFusion: args.N_importance > 0 is not supported (see the class docstring)")
+        dev = self.bbox_3d.device
+        rays, target = batch["rays"].reshape(-1, 8).to(dev, torch.float32), batch["rgbs"].reshape(-1, 3).to(dev, torch.float32)
+        with torch.no_grad():                                             # :259-263
+            jitter = torch.rand((rays.shape[0], args.N_samples), device=dev) if args.perturb > 0 else None
+            pts, ndc, z_vals = ops.ray_march_bbox(rays, self.bbox_3d, args.N_samples, lindisp=getattr(args, "use_disp", False),
+                                                  perturb=args.perturb, jitter=jitter)
+        with ops.mlp_precision("bf16" if getattr(args, "use_amp", False) else ops.MLP_PRECISION):
+            rgbs, _, _, _, _, _ = rendering(args, self.pose_source_ref, pts, ndc, z_vals, rays[:, 0:3], rays[:, 3:6].contiguous(), self.volume,
+                                            self.imgs_ref, **self.render_kwargs_train)                       # :266-267
+        img_loss = img2mse(rgbs, target)
+        with torch.no_grad():
+            self.log("train/loss", img_loss, prog_bar=True)
+            self.log("train/img_mse_loss", img_loss)
+            self.log("train/PSNR", mse2psnr2(img_loss), prog_bar=True)
+        return {"loss": img_loss}
+
+    # -- rendering the fused scene -----------------------------------------------------------------
+    @torch.no_grad()
+    def render_rays(self, rays, chunk=None, batch_rays=65536):
+        """The rendering part of validation_step (:307-324) for rays (N,8): per chunk ops.ray_march_bbox -> rendering, the chunks of up to batch_rays
+        rays issued as one renderer.rendering_batched call; chunk ranges are sharded over the ranks as in MVSSystemFinetune.render_rays.
+        Returns (rgb (N,3), depth (N,))."""
+        from .renderer import rendering_batched
+        self._need_volume()
+        args = self.args
+        chunk = int(chunk or args.chunk)
+        dev = self.bbox_3d.device
+        rays = rays.reshape(-1, 8).to(dev, torch.float32).contiguous()
+        N = rays.shape[0]
+        if N == 0:
+            return torch.empty((0, 3), device=dev), torch.empty((0,), device=dev)
+        n_chunks = (N + chunk - 1) // chunk
+        world, rank = D.world_rank()
+        lo, hi = D.shard_range(n_chunks, world, rank)
+        t = torch.linspace(0, 1, args.N_samples, device=dev)
+        group = max(1, int(batch_rays) // chunk)
+        rows = []
+        for g0 in range(lo, hi, group):
+            batches = []
+            for idx in range(g0, min(g0 + group, hi)):
+                r = rays[idx * chunk:(idx + 1) * chunk]
+                pts, ndc, z = ops.ray_march_bbox(r, self.bbox_3d, args.N_samples, lindisp=getattr(args, "use_disp", False), t=t)
+                batches.append((pts, ndc, z, r[:, 0:3], r[:, 3:6].contiguous()))
+            outs = rendering_batched(args, self.pose_source_ref, batches, self.volume, self.imgs_ref, **self.render_kwargs_train)
+            rows += [torch.cat([o[0], o[3][:, None]], 1) for o in outs]
+        return D._assemble_frame(torch.cat(rows, 0) if rows else None, 1, N, chunk, n_chunks, world, None, dev)
+
+    @torch.no_grad()
+    def validation_step(self, batch, batch_nb):
+        """:294-343.  batch = {'rays': (1,N,8) | (N,8), 'rgbs': (1,H,W,3) | (H,W,3) | (N,3)} -> {'val_psnr_all'}; the image grids and the PNG dump
+        are left out as in the other systems (`last_val_images` keeps what they show)."""
+        from .utils import mse2psnr
+        img = batch["rgbs"].to(torch.float32).cpu()
+        img = img[0] if img.dim() == 4 else img
+        rgb, depth = self.render_rays(batch["rays"].reshape(-1, 8))
+        rgb = torch.clamp(rgb.cpu().reshape(img.shape), 0, 1)            # :327
+        depth = depth.cpu().reshape(img.shape[:-1])
+        img_err_abs = (rgb - img).abs()
+        self.idx += 1
+        self.last_val_images = {"rgb": rgb, "depth": depth, "err": img_err_abs}
+        return {"val_psnr_all": mse2psnr(torch.mean(img_err_abs ** 2))}  # :330
+
+    validation_epoch_end = MVSSystemFinetune.validation_epoch_end
+    save_ckpt = MVSSystemFinetune.save_ckpt                               # :370-382, the fine-tuning script's keys
+    configure_optimizers = MVSSystemFinetune.configure_optimizers
