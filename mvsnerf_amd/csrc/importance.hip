@@ -8,6 +8,7 @@
 // integer+fp32 work: no MFMA.
 #include "common.h"
 #include "march.h"
+#include "ray_dev.h"
 
 constexpr int IMP_MAX = 512;     // max samples / bins / importance samples per ray held in LDS
 
@@ -190,20 +191,6 @@ extern "C" int mvsnerf_ray_marcher_fine_fwd(const float* density, int D, int H, 
     return MVSNERF_OK;
 }
 
-// The coarse depths of ray_marcher (data/ray_utils.py:152-197 without jitter) as train.ray_marcher forms them with torch: (1 - t) rounded, two
-// rounded products, one sum; lindisp: the reciprocals are IEEE divisions like torch's.
-__device__ __forceinline__ float coarse_depth(float near, float far, float t, int lindisp)
-{
-#pragma clang fp contract(off)
-    const float omt = 1.0f - t;
-    if (lindisp) {
-        const float a = (1.0f / near) * omt, b = (1.0f / far) * t;
-        return 1.0f / (a + b);
-    }
-    const float a = near * omt, b = far * t;
-    return a + b;
-}
-
 // pts = o + d*z and their reference-view NDC coordinates (get_ndc_coordinate, utils.py:112-146), one thread per sample.
 // rays_o: [N][o_stride], or [1][3] broadcast when o_stride == 0; rays_d: [N][d_stride].
 // tvals != NULL: the depths are not read but FORMED here from the rays' own (near, far) = near_far_rays[n * nf_stride + 0 / 1] and t = tvals[s]
@@ -229,7 +216,7 @@ __global__ __launch_bounds__(256) void ray_points_kernel(const float* __restrict
     } else {
         z = z_vals[t];
     }
-    const float px = o[0] + d[0] * z, py = o[1] + d[1] * z, pz = o[2] + d[2] * z;      // o + d*z
+    const float px = ray_point(o[0], d[0], z), py = ray_point(o[1], d[1], z), pz = ray_point(o[2], d[2], z);      // o + d*z (ray_dev.h)
     pts[t * 3 + 0] = px; pts[t * 3 + 1] = py; pts[t * 3 + 2] = pz;
     if (!ndc) return;
     const float near_ref = nf_ref[0], far_ref = nf_ref[1];

@@ -6,6 +6,7 @@
 // walk depth (the `_zfast` kernels below; sample_dev.h).  Same arithmetic, same bits.
 #include "common.h"
 #include "sample_dev.h"
+#include "ray_dev.h"
 #include <type_traits>
 
 // ---------------------------------------------------------------------------------------------
@@ -780,18 +781,15 @@ __global__ __launch_bounds__(256) void raygen_kernel(RayGenArgs a)
     const float dx = fmaf(1.0f, a.c2w[2], fmaf(cyd, a.c2w[1], cxd * a.c2w[0]));
     const float dy = fmaf(1.0f, a.c2w[6], fmaf(cyd, a.c2w[5], cxd * a.c2w[4]));
     const float dz = fmaf(1.0f, a.c2w[10], fmaf(cyd, a.c2w[9], cxd * a.c2w[8]));
-    auto zplain = [&](int i) {
-        const float tv = linspace01(i, a.S);
-        return a.lindisp ? 1.0f / (1.0f / near * (1.0f - tv) + 1.0f / far * tv) : near * (1.0f - tv) + far * tv;
-    };
+    auto zplain = [&](int i) { return coarse_depth(near, far, linspace01(i, a.S), a.lindisp); };      // ray_dev.h: torch's roundings, shared with ray_points_kernel
     float z = a.depth_mode == 2 ? a.z_map[pix_off] : zplain(s);           // :200: one candidate per ray, no stratification
     if (a.t_rand && a.depth_mode != 2) {
         const float lo = s == 0 ? z : 0.5f * (z + zplain(s - 1));
         const float up = s == a.S - 1 ? z : 0.5f * (zplain(s + 1) + z);
-        z = lo + (up - lo) * a.t_rand[t];
+        z = jittered_depth(lo, up, a.t_rand[t]);
     }
     const float ox = a.c2w[3], oy = a.c2w[7], oz = a.c2w[11];
-    const float px = ox + z * dx, py = oy + z * dy, pz = oz + z * dz;
+    const float px = ray_point(ox, dx, z), py = ray_point(oy, dy, z), pz = ray_point(oz, dz, z);
     // reference camera: R x + t, K p, /z, /(W-1,H-1), depth normalisation, pad re-scale
     const float cx = fmaf(pz, a.w2c[2], fmaf(py, a.w2c[1], px * a.w2c[0])) + a.w2c[3];
     const float cy = fmaf(pz, a.w2c[6], fmaf(py, a.w2c[5], px * a.w2c[4])) + a.w2c[7];

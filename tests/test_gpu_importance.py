@@ -84,7 +84,8 @@ def test_ray_marcher_fine_vs_oracle(N, S, NI, scale):
 
 
 def test_sample_pdf_properties():
-    """Size-independent properties: samples lie within [bins[0], bins[-1]], are monotone in u, and u = cdf knots reproduce the bins."""
+    """Size-independent properties: samples lie within [bins[0], bins[-1]] and are monotone in u.  That u = cdf knots reproduce the bins is asserted bit for
+    bit on the exact family of test_gpu_importance_f64.py::test_sample_pdf_exact_family_bit_for_bit (random weights have no fp32 u that equals a knot)."""
     from mvsnerf_amd import ops
     g = torch.Generator().manual_seed(1)
     N, nb, NI = 257, 63, 128
