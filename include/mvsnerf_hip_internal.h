@@ -209,6 +209,23 @@ int mvsnerf_mlp_pack_fold(const float* const w[11], const float* const b[11], in
  * v0 and v2 alike; the saved-activation format keeps feature operands 16..19 of an F > 32 row in slots 2..5 of its direction block,
  * csrc/mlp_layout.h S_FV_HI). */
 int mvsnerf_mlp_pack_fold_variant(const float* const w[11], const float* const b[11], int F, int variant, float* packed, void* stream);
+/* ---- netwidth 256 (csrc/mlp_wide.hip, csrc/mlp_wide_layout.h): the no-grad fp32 forward of the same two networks at W = 256 ----
+ * netdepth 6, skips [4], multires 10, raw 3-d view directions as above; the 11 tensors have the shapes of the reference's W = 256 network
+ * (pts_linears 256x63, 4 x 256x256, 256x319; pts_bias 256xF; feature_linear 256x256; alpha_linear 1x256; views_linears.0 128x259; rgb_linear
+ * 3x128), in the order of mvsnerf_mlp_pack.
+ * mvsnerf_mlp_wide_packed_floats(F, width): floats of the packed buffer; 0 when unsupported: width != 256, F odd, F < 4 or F > 40.
+ * mvsnerf_mlp_pack_wide: variant as for mvsnerf_mlp_pack_fold_variant (0 = v0, 1 = v2; the buffer carries it, no fold tail exists at this width).
+ * mvsnerf_mlp_fwd_wide: the arguments and results of mvsnerf_mlp_fwd from `ndc` on (strided inputs, direction of point p = dirs[(p / S) *
+ *   dirs_stride], alpha_only: raw[P][1], un-clamped on a v2 buffer).  One 256-thread workgroup per 128 points, 139 KB of LDS, one workgroup
+ *   per CU.  ONLY a buffer written by mvsnerf_mlp_pack_wide may be passed, and such a buffer to no other entry: the 128-wide kernels would read
+ *   it with their own offsets.  No training forward, backward, 16-bit, ray-march or whole-frame entry exists at this width.
+ * Return codes as everywhere: -1 invalid argument, -2 unsupported shape, -3 misaligned pointer (packed, raw: 16 bytes).  Nothing is allocated. */
+size_t mvsnerf_mlp_wide_packed_floats(int F, int width);
+int mvsnerf_mlp_pack_wide(const float* const w[11], const float* const b[11], int F, int width, int variant, float* packed, void* stream);
+int mvsnerf_mlp_fwd_wide(const float* packed, int F, int width,
+                         const float* ndc, int ndc_stride, const float* feat, int feat_stride,
+                         const float* dirs, int dirs_stride, int64_t N, int S, int alpha_only,
+                         float* raw, void* stream);
 /* (described in mvsnerf_hip.h: "---- Guarded 16-bit sequences (ABI v10) ---- ...") */
 typedef struct {
     const float* feats_cl; const float* imgs_cl;   /* [V][H][W][32], [V][H][W][4] as for mvsnerf_planesweep_costvar_fwd (with_img = 1) */

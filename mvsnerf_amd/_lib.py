@@ -214,6 +214,9 @@ SIGNATURES = {
     "mvsnerf_mlp_packed_fold_floats": (ctypes.c_size_t, [_c_i]),
     "mvsnerf_mlp_pack_fold": (_c_i, [ctypes.POINTER(_c_fp), ctypes.POINTER(_c_fp), _c_i, _c_fp, _c_fp]),
     "mvsnerf_mlp_pack_fold_variant": (_c_i, [ctypes.POINTER(_c_fp), ctypes.POINTER(_c_fp), _c_i, _c_i, _c_fp, _c_fp]),
+    "mvsnerf_mlp_wide_packed_floats": (ctypes.c_size_t, [_c_i, _c_i]),
+    "mvsnerf_mlp_pack_wide": (_c_i, [ctypes.POINTER(_c_fp), ctypes.POINTER(_c_fp), _c_i, _c_i, _c_i, _c_fp, _c_fp]),
+    "mvsnerf_mlp_fwd_wide": (_c_i, [_c_fp, _c_i, _c_i, _c_fp, _c_i, _c_fp, _c_i, _c_fp, _c_i, _c_l, _c_i, _c_i, _c_fp, _c_fp]),
     "mvsnerf_mlp_fwd": (_c_i, [_c_fp, _c_i, _c_fp, _c_i, _c_fp, _c_i, _c_fp, _c_i, _c_l, _c_i, _c_i, _c_fp, _c_fp]),
     "mvsnerf_mlp_fwd_census": (_c_i, [_c_fp, _c_i, _c_fp, _c_i, _c_fp, _c_i, _c_fp, _c_i, _c_l, _c_i, _c_i, _c_fp, _c_fp, _c_fp]),
     "mvsnerf_mlp_packed_split_elems": (ctypes.c_size_t, [_c_i, _c_i]),

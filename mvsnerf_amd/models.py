@@ -59,7 +59,8 @@ class _RendererMLP(nn.Module):
     A subclass names the network variant the kernels run (`_variant`, the `variant` argument of mvsnerf_mlp_pack_fold_variant):
         0  h_i = relu(pts_linears.i(h) * bias)   Renderer_ours   (net_type 'v0')
         1  h_i = relu(pts_linears.i(h) + bias)   Renderer_linear (net_type 'v2'; forward_alpha without the ReLU)
-    with bias = pts_bias(feat).
+    with bias = pts_bias(feat).  netwidth 128 runs every kernel; netwidth 256 (`wide`) runs the no-grad fp32 queries below on csrc/mlp_wide.hip and
+    refuses the rest by name (16-bit modes, training, the fused ray march).
     forward(x) / forward_alpha(x) take the reference's concatenated rows
         x = [embed(pts)(63) | feat(F) | dir(3)]      (forward_alpha: no dir)
     and run the fused HIP kernel on them in place: the kernel reads pts from x[..., :3] (the embedding's
@@ -95,21 +96,33 @@ class _RendererMLP(nn.Module):
         F = self.in_ch_feat if feat_dim is None else feat_dim
         if F != self.in_ch_feat:
             raise RuntimeError(f"feat_dim {F} does not match the network's input_ch_feat {self.in_ch_feat}")
-        if self.D != 6 or self.W != 128 or self.skips != [4] or self.in_ch_pts != 63 or self.in_ch_views != 3:
+        if self.D != 6 or self.W not in (128, ops.WIDE_WIDTH) or self.skips != [4] or self.in_ch_pts != 63 or self.in_ch_views != 3:
             raise NotImplementedError(
-                "the HIP MLP kernel is specialised for netdepth=6, netwidth=128, skips=[4], multires=10, raw view dirs "
+                "the HIP MLP kernels are specialised for netdepth=6, netwidth=128 or 256, skips=[4], multires=10, raw view dirs "
                 f"(got D={self.D}, W={self.W}, skips={self.skips}, in_ch_pts={self.in_ch_pts}, in_ch_views={self.in_ch_views})")
         self.need_fp32_mode(ops.MLP_PRECISION)
         key = self._weights_key()
         if self._packed is None or key != self._packed_key:
             lins = self._linears()
-            self._packed = ops.mlp_pack([l.weight.detach() for l in lins], [l.bias.detach() for l in lins], F, variant=self._variant)
+            ws, bs = [l.weight.detach() for l in lins], [l.bias.detach() for l in lins]
+            # netwidth 256: the wide kernel's buffer (an ops.WidePacked, which only ops.mlp_forward takes), same cache policy
+            self._packed = ops.mlp_pack_wide(ws, bs, F, self.W, self._variant) if self.wide else ops.mlp_pack(ws, bs, F, variant=self._variant)
             self._packed_key = key
         return self._packed
 
+    @property
+    def wide(self):
+        """netwidth 256: no-grad fp32 queries on csrc/mlp_wide.hip; no fused ray march, no whole-frame entry, no training, no 16-bit kernel."""
+        return self.W == ops.WIDE_WIDTH
+
     def need_fp32_mode(self, mode):
         """The additive network runs on the fp32 kernels only (the 16-bit kernels' exponent management assumes the multiplicative form): under
-        "auto" it resolves to them, an explicit 16-bit mode - what use_amp sets - is refused before anything is packed or launched."""
+        "auto" it resolves to them, an explicit 16-bit mode - what use_amp sets - is refused before anything is packed or launched.
+        A netwidth-256 network (either variant) has the same policy: its one kernel is fp32."""
+        if self.wide and mode not in ("auto", "fp32"):
+            raise NotImplementedError(
+                f"netwidth {self.W} runs on the fp32 wide MLP kernel only: mlp precision {mode!r} (use_amp sets 'bf16') is built for netwidth 128; "
+                "use ops.set_mlp_precision('fp32') or 'auto'")
         if self._variant and mode not in ("auto", "fp32"):
             raise NotImplementedError(
                 f"net_type v2 ({type(self).__name__}) runs on the fp32 MLP kernels only: mlp precision {mode!r} (use_amp sets 'bf16') is built "
@@ -150,6 +163,7 @@ class _RendererMLP(nn.Module):
         """bf16 fragment-ordered weights for the opt-in bf16-MFMA kernel (same cache policy as packed()).
         fresh: packed() has just been called for these weights (same host call) - its key is current."""
         F = self.in_ch_feat if feat_dim is None else feat_dim
+        self._need_narrow("packed_bf16")
         if not fresh:
             self.packed(F)                  # validates the architecture and keeps the fp32 vectors current
         if getattr(self, "_packed_b", None) is None or self._packed_b_key != self._packed_key:
@@ -160,6 +174,7 @@ class _RendererMLP(nn.Module):
     def packed_split(self, feat_dim=None, n_split=3, fresh=False):
         """(split weight planes, n_split) for the bf16x3 / bf16x6 / fp16x3 kernels (same cache policy as packed(); fresh: see packed_bf16)."""
         F = self.in_ch_feat if feat_dim is None else feat_dim
+        self._need_narrow("packed_split")
         if not fresh:
             self.packed(F)
         cache = getattr(self, "_packed_s", None)
@@ -167,10 +182,14 @@ class _RendererMLP(nn.Module):
             self._packed_s = ((self._packed_key, n_split), ops.mlp_pack_split([l.weight.detach() for l in self._linears()], F, n_split))
         return self._packed_s[1], n_split
 
+    def _need_narrow(self, what):
+        if self.wide:
+            raise NotImplementedError(f"{type(self).__name__}.{what}: the 16-bit MLP kernels are built for netwidth 128, this network has netwidth {self.W}")
+
     def packed_alt(self, feat_dim=None, fresh=False):
         """Keyword arguments selecting the MLP kernel of ops.raymarch / ops.render_pixels / ops.mlp_forward for the current ops.MLP_PRECISION."""
         mode = ops.inference_mlp_mode()
-        if self._variant:            # net_type v2: "auto" resolves to the fp32 kernel, a 16-bit mode raises
+        if self._variant or self.wide:            # net_type v2, netwidth 256: "auto" resolves to the fp32 kernel, a 16-bit mode raises
             self.need_fp32_mode(ops.MLP_PRECISION)
             return {}
         if mode == "bf16":
@@ -246,6 +265,10 @@ class MVSNeRF(nn.Module):
                 "v1 (Renderer_attention) is dead code in the reference (SURVEY.md 2)")
         self.nerf = _NET_TYPES[net_type](D=D, W=W, input_ch_feat=input_ch_feat, input_ch=input_ch_pts, output_ch=4, skips=skips,
                                   input_ch_views=input_ch_views, use_viewdirs=True)
+
+    @property
+    def wide(self):
+        return self.nerf.wide
 
     def packed(self, feat_dim=None):
         return self.nerf.packed(feat_dim)

@@ -371,6 +371,65 @@ def mlp_pack(weights, biases, F, variant=0):
     return packed
 
 
+WIDE_WIDTH = 256            # the one width of csrc/mlp_wide.hip
+
+
+class WidePacked:
+    """The packed weights of a netwidth-256 network (mlp_pack_wide): the buffer of csrc/mlp_wide_layout.h with the width, feat_dim and variant it
+    was packed for.  Deliberately not a tensor: only ops.mlp_forward takes it; every other entry that takes a packed MLP buffer hands its
+    pointer to a 128-wide kernel, which would read the buffer with its own offsets, and refuses it instead (_need_narrow)."""
+    __slots__ = ("buffer", "width", "F", "variant")
+
+    def __init__(self, buffer, width, F, variant):
+        self.buffer, self.width, self.F, self.variant = buffer, int(width), int(F), int(variant)
+
+    @property
+    def device(self):
+        return self.buffer.device
+
+    def __repr__(self):
+        return f"WidePacked(width={self.width}, F={self.F}, variant={self.variant}, device={self.buffer.device})"
+
+
+def _wide_refusal(op):
+    return NotImplementedError(
+        f"{op}: netwidth {WIDE_WIDTH} runs on the no-grad fp32 network query only (ops.mlp_forward: MVSNeRF.query / forward / forward_alpha, "
+        "renderer.rendering's piecewise path); the fused ray march, the whole-frame entries, training and the 16-bit kernels are built for "
+        "netwidth 128")
+
+
+def _need_narrow(packed, op):
+    """Refuse a netwidth-256 buffer - or the 11 weights of such a network - before anything is launched."""
+    if isinstance(packed, WidePacked):
+        raise _wide_refusal(op)
+    if isinstance(packed, (list, tuple)) and len(packed) and torch.is_tensor(packed[0]) and packed[0].shape[0] != 128:
+        raise _wide_refusal(op)
+
+
+def mlp_pack_wide(weights, biases, F, width=WIDE_WIDTH, variant=0):
+    """mlp_pack for a netwidth-256 network (mvsnerf_mlp_pack_wide): 11 contiguous fp32 GPU tensors each in MLP_ORDER -> WidePacked."""
+    if variant not in (0, 1):
+        raise ValueError(f"mlp_pack_wide: variant must be 0 (Renderer_ours) or 1 (Renderer_linear), got {variant!r}")
+    W = int(width)
+    if W != WIDE_WIDTH:
+        raise NotImplementedError(f"mlp_pack_wide: netwidth {W}: the wide kernel is built for netwidth {WIDE_WIDTH} (and mlp_pack for 128)")
+    expect = [(W, 63)] + [(W, W)] * 4 + [(W, W + 63), (W, F), (W, W), (1, W), (W // 2, W + 3), (3, W // 2)]
+    if len(weights) != 11 or len(biases) != 11:
+        raise RuntimeError("mlp_pack_wide: 11 weights and 11 biases in ops.MLP_ORDER")
+    for name, w, b, e in zip(MLP_ORDER, weights, biases, expect):
+        if tuple(w.shape) != e or tuple(b.shape) != (e[0],):
+            raise RuntimeError(f"mlp_pack_wide: {name} has weight {tuple(w.shape)}, bias {tuple(b.shape)}; netwidth {W} needs {e}, {(e[0],)} "
+                               "(netdepth 6, skips [4], multires 10, raw 3-d view dirs)")
+    n = _lib.lib().mvsnerf_mlp_wide_packed_floats(F, W)
+    if n == 0:
+        raise RuntimeError(f"mlp_pack_wide: feat_dim {F} unsupported (must be even, 4 <= F <= 40)")
+    packed = torch.empty(n, device=weights[0].device, dtype=torch.float32)
+    wp = (ctypes.c_void_p * 11)(*[dev_f32(w, "weight") for w in weights])
+    bp = (ctypes.c_void_p * 11)(*[dev_f32(b, "bias") for b in biases])
+    check(_lib.lib().mvsnerf_mlp_pack_wide(wp, bp, F, W, int(variant), packed.data_ptr(), stream_ptr()), "mlp_pack_wide")
+    return WidePacked(packed, W, F, variant)
+
+
 MLP_PRECISION = "auto"      # "auto" (default) | "fp32" | "bf16" | "bf16x3" | "bf16x6" | "fp16x3"; see set_mlp_precision
 N_SPLIT = {"bf16x3": 2, "bf16x6": 3, "fp16x3": 18}      # n_split of mvsnerf_mlp_*_split; 18 = MVSNERF_SPLIT_FP16 (include/mvsnerf_hip.h)
 _MODES = ("auto", "fp32", "bf16", "bf16x3", "bf16x6", "fp16x3")
@@ -473,10 +532,18 @@ def mlp_forward(packed, F, ndc_ptr, ndc_stride, feat_ptr, feat_stride, dirs_ptr,
                 packed_bf16=None, packed_split=None, guard=None):
     """Network query (run_network_mvs, renderer.py:42-63) -> raw (N*S, 1 if alpha_only else 4).  The keywords choose the kernel as the ray march
     does (Renderer_ours.packed_alt returns them): guard + packed_split = (fp16x3 planes, 18) -> the guarded sequence, packed_split = (planes,
-    n_split) -> the split kernel, packed_bf16 -> bf16, none -> fp32."""
+    n_split) -> the split kernel, packed_bf16 -> bf16, none -> fp32.  A WidePacked (netwidth 256) runs the wide fp32 kernel and takes no keyword."""
+    wide = isinstance(packed, WidePacked)
+    if wide:
+        if packed_bf16 is not None or packed_split is not None or guard is not None:
+            raise ValueError("mlp_forward: netwidth 256 runs on the fp32 wide kernel only; packed_bf16 / packed_split / guard select 128-wide kernels")
+        if packed.F != F:
+            raise RuntimeError(f"mlp_forward: the buffer was packed for feat_dim {packed.F}, the call says {F}")
     l, raw = _lib.lib(), torch.empty((N * S, 1 if alpha_only else 4), device=device, dtype=torch.float32)
     io = (ndc_ptr, ndc_stride, feat_ptr, feat_stride, dirs_ptr, dirs_stride, N, S, int(alpha_only), raw.data_ptr())
-    if guard is not None:
+    if wide:
+        check(l.mvsnerf_mlp_fwd_wide(dev_f32(packed.buffer, "packed"), F, packed.width, *io, stream_ptr()), "mlp_fwd_wide")
+    elif guard is not None:
         if packed_split is None or packed_split[1] != N_SPLIT["fp16x3"]:
             raise ValueError("mlp_forward: a guard needs the fp16x3 split planes (the guarded sequence)")
         check(l.mvsnerf_mlp_fwd_guarded(packed_split[0].data_ptr(), packed.data_ptr(), F, *io, guard.data_ptr(), stream_ptr()), "mlp_fwd_guarded")
@@ -547,6 +614,7 @@ def raymarch(vol_cl, imgs, w2cs, intrinsics, packed, rays_pts, rays_ndc, z_vals,
     """One FFI call for rendering() (renderer.py:138-165).  Returns dict of outputs.
     want: which of the optional per-ray maps `disp` / `acc` to produce (rendering() returns neither: it passes ()).
     imgs_cl: the channel-last copy of `imgs` when the caller already holds it (renderer's per-scene cache)."""
+    _need_narrow(packed, "raymarch")
     _need_no_grad(vol_cl, imgs, rays_pts, rays_ndc, z_vals, rays_dir, op="raymarch")
     out, blk = _raymarch_block(vol_cl, imgs, w2cs, intrinsics, packed, rays_pts, rays_ndc, z_vals, rays_dir, white_bkgd, packed_bf16, packed_split,
                                guard, want, imgs_cl, torch.cuda.current_device())
@@ -559,6 +627,7 @@ def raymarch_batched(vol_cl, imgs, w2cs, intrinsics, packed, ray_batches, white_
     """K ray batches of one scene in ONE FFI call (mvsnerf_raymarch_fwd_batched): ray_batches = [(rays_pts, rays_ndc, z_vals, rays_dir), ...].
     Returns the list of per-batch output dicts of raymarch().  One batch is ~0.1 ms of GPU work; issued one call at a time, a render loop is
     paced by the host."""
+    _need_narrow(packed, "raymarch_batched")
     cur = torch.cuda.current_device()
     outs, blocks = [], (_lib.RaymarchArgs * len(ray_batches))()
     for k, (pts, ndc, z, rdir) in enumerate(ray_batches):
@@ -573,6 +642,7 @@ def raymarch_batched(vol_cl, imgs, w2cs, intrinsics, packed, ray_batches, white_
 def raymarch_colorvol_batched(vol_cl, w2cs, packed, ray_batches, white_bkgd=False, packed_bf16=None, packed_split=None, guard=None, want=()):
     """raymarch_batched on an (8 + 4V)-channel colour volume (mvsnerf_raymarch_colorvol_fwd_batched): ray_batches = [(rays_ndc, z_vals, rays_dir), ...];
     w2cs (V,4,4), view 0 the reference view.  No images, intrinsics or points are needed: the feature row is one lookup of the volume."""
+    _need_narrow(packed, "raymarch_colorvol_batched")
     cur = torch.cuda.current_device()
     D, H, W, C = vol_cl.shape
     V = w2cs.shape[0]
@@ -603,6 +673,7 @@ def render_rays(vol_cl, rays, t, packed, K_ref, w2c_ref, nf_ref, ref_hw, n_views
     chunk loop of the fine-tuning script's validation_step).  vol_cl (D,H,W,C): C == 8 renders from the volume and the source images (imgs (V,3,IH,IW)
     un-normalised, w2cs (V,4,4), intrinsics (V,3,3)); C == 8 + 4*n_views is a colour volume and needs none of them.  t (S,) = linspace(0,1,S);
     density (DD,DH,DW) + u (N,NI): importance sampling (ray_marcher_fine).  Returns dict with rgb (n,3) and the requested extras among depth/acc/disp (n,)."""
+    _need_narrow(packed, "render_rays")
     _need_no_grad(vol_cl, rays, imgs, density, op="render_rays")
     lib = _lib.lib()
     if rays.dim() != 2 or rays.shape[1] != 8:
@@ -660,6 +731,7 @@ def render_pixels(vol_cl, imgs, w2cs, intrinsics, packed, H, W, K_tgt, c2w_tgt, 
     """Pixel range of one target view in ONE FFI call (the chunk loop of validation_step, train_mvs_nerf_pl.py:198-208).
     Returns dict with rgb (n,3) and the requested extras among depth/acc/disp (n,)."""
     _need_no_grad(vol_cl, imgs, op="render_pixels")
+    _need_narrow(packed, "render_pixels")
     lib = _lib.lib()
     n = H * W - first_pixel if n_pixels is None else int(n_pixels)
     V = imgs.shape[0]
@@ -735,6 +807,7 @@ def _mlp_bwd_maps(F, device):
 
 
 def mlp_pack_bwd_bf16(weights, F):
+    _need_narrow(weights, "mlp_pack_bwd_bf16")
     n = _lib.lib().mvsnerf_mlp_packed_bwd_bf16_elems()
     packed = torch.empty(n, device=weights[0].device, dtype=torch.bfloat16)
     wp = (ctypes.c_void_p * 11)(*[dev_f32(w, "weight") for w in weights])
@@ -743,6 +816,7 @@ def mlp_pack_bwd_bf16(weights, F):
 
 
 def mlp_pack_bwd(weights, F):
+    _need_narrow(weights, "mlp_pack_bwd")
     n = _lib.lib().mvsnerf_mlp_packed_bwd_floats()
     packed = torch.empty(n, device=weights[0].device, dtype=torch.float32)
     wp = (ctypes.c_void_p * 11)(*[dev_f32(w, "weight") for w in weights])
@@ -757,6 +831,7 @@ class RayMarchFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, volume, imgs, w2cs, intrinsics, rays_pts, rays_ndc, z_vals, rays_dir, white_bkgd, packed, dp_samples, *mlp_params):
         """ONE FFI call (mvsnerf_raymarch_train_fwd): lookups -> MLP training forward with activation store -> compositing."""
+        _need_narrow(packed, "raymarch_train")
         lib = _lib.lib()
         vol_cl = channels_last_volume(volume)
         D, H, W, C = vol_cl.shape
@@ -904,6 +979,8 @@ def volume_grad_from_all_ranks(d_feat, ndc, gvol_cl, group=None, scatter=_scatte
 def raymarch_train(volume, imgs, w2cs, intrinsics, net, rays_pts, rays_ndc, z_vals, rays_dir, white_bkgd=False, dp_samples=False):
     """Differentiable rendering(): `net` is a models.MVSNeRF; returns the dict of ops.raymarch.
     dp_samples: data-parallel volume gradient by exchanging sample gradients (volume_grad_from_all_ranks)."""
+    if getattr(net.nerf, "W", 128) != 128:      # before packed(): nothing is packed or launched for a width that cannot be trained
+        raise _wide_refusal("raymarch_train")
     V = imgs.shape[0]
     lins = net.nerf._linears()
     params = []

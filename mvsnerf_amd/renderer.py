@@ -100,6 +100,9 @@ def gen_pts_feats(imgs, volume_feature, rays_pts, pose_ref, rays_ndc, feat_dim, 
     return out
 
 
+WIDE_TRAINING_MSG = ("training at netwidth 256 is not built: the wide MLP kernel (csrc/mlp_wide.hip) is a no-grad forward; render under "
+                     "torch.no_grad(), or train a netwidth-128 network")
+
 _scene = [None]
 
 
@@ -125,6 +128,12 @@ def rendering(args, pose_ref, rays_pts, rays_ndc, depth_candidates, rays_o, rays
     color_vol = bool(getattr(args, "use_color_volume", False))
     fusable = (pose_ref is not None and isinstance(network_fn, MVSNeRF) and img_feat is None and getattr(network_query_fn, "_mvsnerf_fused", False))
     vol = volume_feature.feat_volume if isinstance(volume_feature, RefVolume) else volume_feature
+    if isinstance(network_fn, MVSNeRF) and network_fn.wide:
+        # netwidth 256: the no-grad network query on the wide fp32 kernel between the individually HIP-backed pieces below (no one-call ray
+        # march, no backward at this width) - refused here, before anything is enqueued, when the call wants gradients
+        if torch.is_grad_enabled() and ((vol is not None and vol.requires_grad) or any(p.requires_grad for p in network_fn.parameters())):
+            raise NotImplementedError(WIDE_TRAINING_MSG)
+        fusable = False
     fusable = fusable and vol is not None
     needs_grad = fusable and torch.is_grad_enabled() and (vol.requires_grad or any(p.requires_grad for p in network_fn.parameters()))
     fused = fusable and (not color_vol or needs_grad)     # a colour volume is rendered piecewise below, trained through raymarch_train
@@ -168,6 +177,9 @@ def rendering_batched(args, pose_ref, ray_batches, volume_feature=None, imgs=Non
     vol = volume_feature.feat_volume if isinstance(volume_feature, RefVolume) else volume_feature
     if not (pose_ref is not None and isinstance(network_fn, MVSNeRF) and getattr(network_query_fn, "_mvsnerf_fused", False) and vol is not None):
         raise NotImplementedError("rendering_batched: the fused configuration only (what create_nerf_mvs builds); call rendering() per batch otherwise")
+    if network_fn.wide:      # netwidth 256 has no batched entry: rendering() once per batch, the same tuples
+        return [rendering(args, pose_ref, *b, volume_feature=volume_feature, imgs=imgs, network_fn=network_fn, network_query_fn=network_query_fn,
+                          white_bkgd=white_bkgd, **kwargs) for b in ray_batches]
     V = imgs.shape[1]
     if args.feat_dim != 8 + 4 * V:
         raise RuntimeError(f"args.feat_dim {args.feat_dim} != 8 + 4*V ({V} views)")

@@ -36,7 +36,7 @@ import torch.nn as nn
 from . import distributed as D
 from . import ops
 from .models import MVSNeRF, create_nerf_mvs
-from .renderer import rendering
+from .renderer import rendering, WIDE_TRAINING_MSG
 from .utils import build_rays, build_rays_test, img2mse
 
 
@@ -268,7 +268,8 @@ class MVSSystem(_ModuleShim):
         kw = self.render_kwargs_train
         net = kw["network_fn"]
         fused = (isinstance(net, MVSNeRF) and getattr(kw.get("network_query_fn"), "_mvsnerf_fused", False)
-                 and not getattr(args, "use_color_volume", False) and args.feat_dim == 8 + 4 * V and not whole_frame_off)
+                 and not getattr(args, "use_color_volume", False) and args.feat_dim == 8 + 4 * V and not whole_frame_off
+                 and not net.wide)                       # netwidth 256 has no whole-frame entry: the per-chunk loop below
         if target is not None and not fused:
             raise RuntimeError("render_view(target=...) needs the fused ray-march path (MVSNeRF + fused network_query_fn)")
         if fused:
@@ -501,6 +502,8 @@ class MVSSystemFinetune(_ModuleShim):
         from .models import RefVolume
         self.args = args
         self.args.feat_dim = 8 + 4 * int(getattr(args, "n_views", 3))       # :39 hard-wires 3 source views (8 + 3*4); n_views is the config-4 extension
+        if int(args.netwidth) == ops.WIDE_WIDTH:                            # this system trains the MLP; before anything is built or loaded
+            raise NotImplementedError(f"MVSSystemFinetune: {WIDE_TRAINING_MSG}")
         if getattr(args, "use_color_volume", False) and getattr(args, "use_density_volume", False):
             raise NotImplementedError("--use_color_volume together with --use_density_volume: update_density_volume would concatenate the "
                                       "colours to a volume that already holds them (train_mvs_nerf_finetuning_pl.py:96); not supported")
@@ -762,6 +765,8 @@ class MVSSystemFusion(_ModuleShim):
                                       "takes neither N_importance= nor density_volume=, data/ray_utils.py:152-156)")
         if int(args.pad) % 4:
             raise ValueError(f"MVSSystemFusion: args.pad must be a multiple of 4 (the quarter-resolution march pads by pad / 4), got {args.pad}")
+        if int(args.netwidth) == ops.WIDE_WIDTH:                          # this system trains the MLP; before anything is built or loaded
+            raise NotImplementedError(f"MVSSystemFusion: {WIDE_TRAINING_MSG}")
         self.args = args
         self.args.feat_dim = 8 + 12                                       # :82
         if not hasattr(args, "fusion_N_samples"):
