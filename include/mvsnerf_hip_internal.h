@@ -351,6 +351,25 @@ int mvsnerf_volume_fuse_splat(int D, int H, int W, int C, const float* ndc, int6
 int mvsnerf_volume_fuse_finish(int D, int H, int W, int C, const void* workspace, float* feat_volume, float* density_volume, void* stream);
 int mvsnerf_ray_march_bbox_fwd(const float* rays, const float* bbox, const float* t, const float* jitter, float perturb, int lindisp,
                                int64_t N, int S, float* z, float* pts, float* ndc, void* stream);
+/* ---- 8-bit video frames (renderer_video.ipynb: clamp * 255 -> uint8, visualize_depth_numpy of utils.py:30-45, crop, rgb | depth; csrc/frames.hip) ----
+ * depth_range: x0 = nan_to_num(depth[n]) (NaN -> 0, +inf -> FLT_MAX, -inf -> -FLT_MAX); out2[0] = min{x0 : x0 > 0} (+inf when no element is positive),
+ *   out2[1] = max x0 (utils.py:35-38), both written on the device.  Two launches, no atomics; min and max never round, so every run gives the same bits.
+ *   workspace: depth_range_workspace_floats(n) floats (0: n < 1), 4-byte aligned like depth and out2.
+ * frame_u8: rgb [H][W][3] and depth [H][W] fp32 -> out [H'][W' * panels][3] bytes, H' = H - 2 crop_h, W' = W - 2 crop_w: crop_h rows and crop_w columns are
+ *   removed from every side of each panel, then the colour panel (rgb != NULL) and the depth panel (depth_panel = 1) are placed side by side.
+ *   rgb may be NULL with depth_panel = 1 (the depth panel alone: visualize_depth*); depth / minmax / lut may be NULL with depth_panel = 0.
+ *   minmax: DEVICE pointer to {mi, ma}; lut: DEVICE pointer to [256][3] bytes, copied as they are (the channel order is the table's).
+ *   All arithmetic is fp32 with every operation rounded on its own (no FMA contraction, IEEE division):
+ *     colour  byte = trunc(clamp(rgb, 0, 1) * 255), NaN -> 0
+ *     depth   x0 = nan_to_num(depth), t = (x0 - mi) / ((ma - mi) + 1e-8f), i = trunc(255 t) SATURATED to [0, 255] (numpy's cast wraps or is undefined
+ *             out of range), NaN -> 0, pixel = lut[i][0..2]
+ *   out needs NO alignment (frame k of a (K,H',Wout,3) tensor with odd sizes starts anywhere); rgb, depth, minmax 4 bytes.  Exactly H' * W' * panels * 3
+ *   bytes are written.  MVSNERF_EINVAL: NULL out, no panel at all, a missing pointer of a requested panel, H or W < 1, a negative crop or one that leaves
+ *   nothing, depth_panel not 0 / 1; MVSNERF_EALIGN; MVSNERF_EUNSUPPORTED for H * W >= 2^28; all before the launch. */
+size_t mvsnerf_depth_range_workspace_floats(int64_t n);
+int mvsnerf_depth_range_fwd(const float* depth, int64_t n, float* out2, float* workspace, void* stream);
+int mvsnerf_frame_u8_fwd(const float* rgb, const float* depth, int H, int W, const float* minmax, const unsigned char* lut,
+                         int crop_h, int crop_w, int depth_panel, unsigned char* out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -263,6 +263,9 @@ SIGNATURES = {
     "mvsnerf_volume_fuse_splat": (_c_i, [_c_i] * 4 + [_c_fp, _c_l, _c_fp, _c_i, _c_fp, _c_fp, _c_fp]),
     "mvsnerf_volume_fuse_finish": (_c_i, [_c_i] * 4 + [_c_fp] * 4),
     "mvsnerf_ray_march_bbox_fwd": (_c_i, [_c_fp] * 4 + [ctypes.c_float, _c_i, _c_l, _c_i] + [_c_fp] * 4),
+    "mvsnerf_depth_range_workspace_floats": (ctypes.c_size_t, [_c_l]),
+    "mvsnerf_depth_range_fwd": (_c_i, [_c_fp, _c_l, _c_fp, _c_fp, _c_fp]),
+    "mvsnerf_frame_u8_fwd": (_c_i, [_c_fp, _c_fp, _c_i, _c_i, _c_fp, _c_fp, _c_i, _c_i, _c_i, _c_fp, _c_fp]),
 }
 
 _lib = None

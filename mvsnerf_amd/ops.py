@@ -1035,3 +1035,84 @@ def frame_metrics(pred, gt, depth_pred=None, depth_gt=None, win_size=7, data_ran
     check(_lib.lib().mvsnerf_frame_metrics_fwd(*ptrs, K, H, W, int(win_size), float(data_range), float(K1), float(K2), float(gt_scale), thr,
                                                out.data_ptr(), workspace.data_ptr(), stream_ptr()), "frame_metrics_fwd")
     return out
+
+
+# ------------------------------------------------------------------ 8-bit video frames (csrc/frames.hip)
+_JET = {}
+
+
+def jet_lut(device):
+    """The default colour table of the depth panel, (256,3) uint8 in RGB order: the jet ramp in closed form.  For i = 0..255, x = i / 255:
+    r = clamp(1.5 - |4x - 3|, 0, 1), g = clamp(1.5 - |4x - 2|, 0, 1), b = clamp(1.5 - |4x - 1|, 0, 1), each round(255 c).  255 c is always an
+    integer or a half, so it is formed in integers (510 c = clamp(765 - 2 |4i - 765 + 255 k|, 0, 510), k = 0, 1, 2) and halves round UP.
+    cv2's COLORMAP_JET bytes are not pinned by this (cv2 is not in this image); a caller who wants them passes cv2's own table as `lut`."""
+    key = str(torch.device(device))
+    if key not in _JET:
+        i = torch.arange(256, dtype=torch.int64).view(256, 1)
+        k = torch.tensor([0, 1, 2], dtype=torch.int64).view(1, 3)
+        twice = (765 - 2 * (4 * i - 765 + 255 * k).abs()).clamp(0, 510)
+        _JET[key] = ((twice + 1) // 2).to(torch.uint8).to(device)
+    return _JET[key]
+
+
+def depth_range(depth):
+    """utils.py:35-38 on the device: x0 = nan_to_num(depth) -> tensor([min{x0 : x0 > 0}, max x0]) (2,) fp32 on the GPU; the minimum is +inf when no
+    element is positive.  Two launches on the current stream, no host synchronisation; two runs give the same bits."""
+    _need_no_grad(depth, op="depth_range")
+    if not torch.is_tensor(depth) or depth.numel() < 1:
+        raise RuntimeError("depth_range: a non-empty tensor on the GPU")
+    keep = _Keep()
+    ptr = keep(depth, "depth_range: depth")
+    n = depth.numel()
+    out = torch.empty((2,), device=depth.device, dtype=torch.float32)
+    ws = torch.empty((int(_lib.lib().mvsnerf_depth_range_workspace_floats(n)),), device=depth.device, dtype=torch.float32)
+    check(_lib.lib().mvsnerf_depth_range_fwd(ptr, n, out.data_ptr(), ws.data_ptr(), stream_ptr()), "depth_range_fwd")
+    return out
+
+
+def frame_u8(rgb, depth=None, minmax=None, lut=None, crop=(0, 0), out=None):
+    """One 8-bit frame of the reference's video notebook (mvsnerf_frame_u8_fwd): rgb (H,W,3) -> trunc(clamp(rgb, 0, 1) * 255); with depth (H,W) a second
+    panel to its right, lut[trunc(255 (nan_to_num(depth) - mi) / (ma - mi + 1e-8))] (visualize_depth_numpy, utils.py:35-44, the index saturated to
+    0..255); crop = (rows, columns) removed from every side of each panel first.  Returns uint8 (H - 2 rows, (W - 2 columns) * panels, 3) on the GPU.
+    rgb=None writes the depth panel alone.  minmax: a (2,) device tensor or a pair of floats; None: ops.depth_range(depth), on the device.
+    lut: (256,3) uint8, None: jet_lut (RGB).  out: where to write - any uint8 tensor of that shape whose memory is contiguous, e.g. frame k of a
+    (K,H',Wout,3) tensor (no alignment needed).  One launch (three with minmax=None), no host synchronisation unless minmax is a pair of floats."""
+    _need_no_grad(rgb, depth, op="frame_u8")
+    if rgb is None and depth is None:
+        raise RuntimeError("frame_u8: rgb, depth or both")
+    ref = rgb if rgb is not None else depth
+    if not (torch.is_tensor(ref) and ref.is_cuda):
+        raise RuntimeError("frame_u8: tensors on the GPU")
+    if rgb is not None and not (rgb.dim() == 3 and rgb.shape[-1] == 3):
+        raise RuntimeError(f"frame_u8: rgb must be (H,W,3), got {tuple(rgb.shape)}")
+    H, W = int(ref.shape[0]), int(ref.shape[1])
+    if depth is not None and tuple(depth.shape) != (H, W):
+        raise RuntimeError(f"frame_u8: depth must be ({H},{W}), got {tuple(depth.shape)}")
+    ch, cw = int(crop[0]), int(crop[1])
+    if ch < 0 or cw < 0 or 2 * ch >= H or 2 * cw >= W:
+        raise RuntimeError(f"frame_u8: crop {(ch, cw)} leaves nothing of a {H} x {W} frame")
+    dev = ref.device
+    keep = _Keep()
+    p_rgb = keep(rgb, "frame_u8: rgb") if rgb is not None else 0
+    p_depth = p_mm = p_lut = 0
+    if depth is not None:
+        p_depth = keep(depth, "frame_u8: depth")
+        if minmax is None:
+            minmax = depth_range(keep.alive[-1])
+        elif not torch.is_tensor(minmax):
+            minmax = torch.tensor([float(minmax[0]), float(minmax[1])], dtype=torch.float32).to(dev)
+        if minmax.numel() != 2:
+            raise RuntimeError("frame_u8: minmax is (mi, ma)")
+        p_mm = keep(minmax.to(dev).reshape(2), "frame_u8: minmax")
+        lut = jet_lut(dev) if lut is None else torch.as_tensor(lut)
+        if tuple(lut.shape) != (256, 3) or lut.dtype != torch.uint8:
+            raise RuntimeError(f"frame_u8: lut must be (256,3) uint8, got {tuple(lut.shape)} {lut.dtype}")
+        lut = lut.to(dev).contiguous()
+        p_lut = lut.data_ptr()
+    shape = (H - 2 * ch, (W - 2 * cw) * ((rgb is not None) + (depth is not None)), 3)
+    if out is None:
+        out = torch.empty(shape, device=dev, dtype=torch.uint8)
+    elif not (torch.is_tensor(out) and out.dtype == torch.uint8 and out.device == dev and tuple(out.shape) == shape and out.is_contiguous()):
+        raise RuntimeError(f"frame_u8: out must be a contiguous uint8 tensor of shape {shape} on {dev}")
+    check(_lib.lib().mvsnerf_frame_u8_fwd(p_rgb, p_depth, H, W, p_mm, p_lut, ch, cw, int(depth is not None), out.data_ptr(), stream_ptr()), "frame_u8_fwd")
+    return out

@@ -299,6 +299,31 @@ class MVSSystem(_ModuleShim):
         return rgb.reshape(H, W, 3), depth.reshape(H, W)
 
     @torch.no_grad()
+    def render_path(self, batch, c2ws_render, hw=None, intrinsic=None, near_far=None, depth_panel=True, crop=False, minmax=None, cmap=None, volume=None):
+        """The reference's video loop (renderer_video.ipynb): the scene is encoded ONCE (or `volume` = encode_scene(batch) is used), every pose of
+        c2ws_render (K,4,4) is rendered with render_view(batch, volume=, target=) and written as an 8-bit `rgb | depth` frame by ops.frame_u8 straight
+        into frame k of the result: uint8 (K, H', W' * panels, 3) on the device, nothing visits the host and the loop never waits on the device.
+        hw / intrinsic / near_far: the rendered camera (defaults: the batch's image size, the last view's intrinsics and near / far).
+        depth_panel=False: colours only.  crop=True: H // 20 rows and W // 20 columns off every side of each panel, as the notebook; or (rows, columns).
+        minmax: the depth range of the colour map - a pair or a (2,) tensor; default the source views' near / far, as the notebooks.
+        cmap: a (256,3) uint8 table (default ops.jet_lut, RGB).  utils.save_frames writes the result as PNGs."""
+        batch = batch_to_device({k: v for k, v in batch.items() if k != "scan"}, self.device)
+        _, pose_ref = self.decode_batch(batch)
+        dev = self.device
+        H, W = (int(batch["images"].shape[-2]), int(batch["images"].shape[-1])) if hw is None else (int(hw[0]), int(hw[1]))
+        intrinsic = pose_ref["intrinsics"][-1] if intrinsic is None else torch.as_tensor(intrinsic).to(dev, torch.float32)
+        near_far = pose_ref["near_fars"][-1] if near_far is None else torch.as_tensor(near_far).to(dev, torch.float32)
+        c2ws = _path_poses(c2ws_render, dev)
+        if c2ws.shape[-2] == 3:
+            c2ws = torch.cat([c2ws, torch.tensor([0.0, 0.0, 0.0, 1.0], device=dev).expand(c2ws.shape[0], 1, 4)], 1)
+        crop, mm, lut, frames = _frame_setup(c2ws.shape[0], H, W, depth_panel, crop, minmax, cmap, pose_ref["near_fars"][0], dev)
+        vol = self.encode_scene(batch) if volume is None else volume
+        for k in range(c2ws.shape[0]):
+            rgb, depth = self.render_view(batch, volume=vol, target=dict(hw=(H, W), intrinsic=intrinsic, c2w=c2ws[k], near_far=near_far))
+            ops.frame_u8(rgb, depth if depth_panel else None, minmax=mm, lut=lut, crop=crop, out=frames[k])
+        return frames
+
+    @torch.no_grad()
     def validation_step(self, batch, batch_nb):
         """:172-254.  Renders the batch's last view from the first three (render_view: encode + the chunk loop, tile-parallel over the
         ranks) and returns the reference's per-sample log dict: 'val_psnr', 'val_depth_loss_r', 'val_abs_err', 'mask_sum',
@@ -665,6 +690,13 @@ class MVSSystemFinetune(_ModuleShim):
         return D.render_frame_pixels(render_range, 1, N, chunk, device=dev)
 
     @torch.no_grad()
+    def render_path(self, c2ws_render, hw, focal, depth_panel=True, crop=False, minmax=None, cmap=None, **render_rays_kw):
+        """The video loop of renderer_video.ipynb for the fine-tuned scene: per pose of c2ws_render (K,4,4) the notebook's rays (get_ray_directions(H, W,
+        focal) / get_rays, the source near / far) -> render_rays -> ops.frame_u8 into frame k.  Returns uint8 (K, H', W' * panels, 3) on the device;
+        depth_panel / crop / minmax / cmap as MVSSystem.render_path (minmax defaults to the source near / far); other keywords go to render_rays."""
+        return _render_path_rays(self, c2ws_render, hw, focal, self.near_far_source, depth_panel, crop, minmax, cmap, self.imgs.device, **render_rays_kw)
+
+    @torch.no_grad()
     def validation_step(self, batch, batch_nb):
         """:192-252.  batch = {'rays': (1,N,8) | (N,8), 'rgbs': (1,H,W,3) | (H,W,3) | (N,3)} - one view of the val split.  Renders the rays
         (render_rays) and returns the reference's log dict: 'val_psnr_all'.  Left out, as in MVSSystem.validation_step: the TensorBoard
@@ -744,6 +776,47 @@ def get_rays(directions, c2w):
     """reference data/ray_utils.py:32-53: (rays_o, rays_d), both (H*W, 3), un-normalised directions."""
     rays_d = directions @ c2w[:3, :3].T
     return c2w[:3, 3].expand(rays_d.shape).reshape(-1, 3), rays_d.reshape(-1, 3)
+
+
+# ------------------------------------------------------------------ camera path -> 8-bit frames (reference renderer_video.ipynb)
+def _path_poses(c2ws_render, dev):
+    """(K,4,4) | (K,3,4) poses (numpy from utils.gen_render_path / pose_spherical_dtu, or tensors) as one fp32 device tensor: one upload for the path."""
+    c2ws = torch.as_tensor(c2ws_render).to(dev, torch.float32)
+    if c2ws.dim() != 3 or c2ws.shape[-1] != 4 or c2ws.shape[-2] not in (3, 4):
+        raise ValueError(f"render_path: c2ws_render must be (K,4,4) or (K,3,4), got {tuple(c2ws.shape)}")
+    return c2ws
+
+
+def _frame_setup(K, H, W, depth_panel, crop, minmax, cmap, near_far, dev):
+    """What every frame of a path shares, built once so that the loop issues launches only: the crop (the notebook's H // 20, W // 20), the depth
+    range as a device tensor (default: the source near / far, `visualize_depth_numpy(depth, near_far_source)`), the colour table, the output."""
+    crop = (H // 20, W // 20) if crop is True else ((0, 0) if not crop else (int(crop[0]), int(crop[1])))
+    if minmax is None:
+        minmax = near_far
+    mm = (minmax.to(dev, torch.float32) if torch.is_tensor(minmax) else torch.tensor([float(minmax[0]), float(minmax[1])]).to(dev)).reshape(-1)[:2].contiguous()
+    lut = ops.jet_lut(dev) if cmap is None else torch.as_tensor(cmap).reshape(256, 3).to(dev, torch.uint8).contiguous()
+    frames = torch.empty((K, H - 2 * crop[0], (W - 2 * crop[1]) * (2 if depth_panel else 1), 3), device=dev, dtype=torch.uint8)
+    return crop, mm, lut, frames
+
+
+def _path_rays(directions, c2w, near_far):
+    """The notebook's (H*W, 8) rays of one pose: get_rays, then the source near / far in columns 6 and 7."""
+    rays_o, rays_d = get_rays(directions, c2w)
+    nf = near_far.reshape(-1)
+    return torch.cat([rays_o, rays_d, nf[0] * torch.ones_like(rays_o[:, :1]), nf[1] * torch.ones_like(rays_o[:, :1])], 1)
+
+
+def _render_path_rays(system, c2ws_render, hw, focal, near_far, depth_panel, crop, minmax, cmap, dev, **kw):
+    """render_path of the systems that render rays: per pose the notebook's rays -> system.render_rays -> ops.frame_u8 into frame k."""
+    H, W = int(hw[0]), int(hw[1])
+    c2ws = _path_poses(c2ws_render, dev)
+    near_far = near_far.to(dev, torch.float32)
+    crop, mm, lut, frames = _frame_setup(c2ws.shape[0], H, W, depth_panel, crop, minmax, cmap, near_far, dev)
+    directions = get_ray_directions(H, W, focal).to(dev)
+    for k in range(c2ws.shape[0]):
+        rgb, depth = system.render_rays(_path_rays(directions, c2ws[k], near_far), **kw)
+        ops.frame_u8(rgb.reshape(H, W, 3), depth.reshape(H, W) if depth_panel else None, minmax=mm, lut=lut, crop=crop, out=frames[k])
+    return frames
 
 
 class MVSSystemFusion(_ModuleShim):
@@ -891,6 +964,14 @@ class MVSSystemFusion(_ModuleShim):
             outs = rendering_batched(args, self.pose_source_ref, batches, self.volume, self.imgs_ref, **self.render_kwargs_train)
             rows += [torch.cat([o[0], o[3][:, None]], 1) for o in outs]
         return D._assemble_frame(torch.cat(rows, 0) if rows else None, 1, N, chunk, n_chunks, world, None, dev)
+
+    @torch.no_grad()
+    def render_path(self, c2ws_render, hw, focal, depth_panel=True, crop=False, minmax=None, cmap=None, **render_rays_kw):
+        """MVSSystemFinetune.render_path for the fused scene: the rays of each pose carry the first camera's source near / far (render_rays clips them to
+        the box), which is also the default depth range of the colour map."""
+        self._need_volume()
+        return _render_path_rays(self, c2ws_render, hw, focal, torch.as_tensor(self.views[0][2]), depth_panel, crop, minmax, cmap, self.bbox_3d.device,
+                                 **render_rays_kw)
 
     @torch.no_grad()
     def validation_step(self, batch, batch_nb):

@@ -6,6 +6,7 @@ Ray generation: the RNG draws stay here, exactly as in the reference, because th
 build_rays_test is one HIP kernel (mvsnerf_raygen_fwd).  get_rays_mvs / get_ndc_coordinate keep host-side torch bodies
 for callers that use them on their own (and for CPU tensors).
 """
+import numpy as np
 import torch
 
 from . import ops
@@ -241,6 +242,129 @@ def get_ptsvolume(H, W, D, pad, near_far, intrinsic, c2w):
 
 def normal_vect(vect, dim=-1):
     return vect / (torch.sqrt(torch.sum(vect ** 2, dim=dim, keepdim=True)) + 1e-7)
+
+
+
+# ------------------------------------------------------------------ depth colour maps (reference utils.py:30-65; csrc/frames.hip)
+def _depth_panel(depth, minmax, cmap, name):
+    """The depth panel of ops.frame_u8 for a numpy array or a tensor anywhere -> ((H,W,3) uint8 ndarray, [mi, ma]).  The package has no CPU arithmetic
+    of its own: the map goes to the current GPU and the bytes come back."""
+    d = torch.as_tensor(depth)
+    if d.dim() != 2:
+        raise ValueError(f"{name}: depth must be (H, W), got {tuple(d.shape)}")
+    d = d.to("cuda", torch.float32)
+    lut = None if cmap is None else torch.as_tensor(np.ascontiguousarray(np.asarray(cmap).reshape(256, 3)).astype(np.uint8))
+    if minmax is None:
+        rng = ops.depth_range(d)
+        mi, ma = (np.float32(v) for v in rng.cpu().numpy())          # the reference returns them (np.min / np.max of a float32 array)
+        if not mi < np.inf:
+            raise ValueError(f"{name}: no positive depth to take the minimum of (utils.py:37, np.min of an empty selection)")
+        mm = rng
+    else:
+        mi, ma = minmax
+        mm = (float(mi), float(ma))
+    return ops.frame_u8(None, d, minmax=mm, lut=lut).cpu().numpy(), [mi, ma]
+
+
+def visualize_depth_numpy(depth, minmax=None, cmap=None):
+    """utils.py:30-45.  depth (H,W) -> ((H,W,3) uint8 ndarray, [mi, ma]).  cmap: None (ops.jet_lut, RGB order) or a (256,3) table whose rows are
+    copied as they are - cv2.applyColorMap(np.arange(256, dtype=np.uint8), cv2.COLORMAP_JET).reshape(256, 3) gives cv2's bytes in cv2's BGR order
+    (the reference's default; a cv2 colour-map NUMBER is not accepted: cv2 is not a dependency).  Indices saturate to 0..255 where numpy's cast wraps."""
+    return _depth_panel(depth, minmax, cmap, "visualize_depth_numpy")
+
+
+def visualize_depth(depth, minmax=None, cmap=None):
+    """utils.py:47-65: the same panel as a float (3,H,W) tensor in [0,1] (the reference's PIL image -> ToTensor: bytes / 255)."""
+    x, mm = _depth_panel(depth, minmax, cmap, "visualize_depth")
+    return torch.from_numpy(x).permute(2, 0, 1).contiguous().to(torch.float32).div(255), mm
+
+
+# ------------------------------------------------------------------ camera paths (reference utils.py:479-534, 634-676, 698-711; host, numpy / scipy)
+def gen_render_path(c2ws, N_views=30):
+    """utils.py:479-508: a closed loop through the N poses - between neighbours (and from the last back to the first) N_views // 3 poses whose
+    'xyz' Euler angles (degrees) and positions are blended linearly; an angle more than 180 degrees from the first pose's gets 360 added.
+    Returns (N * (N_views // 3), 4, 4) float64."""
+    from scipy.spatial.transform import Rotation
+    n = len(c2ws)
+    w = np.linspace(1.0, .0, N_views // 3, endpoint=False).reshape(-1, 1)
+    angles, places = [], []
+    for i in range(n):
+        a = Rotation.from_matrix(c2ws[i, :3, :3]).as_euler('xyz', degrees=True).reshape(1, 3)
+        if i:
+            a[np.abs(a - angles[0]) > 180] += 360.0
+        angles.append(a)
+        places.append(c2ws[i, :3, 3:].reshape(1, 3))
+    order = [(i - 1, i) for i in range(1, n)] + [(n - 1, 0)]
+    ang = np.concatenate([w * angles[a] + (1.0 - w) * angles[b] for a, b in order])
+    pos = np.concatenate([w * places[a] + (1.0 - w) * places[b] for a, b in order])
+    out = []
+    for a, p in zip(ang, pos):
+        m = np.eye(4)
+        m[:3, :3] = Rotation.from_euler('xyz', a, degrees=True).as_matrix()
+        m[:3, 3:] = p.reshape(3, 1)
+        out.append(m)
+    return np.stack(out)
+
+
+def gen_render_path_spherical(theta, phi, radius=1.0):
+    """utils.py:510-534: the blender-style pose at (theta, phi) degrees on a sphere, a float32 (4,4) tensor: translate along z, rotate about x by phi,
+    about y by theta, then swap the axes."""
+    t = torch.Tensor([[1, 0, 0, 0], [0, 1, 0, 0], [0, 0, 1, radius], [0, 0, 0, 1]]).float()
+    p, th = phi / 180. * np.pi, theta / 180. * np.pi
+    rx = torch.Tensor([[1, 0, 0, 0], [0, np.cos(p), -np.sin(p), 0], [0, np.sin(p), np.cos(p), 0], [0, 0, 0, 1]]).float()
+    ry = torch.Tensor([[np.cos(th), 0, -np.sin(th), 0], [0, 1, 0, 0], [np.sin(th), 0, np.cos(th), 0], [0, 0, 0, 1]]).float()
+    c2w = ry @ (rx @ t)
+    return torch.Tensor(np.array([[-1, 0, 0, 0], [0, 0, 1, 0], [0, 1, 0, 0], [0, 0, 0, 1]])) @ c2w
+
+
+def pose_spherical_nerf(euler, radius=4.0):
+    """utils.py:634-638: rotation from 'xyz' Euler angles in degrees, the camera `radius` behind the origin along its own z.  (4,4) float64."""
+    from scipy.spatial.transform import Rotation
+    c2w = np.eye(4)
+    c2w[:3, :3] = Rotation.from_euler('xyz', euler, degrees=True).as_matrix()
+    c2w[:3, 3] = c2w[:3, :3] @ np.array([0.0, 0.0, -radius])
+    return c2w
+
+
+def normalize(v):
+    """utils.py:640-642."""
+    return v / np.linalg.norm(v)
+
+
+def pose_spherical_dtu(radii, focus_depth, n_poses=120, world_center=np.array([0, 0, 0])):
+    """utils.py:644-676: two turns of the LLFF spiral - centres (cos t, -sin t, -sin t/2) * radii, each camera looking from the plane z = -focus_depth
+    at its centre, y up - times diag(1,-1,-1,1).  Returns (n_poses, 3, 4) float64."""
+    poses = []
+    for t in np.linspace(0, 4 * np.pi, n_poses + 1)[:-1]:
+        center = np.array([np.cos(t), -np.sin(t), -np.sin(0.5 * t)]) * radii
+        z = normalize(center - np.array([0, 0, -focus_depth]))
+        x = normalize(np.cross(np.array([0, 1, 0]), z))
+        y = np.cross(z, x)
+        poses += [np.stack([x, y, z, center + world_center], 1)]
+    return np.stack(poses, 0) @ np.array([[1, 0, 0, 0], [0, -1, 0, 0], [0, 0, -1, 0], [0, 0, 0, 1]])
+
+
+def get_nearest_pose_ids(tar_pose, ref_poses, num_select):
+    """utils.py:698-711: for each of the N target poses (N,4,4) the indices of the num_select reference poses (M,4,4) whose camera centres are
+    nearest, nearest first.  (N, num_select) int64."""
+    dists = np.linalg.norm(tar_pose[:, None, :3, 3] - ref_poses[None, :, :3, 3], axis=-1)
+    return np.argsort(dists, axis=-1)[:, :num_select]
+
+
+def save_frames(frames, directory, prefix=""):
+    """One PNG per frame of a (K,H,W,3) uint8 tensor or array (what the systems' render_path returns), named <prefix>0000.png, <prefix>0001.png ...
+    as the video notebook numbers its images.  Returns the paths.  (An mp4 needs imageio, which is not a dependency.)"""
+    import os
+    from PIL import Image
+    arr = frames.cpu().numpy() if torch.is_tensor(frames) else np.asarray(frames)
+    if arr.ndim != 4 or arr.shape[-1] != 3 or arr.dtype != np.uint8:
+        raise ValueError(f"save_frames: (K,H,W,3) uint8 frames, got {arr.shape} {arr.dtype}")
+    os.makedirs(directory, exist_ok=True)
+    paths = []
+    for k, f in enumerate(arr):
+        paths.append(os.path.join(directory, f"{prefix}{k:04d}.png"))
+        Image.fromarray(np.ascontiguousarray(f)).save(paths[-1])
+    return paths
 
 
 from .encoder import homo_warp  # noqa: E402,F401  (reference utils.py:580; implemented next to the plane-sweep kernels)
