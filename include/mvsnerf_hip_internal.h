@@ -370,6 +370,28 @@ size_t mvsnerf_depth_range_workspace_floats(int64_t n);
 int mvsnerf_depth_range_fwd(const float* depth, int64_t n, float* out2, float* workspace, void* stream);
 int mvsnerf_frame_u8_fwd(const float* rgb, const float* depth, int H, int W, const float* minmax, const unsigned char* lut,
                          int crop_h, int crop_w, int depth_panel, unsigned char* out, void* stream);
+/* ---- empty-space skipping (no reference counterpart: its renderer queries every sample; csrc/sparse.hip) ----
+ * live_samples: which of the P = N*S samples of a ray batch can contribute, and their stable compaction.  density [D][H][W] (update_density_volume's sigma
+ *   at the voxel centres), ndc [N][S][3] reference-view NDC.  A sample is LIVE iff one of its three coordinates is non-finite, or some IN-GRID corner of
+ *   its trilinear cell holds a value v with !(v <= thr) (strictly above; a NaN voxel is live).  The cell is floor(ix), floor(iy), floor(iz) with
+ *   ix = ((gx + 1) / 2) * (W - 1), gx = x * 2 - 1 (iy from y, H; iz from z, D), fp32 with every operation rounded on its own - the index arithmetic of
+ *   the density lookup of mvsnerf_ray_marcher_fine_fwd (csrc/density_cell.h holds it for both).  Corners outside the grid do not count (the lookup pads
+ *   with zeros): for thr >= 0 a dead sample's trilinear density is <= thr.
+ *   Outputs: count[0] = number of live samples (int32, on the device); idx[j] = flat index n*S + s of the j-th live sample, ASCENDING; ndc_c[j][3],
+ *   pts_c[j][3] = the rows of ndc / pts [N][S][3] at idx[j]; dir_c[j][3] = rays_dir[idx[j] / S][3] as given.  pts / pts_c and rays_dir / dir_c may be NULL.
+ *   idx holds P entries, the compact rows P rows (the worst case); entries from count on are not written.  No atomics, three launches in stream order,
+ *   no workgroup waits on another: two runs give the same bytes.
+ *   workspace: live_samples_workspace_bytes(P) bytes (0: P < 1 or P >= 2^31), 8-byte aligned; everything else 4-byte aligned.
+ *   MVSNERF_EINVAL: a NULL density / count (ndc / idx / ndc_c / workspace with P > 0), pts without pts_c or rays_dir without dir_c, D, H or W < 1, N < 0,
+ *   S < 1, a NaN thr; MVSNERF_EUNSUPPORTED: P >= 2^31; MVSNERF_EALIGN; all before the first launch.  P == 0 writes count = 0.
+ * expand_rows: dst[P][C] with dst[idx[j]] = src[j] for j < min(count[0], src_rows) and every other row zero; every element of dst is written by the call.
+ *   idx ascending as live_samples leaves it (an entry can only ever select a row of dst: it is range-checked per tile); count is read on the device, so
+ *   a caller that sized src from an earlier read of it needs no second one.  src / idx may be NULL with src_rows == 0.
+ *   MVSNERF_EINVAL: NULL count / dst, src_rows < 0 or > P, P < 0, C < 1; MVSNERF_EUNSUPPORTED: C > 64, P >= 2^31; MVSNERF_EALIGN (4 bytes). */
+size_t mvsnerf_live_samples_workspace_bytes(int64_t P);
+int mvsnerf_live_samples_fwd(const float* density, int D, int H, int W, float thr, const float* ndc, const float* pts, const float* rays_dir,
+                             int64_t N, int S, int* count, int* idx, float* ndc_c, float* pts_c, float* dir_c, void* workspace, void* stream);
+int mvsnerf_expand_rows_fwd(const float* src, const int* idx, const int* count, int64_t src_rows, int64_t P, int C, float* dst, void* stream);
 
 #ifdef __cplusplus
 }

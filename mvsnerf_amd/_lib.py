@@ -266,6 +266,9 @@ SIGNATURES = {
     "mvsnerf_depth_range_workspace_floats": (ctypes.c_size_t, [_c_l]),
     "mvsnerf_depth_range_fwd": (_c_i, [_c_fp, _c_l, _c_fp, _c_fp, _c_fp]),
     "mvsnerf_frame_u8_fwd": (_c_i, [_c_fp, _c_fp, _c_i, _c_i, _c_fp, _c_fp, _c_i, _c_i, _c_i, _c_fp, _c_fp]),
+    "mvsnerf_live_samples_workspace_bytes": (ctypes.c_size_t, [_c_l]),
+    "mvsnerf_live_samples_fwd": (_c_i, [_c_fp, _c_i, _c_i, _c_i, ctypes.c_float, _c_fp, _c_fp, _c_fp, _c_l, _c_i] + [_c_fp] * 7),
+    "mvsnerf_expand_rows_fwd": (_c_i, [_c_fp, _c_fp, _c_fp, _c_l, _c_l, _c_i, _c_fp, _c_fp]),
 }
 
 _lib = None

@@ -7,6 +7,7 @@
 // deterministic function of the inputs.  One 64-lane wave per ray; per-wave arrays live in LDS.  All HBM/latency-bound
 // integer+fp32 work: no MFMA.
 #include "common.h"
+#include "density_cell.h"
 #include "march.h"
 #include "ray_dev.h"
 
@@ -116,19 +117,16 @@ extern "C" int mvsnerf_sample_pdf_fwd(const float* bins, const float* weights, c
 // index_point_feature, data/ray_utils.py:209-210 - the double transform is the reference's behaviour)
 __device__ __forceinline__ float density_lookup(const float* __restrict__ vol, int D, int H, int W, float cx, float cy, float cz)
 {
-    const float gx = cx * 2.0f - 1.0f, gy = cy * 2.0f - 1.0f, gz = cz * 2.0f - 1.0f;
-    const float ix = ((gx + 1.0f) / 2.0f) * (float)(W - 1);
-    const float iy = ((gy + 1.0f) / 2.0f) * (float)(H - 1);
-    const float iz = ((gz + 1.0f) / 2.0f) * (float)(D - 1);
-    const float fx = floorf(ix), fy = floorf(iy), fz = floorf(iz);
+    const DensityCell c = density_cell(D, H, W, cx, cy, cz);                     // density_cell.h: shared with the empty-space predicate (sparse.hip)
+    const float ix = c.ix, iy = c.iy, iz = c.iz, fx = c.fx, fy = c.fy, fz = c.fz;
     float acc = 0.0f;
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
         const int zc = k >> 2, yc = (k >> 1) & 1, xc = k & 1;
         const float x = fx + xc, y = fy + yc, z = fz + zc;
         const float w = (xc ? ix - fx : fx + 1.0f - ix) * (yc ? iy - fy : fy + 1.0f - iy) * (zc ? iz - fz : fz + 1.0f - iz);
-        if (x >= 0.0f && x <= (float)(W - 1) && y >= 0.0f && y <= (float)(H - 1) && z >= 0.0f && z <= (float)(D - 1))
-            acc += vol[(((int64_t)z * H + (int)y) * W + (int)x)] * w;
+        if (density_corner_in_grid(D, H, W, x, y, z))
+            acc += vol[density_corner_index(H, W, x, y, z)] * w;
     }
     return acc;
 }

@@ -1,0 +1,224 @@
+// Empty-space skipping for the render of a fine-tuned scene: which of the P = N*S samples of a ray batch can contribute at all, their stable
+// compaction, and the way back to dense rows.  No counterpart in the reference (its renderer queries every sample).
+//
+// A sample is LIVE iff one of its NDC coordinates is non-finite, or some in-grid corner of its trilinear cell in the (D,H,W) density volume holds
+// a value v with !(v <= thr) (a NaN voxel is live).  The cell is density_cell.h's: floor of ((x*2-1 + 1) / 2) * (W-1), ... - what density_lookup
+// (importance.hip) forms.  The trilinear density is a convex combination of the in-grid corners and zeros, so for thr >= 0 a dead sample's density
+// is <= thr.
+//
+// live_count_kernel    a workgroup owns LS_TILE = 1024 consecutive samples, four rounds of 256; each wave ballots its 64 predicates, stores the
+//                      ballot word (16 words per workgroup) and counts its bits; the four waves' counts meet in LDS -> one count per workgroup.
+// live_scan_kernel     ONE workgroup: exclusive scan of the workgroup counts (a thread owns a contiguous run; shuffle scan inside a wave, the four
+//                      wave totals through LDS) and the total -> *count.
+// live_write_kernel    reads the ballot words back (the predicate is evaluated once): a live lane's slot is the workgroup's offset + the bits of
+//                      the words in front of its own (through LDS) + mbcnt of its own word.  Slot order = sample order: idx is ascending, the
+//                      order of torch.nonzero, and every run gives the same bytes.  Nothing is placed with an atomic and no workgroup waits on
+//                      another (three launches in stream order instead).
+// expand_rows_kernel   dst[idx[j]] = src[j], every other row zero, every row written once: a workgroup owns ER_TILE consecutive rows of dst, finds
+//                      the first j with idx[j] >= its first row by one binary search (idx is ascending), and marks its rows' j in LDS.  An idx
+//                      entry can only ever select a row of the workgroup's own tile, whatever the buffer holds.
+#include "common.h"
+#include "density_cell.h"
+#include <math.h>
+
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int LS_THREADS = 256, LS_ROUNDS = 4, LS_TILE = LS_THREADS * LS_ROUNDS, LS_WORDS = LS_TILE / 64;
+constexpr int SCAN_THREADS = 256;
+constexpr int ER_THREADS = 256, ER_TILE = 1024, ER_MAX_C = 64;
+
+inline int64_t live_blocks(int64_t P) { return (P + LS_TILE - 1) / LS_TILE; }
+
+__device__ __forceinline__ bool sample_live(const float* __restrict__ density, int D, int H, int W, float thr, float x, float y, float z)
+{
+    if (!(isfinite(x) && isfinite(y) && isfinite(z))) return true;
+    const DensityCell c = density_cell(D, H, W, x, y, z);
+    bool live = false;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const float cx = c.fx + (float)(k & 1), cy = c.fy + (float)((k >> 1) & 1), cz = c.fz + (float)(k >> 2);
+        if (density_corner_in_grid(D, H, W, cx, cy, cz)) {
+            const float v = density[density_corner_index(H, W, cx, cy, cz)];
+            live = live || !(v <= thr);
+        }
+    }
+    return live;
+}
+
+__global__ __launch_bounds__(LS_THREADS) void live_count_kernel(const float* __restrict__ density, int D, int H, int W, float thr,
+                                                                const float* __restrict__ ndc, int64_t P,
+                                                                unsigned long long* __restrict__ masks, int* __restrict__ counts)
+{
+    __shared__ int s_cnt[LS_THREADS / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int n = 0;
+#pragma unroll
+    for (int r = 0; r < LS_ROUNDS; ++r) {
+        const int64_t t = (int64_t)blockIdx.x * LS_TILE + r * LS_THREADS + threadIdx.x;
+        bool live = false;
+        if (t < P) live = sample_live(density, D, H, W, thr, ndc[t * 3 + 0], ndc[t * 3 + 1], ndc[t * 3 + 2]);
+        const unsigned long long m = __ballot(live);
+        if (lane == 0) masks[(int64_t)blockIdx.x * LS_WORDS + r * (LS_THREADS / 64) + wave] = m;      // all 16 words, the tail's zeros too
+        n += __popcll(m);
+    }
+    if (lane == 0) s_cnt[wave] = n;
+    __syncthreads();
+    if (threadIdx.x == 0) counts[blockIdx.x] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+}
+
+__global__ __launch_bounds__(SCAN_THREADS) void live_scan_kernel(const int* __restrict__ counts, int nb, int* __restrict__ offsets, int* __restrict__ count)
+{
+    __shared__ int s_tot[SCAN_THREADS / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int c = (nb + SCAN_THREADS - 1) / SCAN_THREADS;                // run length: nb < 2^21 + 1, so threadIdx.x * c stays far inside 32 bits
+    const int b = threadIdx.x * c, e = b + c < nb ? b + c : nb;
+    int sum = 0;
+    for (int i = b; i < e; ++i) sum += counts[i];
+    int incl = sum;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const int o = __shfl_up(incl, d, 64);
+        if (lane >= d) incl += o;
+    }
+    if (lane == 63) s_tot[wave] = incl;
+    __syncthreads();
+    int run = incl - sum;
+    for (int w = 0; w < wave; ++w) run += s_tot[w];
+    for (int i = b; i < e; ++i) { offsets[i] = run; run += counts[i]; }
+    if (threadIdx.x == 0) *count = s_tot[0] + s_tot[1] + s_tot[2] + s_tot[3];
+}
+
+__global__ __launch_bounds__(LS_THREADS) void live_write_kernel(const unsigned long long* __restrict__ masks, const int* __restrict__ offsets,
+                                                                const float* __restrict__ ndc, const float* __restrict__ pts,
+                                                                const float* __restrict__ rays_dir, int64_t P, unsigned S,
+                                                                int* __restrict__ idx, float* __restrict__ ndc_c, float* __restrict__ pts_c,
+                                                                float* __restrict__ dir_c)
+{
+    __shared__ unsigned long long s_mask[LS_WORDS];
+    __shared__ int s_pop[LS_WORDS];
+    if (threadIdx.x < LS_WORDS) {
+        const unsigned long long m = masks[(int64_t)blockIdx.x * LS_WORDS + threadIdx.x];
+        s_mask[threadIdx.x] = m;
+        s_pop[threadIdx.x] = __popcll(m);
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int base = offsets[blockIdx.x];
+#pragma unroll
+    for (int r = 0; r < LS_ROUNDS; ++r) {
+        const int w = r * (LS_THREADS / 64) + wave;
+        const unsigned long long m = s_mask[w];
+        if (!((m >> lane) & 1ull)) continue;
+        int pre = 0;
+        for (int k = 0; k < w; ++k) pre += s_pop[k];
+        const int rank = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+        const int64_t j = (int64_t)base + pre + rank;                   // < count <= P: inside every output
+        const int64_t t = (int64_t)blockIdx.x * LS_TILE + r * LS_THREADS + threadIdx.x;       // < P: the count pass sets no bit past the end
+        if (t >= P || j >= P) continue;
+        idx[j] = (int)t;
+        ndc_c[j * 3 + 0] = ndc[t * 3 + 0]; ndc_c[j * 3 + 1] = ndc[t * 3 + 1]; ndc_c[j * 3 + 2] = ndc[t * 3 + 2];
+        if (pts) { pts_c[j * 3 + 0] = pts[t * 3 + 0]; pts_c[j * 3 + 1] = pts[t * 3 + 1]; pts_c[j * 3 + 2] = pts[t * 3 + 2]; }
+        if (rays_dir) {
+            const int64_t n = (unsigned)t / S;                          // P < 2^31: one 32-bit division
+            dir_c[j * 3 + 0] = rays_dir[n * 3 + 0]; dir_c[j * 3 + 1] = rays_dir[n * 3 + 1]; dir_c[j * 3 + 2] = rays_dir[n * 3 + 2];
+        }
+    }
+}
+
+template <bool VEC4>
+__global__ __launch_bounds__(ER_THREADS) void expand_rows_kernel(const float* __restrict__ src, const int* __restrict__ idx, const int* __restrict__ count,
+                                                                 int64_t src_rows, int64_t P, int C, float* __restrict__ dst)
+{
+    __shared__ int s_j[ER_TILE];
+    const int64_t row0 = (int64_t)blockIdx.x * ER_TILE;
+    const int rows = (int)(P - row0 < ER_TILE ? P - row0 : ER_TILE);
+    for (int r = threadIdx.x; r < ER_TILE; r += ER_THREADS) s_j[r] = -1;
+    int64_t n = *count;
+    n = n < 0 ? 0 : (n > src_rows ? src_rows : n);                      // never past what src and idx hold
+    // first j with idx[j] >= row0 (every thread runs the same search: uniform loads)
+    int64_t lo = 0, hi = n;
+    while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if ((int64_t)idx[mid] < row0) lo = mid + 1; else hi = mid; }
+    __syncthreads();
+    // at most `rows` entries of an ascending idx fall into this tile
+    for (int k = threadIdx.x; k < rows; k += ER_THREADS) {
+        const int64_t j = lo + k;
+        if (j >= n) break;
+        const int64_t r = (int64_t)idx[j] - row0;
+        if (r >= 0 && r < rows) s_j[r] = (int)j;
+    }
+    __syncthreads();
+    if (VEC4) {
+        for (int r = threadIdx.x; r < rows; r += ER_THREADS) {
+            const int j = s_j[r];
+            f32x4 v = {0.f, 0.f, 0.f, 0.f};
+            if (j >= 0) v = reinterpret_cast<const f32x4*>(src)[j];
+            reinterpret_cast<f32x4*>(dst)[row0 + r] = v;
+        }
+    } else {
+        const int total = rows * C;                                     // C <= ER_MAX_C: far inside 32 bits
+        for (int e = threadIdx.x; e < total; e += ER_THREADS) {
+            const int r = e / C, c = e - r * C;
+            const int j = s_j[r];
+            dst[row0 * C + e] = j >= 0 ? src[(int64_t)j * C + c] : 0.f;
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" size_t mvsnerf_live_samples_workspace_bytes(int64_t P)
+{
+    if (P < 1 || P >= ((int64_t)1 << 31)) return 0;
+    const size_t nb = (size_t)live_blocks(P);
+    return nb * LS_WORDS * sizeof(unsigned long long) + nb * 2 * sizeof(int);
+}
+
+extern "C" int mvsnerf_live_samples_fwd(const float* density, int D, int H, int W, float thr, const float* ndc, const float* pts, const float* rays_dir,
+                                        int64_t N, int S, int* count, int* idx, float* ndc_c, float* pts_c, float* dir_c, void* workspace, void* stream)
+{
+    if (!density || !count || D < 1 || H < 1 || W < 1 || N < 0 || S < 1 || thr != thr) return MVSNERF_EINVAL;
+    if ((pts && !pts_c) || (rays_dir && !dir_c)) return MVSNERF_EINVAL;
+    if (N > (((int64_t)1 << 31) - 1) / S) return MVSNERF_EUNSUPPORTED;                  // P >= 2^31: idx is int32
+    const int64_t P = N * (int64_t)S;
+    hipStream_t st = (hipStream_t)stream;
+    auto mis = [](const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; };
+    if (mis(density, 4) || mis(ndc, 4) || mis(pts, 4) || mis(rays_dir, 4) || mis(count, 4) || mis(idx, 4) || mis(ndc_c, 4) || mis(pts_c, 4) || mis(dir_c, 4) ||
+        mis(workspace, 8))
+        return MVSNERF_EALIGN;
+    if (P == 0) {
+        hipError_t e = hipMemsetAsync(count, 0, sizeof(int), st);
+        return e == hipSuccess ? MVSNERF_OK : (int)e;
+    }
+    if (!ndc || !idx || !ndc_c || !workspace) return MVSNERF_EINVAL;
+    const int64_t nb = live_blocks(P);
+    unsigned long long* masks = static_cast<unsigned long long*>(workspace);
+    int* counts = reinterpret_cast<int*>(masks + nb * LS_WORDS);
+    int* offsets = counts + nb;
+    live_count_kernel<<<(unsigned)nb, LS_THREADS, 0, st>>>(density, D, H, W, thr, ndc, P, masks, counts);
+    MVS_LAUNCH_CHECK();
+    live_scan_kernel<<<1, SCAN_THREADS, 0, st>>>(counts, (int)nb, offsets, count);
+    MVS_LAUNCH_CHECK();
+    live_write_kernel<<<(unsigned)nb, LS_THREADS, 0, st>>>(masks, offsets, ndc, pts, rays_dir, P, (unsigned)S, idx, ndc_c, pts_c, dir_c);
+    MVS_LAUNCH_CHECK();
+    return MVSNERF_OK;
+}
+
+extern "C" int mvsnerf_expand_rows_fwd(const float* src, const int* idx, const int* count, int64_t src_rows, int64_t P, int C, float* dst, void* stream)
+{
+    if (!count || !dst || src_rows < 0 || P < 0 || C < 1 || src_rows > P) return MVSNERF_EINVAL;
+    if (src_rows > 0 && (!src || !idx)) return MVSNERF_EINVAL;
+    if (C > ER_MAX_C || P >= ((int64_t)1 << 31)) return MVSNERF_EUNSUPPORTED;
+    auto mis = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) != 0; };
+    if (mis(src) || mis(idx) || mis(count) || mis(dst)) return MVSNERF_EALIGN;
+    if (P == 0) return MVSNERF_OK;
+    const unsigned grid = mvs_cdiv(P, ER_TILE);
+    hipStream_t st = (hipStream_t)stream;
+    if (C == 4 && mvs_aligned16(src) && mvs_aligned16(dst))
+        expand_rows_kernel<true><<<grid, ER_THREADS, 0, st>>>(src, idx, count, src_rows, P, C, dst);
+    else
+        expand_rows_kernel<false><<<grid, ER_THREADS, 0, st>>>(src, idx, count, src_rows, P, C, dst);
+    MVS_LAUNCH_CHECK();
+    return MVSNERF_OK;
+}

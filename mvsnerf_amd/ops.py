@@ -770,6 +770,107 @@ def render_pixels(vol_cl, imgs, w2cs, intrinsics, packed, H, W, K_tgt, c2w_tgt, 
 _render_ws = {}
 
 
+# ------------------------------------------------------------------ empty-space skipping (csrc/sparse.hip)
+def _thr_f32(thr, op):
+    thr = float(thr)
+    if thr != thr:
+        raise ValueError(f"{op}: the density threshold is NaN")
+    return thr
+
+
+def live_samples(density, rays_ndc, thr, rays_pts=None, rays_dir=None):
+    """Which samples of a ray batch can contribute, and their stable compaction (mvsnerf_live_samples_fwd): density (D,H,W), rays_ndc (N,S,3) ->
+    (count, idx, ndc_c, pts_c, dir_c).  A sample is live iff a coordinate is non-finite or some in-grid corner of its trilinear cell in `density`
+    holds a value v with not (v <= thr) (thr is rounded to fp32; a NaN voxel is live).  count: int32 (1,) on the device; idx: int32 (P,), its first
+    count entries the flat indices n*S + s of the live samples, ascending (torch.nonzero's order); ndc_c / pts_c / dir_c: (P,3), their first count rows
+    the live samples' NDC rows, rays_pts rows and the rays_dir row of their ray (None for an input that is None).  Buffers have the worst-case size;
+    what lies behind count is not written.  Three launches on the current stream, no host synchronisation, no atomics: two runs give the same bytes."""
+    _need_no_grad(density, rays_ndc, rays_pts, rays_dir, op="live_samples")
+    thr = _thr_f32(thr, "live_samples")
+    if density.dim() != 3:
+        raise RuntimeError(f"live_samples: density must be (D,H,W), got {tuple(density.shape)}")
+    if rays_ndc.dim() != 3 or rays_ndc.shape[-1] != 3:
+        raise RuntimeError(f"live_samples: rays_ndc must be (N,S,3), got {tuple(rays_ndc.shape)}")
+    N, S = int(rays_ndc.shape[0]), int(rays_ndc.shape[1])
+    P = N * S
+    if rays_pts is not None and tuple(rays_pts.shape) != (N, S, 3):
+        raise RuntimeError(f"live_samples: rays_pts must be ({N},{S},3), got {tuple(rays_pts.shape)}")
+    if rays_dir is not None and tuple(rays_dir.shape) != (N, 3):
+        raise RuntimeError(f"live_samples: rays_dir must be ({N},3), got {tuple(rays_dir.shape)}")
+    if S < 1 or P >= 2 ** 31:
+        raise RuntimeError(f"live_samples: {N} x {S} samples: S >= 1 and fewer than 2^31 samples (idx is int32)")
+    lib = _lib.lib()
+    dev = rays_ndc.device
+    D, H, W = density.shape
+    c = _Keep()
+    count = torch.empty((1,), device=dev, dtype=torch.int32)
+    idx = torch.empty((P,), device=dev, dtype=torch.int32)
+    rows = [torch.empty((P, 3), device=dev, dtype=torch.float32) if t is not None else None for t in (rays_ndc, rays_pts, rays_dir)]
+    ws = torch.empty((max(int(lib.mvsnerf_live_samples_workspace_bytes(P)), 8) // 8,), device=dev, dtype=torch.int64)
+    check(lib.mvsnerf_live_samples_fwd(c(density, "density"), D, H, W, thr, c(rays_ndc, "rays_ndc"),
+                                       0 if rays_pts is None else c(rays_pts, "rays_pts"), 0 if rays_dir is None else c(rays_dir, "rays_dir"),
+                                       N, S, count.data_ptr(), idx.data_ptr(), *[0 if r is None else r.data_ptr() for r in rows],
+                                       ws.data_ptr(), stream_ptr()), "live_samples_fwd")
+    return (count, idx, *rows)
+
+
+def expand_rows(src, idx, count, P, out=None):
+    """dst (P,C) with dst[idx[j]] = src[j] for j < count and every other row zero (mvsnerf_expand_rows_fwd): src (n,C) fp32, idx / count as
+    ops.live_samples returns them (count is read on the device and clamped to n).  Every element of dst is written, whatever it held
+    (out: a caller-owned contiguous fp32 (P,C) tensor to write into)."""
+    _need_no_grad(src, op="expand_rows")
+    if src.dim() != 2:
+        raise RuntimeError(f"expand_rows: src must be (n,C), got {tuple(src.shape)}")
+    n, C = int(src.shape[0]), int(src.shape[1])
+    P = int(P)
+    if not (idx.dtype == torch.int32 and idx.is_cuda and idx.is_contiguous() and count.dtype == torch.int32 and count.is_cuda and count.numel() == 1):
+        raise RuntimeError("expand_rows: idx and count are the int32 device tensors of ops.live_samples")
+    if n > P or idx.numel() < n:
+        raise RuntimeError(f"expand_rows: {n} source rows, {idx.numel()} indices, {P} destination rows")
+    c = _Keep()
+    dst = torch.empty((P, C), device=src.device, dtype=torch.float32) if out is None else out
+    if tuple(dst.shape) != (P, C):
+        raise RuntimeError(f"expand_rows: out must be ({P},{C}), got {tuple(dst.shape)}")
+    dev_f32(dst, "expand_rows: out")
+    check(_lib.lib().mvsnerf_expand_rows_fwd(c(src, "src") if n else 0, idx.data_ptr() if n else 0, count.data_ptr(), n, P, C, dst.data_ptr(), stream_ptr()),
+          "expand_rows_fwd")
+    return dst
+
+
+def raymarch_sparse(vol_cl, imgs, w2cs, intrinsics, packed, rays_pts, rays_ndc, z_vals, rays_dir, density, thr, white_bkgd=False, want=(), **packed_alt):
+    """ops.raymarch's outputs with the radiance MLP run on the live samples only (ops.live_samples of `density` at `thr`): live_samples -> ONE host
+    read of the count (the only synchronisation; at 0 neither a gather nor an MLP launch is enqueued) -> ops.gather (ops.gather_colorvol for an
+    (8+4V)-channel colour volume, which needs no imgs / intrinsics / rays_pts) on the compact rows as (n_live,1,3) -> ops.mlp_forward(N=n_live, S=1)
+    -> expand_rows into raw (N,S,4) -> ops.composite.  Dead samples have raw = (0,0,0,0), so alpha = weight = 0; live ones the bits of the dense
+    sequence (a sample's MLP column does not depend on its neighbours in the tile).  packed: mlp_pack's buffer or a WidePacked; **packed_alt: the
+    kernel choice of ops.mlp_forward (MVSNeRF.packed_alt).  Returns raw, rgb_map, weights, depth, alpha, disp / acc when in `want`, and n_live (int)."""
+    _need_no_grad(vol_cl, imgs, rays_pts, rays_ndc, z_vals, rays_dir, density, op="raymarch_sparse")
+    thr = _thr_f32(thr, "raymarch_sparse")
+    N, S = z_vals.shape
+    C = vol_cl.shape[-1]
+    color_vol = C != 8
+    F = C if color_vol else 8 + 4 * imgs.shape[0]
+    if color_vol and C != 8 + 4 * w2cs.shape[0]:
+        raise RuntimeError(f"raymarch_sparse: the volume has {C} channels, 8 + 4V is {8 + 4 * w2cs.shape[0]}")
+    dev = rays_ndc.device
+    count, idx, ndc_c, pts_c, dir_c = live_samples(density, rays_ndc, thr, None if color_vol else rays_pts, rays_dir)
+    n_live = int(count.item())
+    if n_live:
+        ndc_l, dir_l = ndc_c[:n_live].view(n_live, 1, 3), dir_c[:n_live]
+        if color_vol:
+            feat, dirs = gather_colorvol(vol_cl, ndc_l, dir_l, w2cs[0].contiguous())
+        else:
+            feat, dirs = gather(vol_cl, imgs, w2cs, intrinsics, pts_c[:n_live].view(n_live, 1, 3), ndc_l, dir_l)
+        raw_c = mlp_forward(packed, F, ndc_l.data_ptr(), 3, feat.data_ptr(), F, dirs.data_ptr(), 3, n_live, 1, 0, dev, **packed_alt)
+    else:
+        raw_c = torch.empty((0, 4), device=dev, dtype=torch.float32)
+    raw = expand_rows(raw_c, idx, count, N * S).view(N, S, 4)
+    rgb, disp, acc, weights, depth, alpha = composite(raw, z_vals, white_bkgd)
+    out = {"raw": raw, "rgb_map": rgb, "weights": weights, "depth": depth, "alpha": alpha, "n_live": n_live}
+    out.update({k: v for k, v in (("disp", disp), ("acc", acc)) if k in want})
+    return out
+
+
 # ------------------------------------------------------------------ training path (autograd)
 def _act_n(q, h):
     return (q >> 4) * 32 + (q & 3) + 8 * ((q & 15) >> 2) + 4 * h

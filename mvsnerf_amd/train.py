@@ -562,11 +562,9 @@ class MVSSystemFinetune(_ModuleShim):
         self.density_volume = None
         use_cv, use_dv = bool(getattr(args, "use_color_volume", False)), bool(getattr(args, "use_density_volume", False))
         if use_cv or use_dv:
-            from .utils import get_ptsvolume, build_color_volume
+            from .utils import build_color_volume
             Dv, Hv, Wv = vol.shape[-3:]
-            intrinsic, c2w = self.pose_source["intrinsics"][0].clone(), self.pose_source["c2ws"][0]
-            intrinsic[:2] /= 4
-            vox_pts = get_ptsvolume(Hv - 2 * args.pad, Wv - 2 * args.pad, Dv, args.pad, self.near_far_source, intrinsic, c2w).contiguous()
+            vox_pts = self._voxel_points(Dv, Hv, Wv)
             with torch.no_grad():
                 self.color_feature = build_color_volume(vox_pts, self.pose_source, self.imgs, with_mask=True)   # (D*H, W, 4V)
             if use_cv and vol.shape[1] == 8:
@@ -590,13 +588,32 @@ class MVSSystemFinetune(_ModuleShim):
         if args.dp_volume_grad == "samples":
             self._allreduce = D.FlatGradAllReduce([p for p in self.network_fn.parameters()])           # the volume gradient arrives complete
 
+    def _voxel_points(self, Dv, Hv, Wv):
+        """:73-77: the voxel centres of the reference frustum, (D*H, W, 3)."""
+        from .utils import get_ptsvolume
+        intrinsic, c2w = self.pose_source["intrinsics"][0].clone(), self.pose_source["c2ws"][0]
+        intrinsic[:2] /= 4
+        return get_ptsvolume(Hv - 2 * self.args.pad, Wv - 2 * self.args.pad, Dv, self.args.pad, self.near_far_source, intrinsic, c2w).contiguous()
+
     def update_density_volume(self):
-        """:91-99: sigma of every voxel centre from the current volume + MLP (forward_alpha queries), -> (D,H,W)."""
+        """:91-99: sigma of every voxel centre from the current volume + MLP (forward_alpha queries), -> (D,H,W).
+        Under --use_density_volume the voxel positions and colour features are the ones __init__ built.  Any other system builds what is missing
+        on first use (render_rays(skip_empty=) needs the density of a scene that was fine-tuned without importance sampling); a colour volume's
+        feature rows are its own 8 + 4V channels - the colours were projected into it once, :79-80."""
         from .renderer import render_density
         with torch.no_grad():
             Dv, Hv, Wv = self.volume.feat_volume.shape[-3:]
-            vol_cl = ops.channels_last_volume(self.volume.feat_volume.detach())                     # (D,H,W,8)
-            features = torch.cat((vol_cl.reshape(Dv * Hv, Wv, 8), self.color_feature), -1)           # = cat(...).permute(0,2,3,4,1) :96
+            vol_cl = ops.channels_last_volume(self.volume.feat_volume.detach())                     # (D,H,W,8) or (D,H,W,8+4V)
+            if getattr(self, "vox_pts", None) is None:
+                self.vox_pts = self._voxel_points(Dv, Hv, Wv)
+            C = vol_cl.shape[-1]
+            if C == self.args.feat_dim and C != 8:
+                features = vol_cl.reshape(Dv * Hv, Wv, C)
+            else:
+                if getattr(self, "color_feature", None) is None:
+                    from .utils import build_color_volume
+                    self.color_feature = build_color_volume(self.vox_pts, self.pose_source, self.imgs, with_mask=True)   # (D*H, W, 4V)
+                features = torch.cat((vol_cl.reshape(Dv * Hv, Wv, 8), self.color_feature), -1)       # = cat(...).permute(0,2,3,4,1) :96
             self.density_volume = render_density(self.network_fn, self.vox_pts, features,
                                                  self.render_kwargs_train["network_query_fn"]).reshape(Dv, Hv, Wv)
 
@@ -628,7 +645,7 @@ class MVSSystemFinetune(_ModuleShim):
 
     # -- rendering the fine-tuned scene (train_mvs_nerf_finetuning_pl.py:192-252) ---------------------
     @torch.no_grad()
-    def render_rays(self, rays, chunk=None, batch_rays=16384, u=None, whole_frame_off=False):
+    def render_rays(self, rays, chunk=None, batch_rays=16384, u=None, whole_frame_off=False, skip_empty=None):
         """The rendering part of the fine-tuning script's validation_step (:204-237) for the dataset's rays (N,8) = [o | d | near | far]: per
         chunk ray_marcher -> get_ndc_coordinate -> [ray_marcher_fine, when a density volume exists and args.N_importance > 0] -> rendering, from
         the learnt `self.volume` (8 channels + the source images, or the (8 + 4V)-channel colour volume of --use_color_volume).  Returns
@@ -636,7 +653,20 @@ class MVSSystemFinetune(_ModuleShim):
         ranks in contiguous chunk ranges exactly as MVSSystem.render_view shards pixels.
         u: the (N, N_importance) uniform draw of sample_pdf (drawn once with torch.rand when None).  batch_rays: rays per sub-batch inside the
         library call (free parameter: the results do not depend on it).  whole_frame_off=True runs the reference's per-chunk Python loop
-        (ray_marcher -> ops.ray_points -> ray_marcher_fine -> rendering) instead; both produce the same values."""
+        (ray_marcher -> ops.ray_points -> ray_marcher_fine -> rendering) instead; both produce the same values.
+        skip_empty: None (default) is the dense render above, untouched.  A float is a density threshold: samples whose trilinear cell in
+        `self.density_volume` (update_density_volume()) holds no value above it are not sent through the MLP - their raw is (0,0,0,0), the
+        others have the bits of the dense sequence (ops.raymarch_sparse).  The frame then runs per sub-batch of batch_rays rays (ray_marcher ->
+        ops.ray_points -> [ray_marcher_fine] -> ops.raymarch_sparse), the sub-batches sharded over the ranks, one host read of the live count per
+        sub-batch; `self.last_live_fraction` is this rank's live samples over its samples."""
+        if skip_empty is not None:          # refusals first: nothing below needs the library before them
+            if whole_frame_off:
+                raise ValueError("render_rays: skip_empty runs its own per-sub-batch loop; it cannot be combined with whole_frame_off=True")
+            skip_empty = float(skip_empty)
+            if skip_empty != skip_empty:
+                raise ValueError("render_rays: skip_empty is NaN (a density threshold, or None for the dense render)")
+            if getattr(self, "density_volume", None) is None:
+                raise RuntimeError("render_rays: skip_empty needs the scene's density volume; call update_density_volume() first")
         args = self.args
         chunk = int(chunk or args.chunk)
         dev = self.imgs.device
@@ -677,6 +707,29 @@ class MVSSystemFinetune(_ModuleShim):
         if args.feat_dim != 8 + 4 * V or vol.shape[1] != (args.feat_dim if color_vol else 8):
             raise RuntimeError(f"render_rays: volume with {vol.shape[1]} channels, feat_dim {args.feat_dim}, {V} source views")
         vol_cl = ops.channels_last_volume(vol)
+        if skip_empty is not None:
+            B = max(int(batch_rays), 1)
+            imgs0 = None if color_vol else self.imgs[0].contiguous()
+            w2cs = self.pose_source["w2cs"][:V].contiguous()
+            Ks = None if color_vol else self.pose_source["intrinsics"][:V].contiguous()
+            packed, alt = net.packed(args.feat_dim), net.packed_alt(args.feat_dim)
+            live = [0, 0]                   # live samples, samples
+
+            def render_batch(idx):
+                r = rays[idx * B:(idx + 1) * B]
+                _, rays_o, rays_d, z = ray_marcher(r, N_samples=args.N_samples, lindisp=lindisp)
+                pts, ndc = ops.ray_points(rays_o, rays_d, z, w2c_ref, K_ref, self.near_far_source, ref_hw=(H, W), pad=args.pad, lindisp=lindisp)
+                if fine:
+                    pts, rays_o, rays_d, z = ray_marcher_fine(r, self.density_volume, z, ndc, N_importance=NI, u=u[idx * B:(idx + 1) * B].contiguous())
+                    pts, ndc = ops.ray_points(rays_o, rays_d, z, w2c_ref, K_ref, self.near_far_source, ref_hw=(H, W), pad=args.pad, lindisp=lindisp)
+                o = ops.raymarch_sparse(vol_cl, imgs0, w2cs, Ks, packed, pts, ndc, z.contiguous(), rays_d.contiguous(), self.density_volume, skip_empty,
+                                        white_bkgd=white, **alt)
+                live[0] += o["n_live"]
+                live[1] += z.numel()
+                return o["rgb_map"], o["depth"]
+            out = D.render_frame(render_batch, 1, N, B)
+            self.last_live_fraction = live[0] / live[1] if live[1] else 0.0
+            return out
         t = torch.linspace(0, 1, args.N_samples, device=dev)
         src = {} if color_vol else dict(imgs=self.imgs[0].contiguous(), w2cs=self.pose_source["w2cs"][:V].contiguous(),
                                         intrinsics=self.pose_source["intrinsics"][:V].contiguous())
