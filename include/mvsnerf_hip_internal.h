@@ -392,6 +392,26 @@ size_t mvsnerf_live_samples_workspace_bytes(int64_t P);
 int mvsnerf_live_samples_fwd(const float* density, int D, int H, int W, float thr, const float* ndc, const float* pts, const float* rays_dir,
                              int64_t N, int S, int* count, int* idx, float* ndc_c, float* pts_c, float* dir_c, void* workspace, void* stream);
 int mvsnerf_expand_rows_fwd(const float* src, const int* idx, const int* count, int64_t src_rows, int64_t P, int C, float* dst, void* stream);
+/* ---- a density volume in the renderer's own frame (no reference counterpart; csrc/occupancy.hip) ----
+ * voxel_points: the nodes (k,j,i) of planes [d0, d1) of a [D][H][W] volume, rows in [k][j][i] order: ndc[(d1-d0) H W][3] = (i/(W-1), j/(H-1), k/(D-1)), IEEE
+ *   divisions, 0 on an axis of size 1 - the coordinates whose trilinear cell starts exactly on the node, whether the volume is a reference frustum or a
+ *   world-space box.  pts (may be NULL: a box volume has no camera) receives the world positions that mvsnerf_ray_points_fwd / get_ndc_coordinate map to
+ *   those coordinates: u = ((x (wf + 2 pad) - pad) / wf) (W_img - 1), wf = W_img / 4 (v alike), z = near + z_ndc (far - near) (lindisp: in 1 / z),
+ *   world = c2w (K^-1 (u z, v z, z)).  K_ref[9], c2w_ref[12 or 16, row-major 3x4 part] and near_far[2] are HOST arrays, read during the call: the entry
+ *   inverts K and forms c2w K^-1 once, in double; the kernel does nine multiply-adds per node.  Both outputs are written for every row of the range
+ *   and nothing else; 16-byte aligned outputs are written with 16-byte stores.
+ *   MVSNERF_EINVAL: NULL ndc, D, H or W < 1, a plane range outside 0 <= d0 <= d1 <= D; with pts: a NULL camera array, W_img or H_img < 2, pad < 0, a
+ *   singular or non-finite K, non-finite near / far (zero under lindisp); MVSNERF_EUNSUPPORTED: D H W >= 2^31; MVSNERF_EALIGN (4 bytes); all before the
+ *   launch.  d0 == d1 launches nothing.
+ * max_dilate3d: out[k][j][i] = max of in over the (2r+1)^3 window clipped to the grid, r in {0, 1, 2}; a NaN in the window gives NaN (a NaN voxel must
+ *   stay live for live_samples); r == 0 copies.  Three separable passes (W, H, D); workspace: D H W floats (may be NULL when r == 0), distinct from in
+ *   and out.  Per voxel 4 bytes are read and 4 written in each pass (the neighbours come from cache): 24 bytes for r > 0, 8 for r == 0.  With W % 4 == 0 and
+ *   16-byte aligned buffers a thread moves four voxels of a row per access; the results do not depend on which form runs.
+ *   MVSNERF_EINVAL: NULL in / out (workspace with r > 0), in == out or a workspace equal to either, D, H or W < 1, r outside 0..2;
+ *   MVSNERF_EUNSUPPORTED: D H W >= 2^31; MVSNERF_EALIGN (4 bytes); all before the first launch. */
+int mvsnerf_voxel_points_fwd(int D, int H, int W, int d0, int d1, const float* K_ref, const float* c2w_ref, const float* near_far,
+                             int W_img, int H_img, int pad, int lindisp, float* ndc, float* pts, void* stream);
+int mvsnerf_max_dilate3d_fwd(const float* in, int D, int H, int W, int r, float* out, float* workspace, void* stream);
 
 #ifdef __cplusplus
 }

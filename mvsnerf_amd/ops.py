@@ -871,6 +871,119 @@ def raymarch_sparse(vol_cl, imgs, w2cs, intrinsics, packed, rays_pts, rays_ndc, 
     return out
 
 
+# ------------------------------------------------------------------ a density volume in the renderer's frame (csrc/occupancy.hip)
+def _host_f32(t, n, name):
+    """A camera tensor as a contiguous fp32 HOST tensor of at least n values (the C entry reads it during the call; a device tensor is copied once)."""
+    h = torch.as_tensor(t).detach().to("cpu", torch.float32).contiguous()
+    if h.numel() < n:
+        raise RuntimeError(f"voxel_points: {name} must hold at least {n} values, got {tuple(h.shape)}")
+    return h
+
+
+def voxel_points(D, H, W, K_ref=None, c2w_ref=None, near_far=None, ref_hw=None, pad=0, lindisp=False, planes=None, device=None, out=None):
+    """The nodes of planes [d0, d1) (planes=; default all) of a (D,H,W) volume, rows in [k][j][i] order (mvsnerf_voxel_points_fwd) -> (ndc (n,3), pts (n,3) |
+    None): ndc = (i/(W-1), j/(H-1), k/(D-1)), the coordinates ops.volume_sample / ops.live_samples resolve to the node itself; pts, when the reference
+    camera is given (K_ref (3,3), c2w_ref (4,4) | (3,4), near_far (2,), ref_hw = the reference view's (H_img, W_img), pad, lindisp as ops.ray_points takes
+    them), the world positions ops.ray_points maps to those coordinates.  A box volume (MVSSystemFusion) has no camera: leave K_ref None.
+    Camera tensors on the device are read back once per call (pass host tensors to a loop).  device: where the rows go (default: the camera's device, or the
+    current GPU).  out: (ndc_all, pts_all | None) caller-owned (D*H*W,3) fp32 tensors; rows [d0*H*W, d1*H*W) of them are written, no other, and views
+    of those rows are returned."""
+    D, H, W = int(D), int(H), int(W)
+    d0, d1 = (0, D) if planes is None else (int(planes[0]), int(planes[1]))
+    with_pts = K_ref is not None
+    if with_pts and (c2w_ref is None or near_far is None or ref_hw is None):
+        raise RuntimeError("voxel_points: world positions need K_ref, c2w_ref, near_far and ref_hw together")
+    if D < 1 or H < 1 or W < 1 or not 0 <= d0 <= d1 <= D:
+        raise RuntimeError(f"voxel_points: planes [{d0}, {d1}) of a ({D},{H},{W}) volume")
+    if device is None:
+        device = K_ref.device if (torch.is_tensor(K_ref) and K_ref.is_cuda) else torch.device("cuda", torch.cuda.current_device())
+    n, lo = (d1 - d0) * H * W, d0 * H * W
+    if out is None:
+        ndc = torch.empty((n, 3), device=device, dtype=torch.float32)
+        pts = torch.empty((n, 3), device=device, dtype=torch.float32) if with_pts else None
+    else:
+        if tuple(out[0].shape) != (D * H * W, 3) or (with_pts and (out[1] is None or tuple(out[1].shape) != (D * H * W, 3))):
+            raise RuntimeError(f"voxel_points: out must hold ({D * H * W},3) tensors")
+        dev_f32(out[0], "voxel_points: out[0]")
+        ndc = out[0][lo:lo + n]
+        pts = None
+        if with_pts:
+            dev_f32(out[1], "voxel_points: out[1]")
+            pts = out[1][lo:lo + n]
+    cam = (0, 0, 0, 0, 0)
+    if with_pts:
+        hK, hc, hn = _host_f32(K_ref, 9, "K_ref"), _host_f32(c2w_ref, 12, "c2w_ref"), _host_f32(torch.as_tensor(near_far).reshape(-1), 2, "near_far")
+        cam = (hK.data_ptr(), hc.data_ptr(), hn.data_ptr(), int(ref_hw[1]), int(ref_hw[0]))
+    if n:               # an empty plane range has no row to write (and an empty tensor no address to hand over)
+        check(_lib.lib().mvsnerf_voxel_points_fwd(D, H, W, d0, d1, *cam, int(pad), int(bool(lindisp)), ndc.data_ptr(), 0 if pts is None else pts.data_ptr(),
+                                                  stream_ptr()), "voxel_points_fwd")
+    return ndc, pts
+
+
+def max_dilate3d(density, r):
+    """(D,H,W) fp32 -> the maximum over the (2r+1)^3 window clipped to the grid, r in {0, 1, 2} (mvsnerf_max_dilate3d_fwd); a NaN in the window gives NaN,
+    r = 0 is a copy.  A new tensor: the input is never written."""
+    _need_no_grad(density, op="max_dilate3d")
+    r = int(r)
+    if density.dim() != 3:
+        raise RuntimeError(f"max_dilate3d: density must be (D,H,W), got {tuple(density.shape)}")
+    if r not in (0, 1, 2):
+        raise ValueError(f"max_dilate3d: r must be 0, 1 or 2, got {r}")
+    D, H, W = density.shape
+    c = _Keep()
+    src = c(density, "density")
+    out = torch.empty((D, H, W), device=density.device, dtype=torch.float32)
+    ws = torch.empty((D, H, W), device=density.device, dtype=torch.float32) if r else None
+    check(_lib.lib().mvsnerf_max_dilate3d_fwd(src, D, H, W, r, out.data_ptr(), 0 if ws is None else ws.data_ptr(), stream_ptr()), "max_dilate3d_fwd")
+    return out
+
+
+def node_density(vol_cl, packed, w2cs, imgs=None, intrinsics=None, camera=None, dilate=0, planes_per_call=8, **packed_alt):
+    """The sigma the renderer's kernels give AT the nodes of the volume they render from -> (D,H,W) fp32: per slab of planes_per_call planes
+    voxel_points -> ops.gather (8-channel volume + source images: imgs (V,3,IH,IW) un-normalised, w2cs (V,4,4), intrinsics (V,3,3), and camera =
+    dict(K_ref, c2w_ref, near_far, ref_hw, pad[, lindisp]) of the reference view, for the world positions the colour lookup projects) or
+    ops.gather_colorvol ((8+4V)-channel volume: no images, no camera, the coordinates may be a box's) on the node rows as (n,1,3) without a view
+    direction -> ops.mlp_forward(alpha_only=True) into the slab of the result; then max_dilate3d(dilate) when dilate > 0.  The lookups and the MLP entry
+    are the ray march's (ops.raymarch_sparse runs the same two on its live rows), so density[k,j,i] is the sigma-only output a sample ON node (k,j,i)
+    gets; net_type v2 has no ReLU on it, as forward_alpha has none.  packed / **packed_alt: MVSNeRF.packed / packed_alt (the kernel choice).
+    The slab loop bounds the workspace (8 planes of a 128 x 176 x 208 volume are 293 k rows of 8+4V features); the result does not depend on it."""
+    _need_no_grad(vol_cl, imgs, w2cs, intrinsics, op="node_density")
+    dilate, step = int(dilate), int(planes_per_call)
+    if dilate not in (0, 1, 2):
+        raise ValueError(f"node_density: dilate must be 0, 1 or 2, got {dilate}")
+    if step < 1:
+        raise ValueError(f"node_density: planes_per_call must be >= 1, got {planes_per_call}")
+    if vol_cl.dim() != 4:
+        raise RuntimeError(f"node_density: vol_cl must be (D,H,W,C) (ops.channels_last_volume), got {tuple(vol_cl.shape)}")
+    D, H, W, C = vol_cl.shape
+    color_vol = C != 8
+    if color_vol:
+        if C != 8 + 4 * w2cs.shape[0]:
+            raise RuntimeError(f"node_density: the volume has {C} channels, 8 + 4V is {8 + 4 * w2cs.shape[0]}")
+        F, cam = C, {}
+    else:
+        if imgs is None or intrinsics is None or camera is None:
+            raise RuntimeError("node_density: an 8-channel volume needs imgs, intrinsics and camera= (the reference view) for the colour lookup")
+        F = 8 + 4 * imgs.shape[0]
+        cam = dict(K_ref=_host_f32(camera["K_ref"], 9, "K_ref"), c2w_ref=_host_f32(camera["c2w_ref"], 12, "c2w_ref"),
+                   near_far=_host_f32(torch.as_tensor(camera["near_far"]).reshape(-1), 2, "near_far"), ref_hw=camera["ref_hw"],
+                   pad=int(camera.get("pad", 0)), lindisp=bool(camera.get("lindisp", False)))
+    dev = vol_cl.device
+    density = torch.empty((D, H, W), device=dev, dtype=torch.float32)
+    for d0 in range(0, D, step):
+        d1 = min(d0 + step, D)
+        n = (d1 - d0) * H * W
+        ndc, pts = voxel_points(D, H, W, planes=(d0, d1), device=dev, **cam)
+        ndc = ndc.view(n, 1, 3)
+        if color_vol:
+            feat, _ = gather_colorvol(vol_cl, ndc)
+        else:
+            feat, _ = gather(vol_cl, imgs, w2cs, intrinsics, pts.view(n, 1, 3), ndc)
+        raw = mlp_forward(packed, F, ndc.data_ptr(), 3, feat.data_ptr(), F, 0, 3, n, 1, 1, dev, **packed_alt)
+        density[d0:d1].copy_(raw.view(d1 - d0, H, W))
+    return max_dilate3d(density, dilate) if dilate else density
+
+
 # ------------------------------------------------------------------ training path (autograd)
 def _act_n(q, h):
     return (q >> 4) * 32 + (q & 3) + 8 * ((q & 15) >> 2) + 4 * h

@@ -231,7 +231,39 @@ class MVSSystem(_ModuleShim):
         return self.MVSNet(imgs[:, :V], proj_mats[:, :V], near_fars[0], pad=self.args.pad)[0]
 
     @torch.no_grad()
-    def render_view(self, batch, chunk=None, whole_frame_off=False, target=None, batch_rays=16384, volume=None):
+    def scene_density(self, batch, volume=None, dilate=0):
+        """The density volume of the encoded scene in the RENDERER's frame -> (D,h,w) fp32: ops.node_density over the nodes of `volume`
+        (encode_scene(batch) when None) - at every node the sigma-only output of the lookups and the MLP entry render_view's ray march runs there
+        (DESIGN.md 4f).  Views and cameras are taken from the batch exactly as render_view takes them (all but the last view are sources, view 0 is the
+        reference); the nodes' world positions for the colour lookup come from the reference view's OWN intrinsics, pose and near / far - what the volume
+        is aligned with.  dilate: widen the occupied region by that many voxels (ops.max_dilate3d).  This is what render_view(skip_empty=) tests
+        samples against; build it once per scene (render_path_skip_empty does)."""
+        args = self.args
+        data_mvs, pose_ref = self.decode_batch(dict(batch))
+        imgs, near_fars = data_mvs["images"], pose_ref["near_fars"]
+        H, W = int(imgs.shape[-2]), int(imgs.shape[-1])
+        V = imgs.shape[1] - 1
+        vol = self.encode_scene(batch) if volume is None else volume
+        net, color_vol = self._sparse_net(V, vol)
+        src = {} if color_vol else dict(imgs=self.unpreprocess(imgs)[0, :V].contiguous(), intrinsics=pose_ref["intrinsics"][:V].contiguous(),
+                                        camera=dict(K_ref=pose_ref["intrinsics"][0], c2w_ref=pose_ref["c2ws"][0], near_far=near_fars[0], ref_hw=(H, W),
+                                                    pad=args.pad))
+        return ops.node_density(ops.channels_last_volume(vol), net.packed(args.feat_dim), pose_ref["w2cs"][:V].contiguous(), dilate=dilate, **src,
+                                **net.packed_alt(args.feat_dim))
+
+    def _sparse_net(self, V, vol):
+        """(network, colour volume?) of the per-sub-batch sparse path (ops.node_density, ops.raymarch_sparse): the fused configuration only."""
+        args, kw = self.args, self.render_kwargs_train
+        net = kw["network_fn"]
+        if not (isinstance(net, MVSNeRF) and getattr(kw.get("network_query_fn"), "_mvsnerf_fused", False)):
+            raise NotImplementedError("skip_empty / scene_density: the fused configuration only (what create_nerf_mvs builds)")
+        color_vol = bool(getattr(args, "use_color_volume", False))
+        if args.feat_dim != 8 + 4 * V or vol.shape[-4] != (args.feat_dim if color_vol else 8):
+            raise RuntimeError(f"skip_empty / scene_density: volume with {vol.shape[-4]} channels, feat_dim {args.feat_dim}, {V} source views")
+        return net, color_vol
+
+    @torch.no_grad()
+    def render_view(self, batch, chunk=None, whole_frame_off=False, target=None, batch_rays=16384, volume=None, skip_empty=None, density=None, dilate=0):
         """The rendering part of validation_step (:172-254): encode once, then the chunk loop over the target view's
         pixels - tile-parallel over ranks (contiguous chunk ranges + one all_gather).  Returns (rgb (H,W,3), depth (H,W)).
         whole_frame_off=True keeps the per-chunk Python loop (build_rays_test + rendering per chunk) instead of the single
@@ -242,7 +274,25 @@ class MVSSystem(_ModuleShim):
         reference view's own intrinsics and size are used, which is what the volume is aligned with.
         batch_rays: rays per sub-batch inside the library call (free parameter: the pixels do not depend on it; measured on a 512x640
         frame: 1024 -> 85.5 ms, 4096 -> 81.7, 16384 -> 80.5, 65536 -> 80.9; the workspace is 16 KB per ray).
-        volume: the result of encode_scene(batch) - the encode is skipped (a camera path over one scene; the pixels are the same)."""
+        volume: the result of encode_scene(batch) - the encode is skipped (a camera path over one scene; the pixels are the same).
+        skip_empty: None (default) is the dense render above, untouched.  A float is the density threshold of DESIGN.md 4e: samples whose trilinear
+        cell in `density` holds no value above it are not sent through the MLP - their raw is (0,0,0,0), the others have the bits of the dense
+        sequence (ops.raymarch_sparse).  The frame then runs per sub-batch of batch_rays pixels (ops.raygen -> ops.raymarch_sparse), the sub-batches
+        sharded over the ranks, one host read of the live count per sub-batch; `self.last_live_fraction` is this rank's live samples over its samples.
+        netwidth 256, net_type v2 and colour volumes take the same path.  density: (D,h,w) of the volume in use - default
+        scene_density(batch, volume, dilate), built on every call: a camera path should build it once (render_path_skip_empty does) and pass it.  dilate is
+        read only when the density is built here."""
+        if skip_empty is not None:          # refusals first: nothing below needs the library before them
+            if whole_frame_off:
+                raise ValueError("render_view: skip_empty runs its own per-sub-batch loop; it cannot be combined with whole_frame_off=True")
+            skip_empty = float(skip_empty)
+            if skip_empty != skip_empty:
+                raise ValueError("render_view: skip_empty is NaN (a density threshold, or None for the dense render)")
+            if density is not None and (density.dim() != 3 or (volume is not None and tuple(density.shape) != tuple(volume.shape[-3:]))):
+                raise RuntimeError(f"render_view: density must be the (D,h,w) of the volume in use, got {tuple(density.shape)}"
+                                   + ("" if volume is None else f" for a volume {tuple(volume.shape)}"))
+        elif density is not None:
+            raise ValueError("render_view: density= is read by the skip_empty path only; pass skip_empty= (a threshold) with it")
         args = self.args
         chunk = chunk or args.chunk
         data_mvs, pose_ref = self.decode_batch(dict(batch))
@@ -267,6 +317,36 @@ class MVSSystem(_ModuleShim):
 
         kw = self.render_kwargs_train
         net = kw["network_fn"]
+        if skip_empty is not None:
+            net, color_vol = self._sparse_net(V, volume_feature)
+            if density is None:
+                density = self.scene_density(batch, volume=volume_feature, dilate=dilate)
+            if tuple(density.shape) != tuple(volume_feature.shape[-3:]):
+                raise RuntimeError(f"render_view: density {tuple(density.shape)} is not the (D,h,w) of the volume {tuple(volume_feature.shape)}")
+            density = density.to(imgs.device, torch.float32).contiguous()
+            k_render = intrinsic if intrinsic.dim() == 2 else intrinsic.mean(0)
+            k_ndc = k_render if k_ref is None else k_ref
+            nf_t, nf_r = nf_tgt.reshape(-1)[:2].contiguous(), near_fars[0].reshape(-1)[:2].contiguous()
+            vol_cl = ops.channels_last_volume(volume_feature)
+            src = None if color_vol else imgs[0, :-1].contiguous()
+            w2cs = pose_ref["w2cs"][:V].contiguous()
+            Ks = None if color_vol else pose_ref["intrinsics"][:V].contiguous()
+            packed, alt = net.packed(args.feat_dim), net.packed_alt(args.feat_dim)
+            white = bool(kw.get("white_bkgd", False))
+            B = max(int(batch_rays), 1)
+            live = [0, 0]                   # live samples, samples
+
+            def render_batch(idx):
+                first = idx * B
+                pts, dirs, ndc, z, _ = ops.raygen(H, W, k_render, tgt_to_world, k_ndc, world_to_ref, nf_t, nf_r, args.N_samples, pad=args.pad,
+                                                  first_pixel=first, n_rays=min(B, H * W - first), ref_hw=ref_hw)
+                o = ops.raymarch_sparse(vol_cl, src, w2cs, Ks, packed, pts, ndc, z, dirs, density, skip_empty, white_bkgd=white, **alt)
+                live[0] += o["n_live"]
+                live[1] += z.numel()
+                return o["rgb_map"], o["depth"]
+            rgb, depth = D.render_frame(render_batch, H, W, B)
+            self.last_live_fraction = live[0] / live[1] if live[1] else 0.0
+            return rgb.reshape(H, W, 3), depth.reshape(H, W)
         fused = (isinstance(net, MVSNeRF) and getattr(kw.get("network_query_fn"), "_mvsnerf_fused", False)
                  and not getattr(args, "use_color_volume", False) and args.feat_dim == 8 + 4 * V and not whole_frame_off
                  and not net.wide)                       # netwidth 256 has no whole-frame entry: the per-chunk loop below
@@ -306,7 +386,27 @@ class MVSSystem(_ModuleShim):
         hw / intrinsic / near_far: the rendered camera (defaults: the batch's image size, the last view's intrinsics and near / far).
         depth_panel=False: colours only.  crop=True: H // 20 rows and W // 20 columns off every side of each panel, as the notebook; or (rows, columns).
         minmax: the depth range of the colour map - a pair or a (2,) tensor; default the source views' near / far, as the notebooks.
-        cmap: a (256,3) uint8 table (default ops.jet_lut, RGB).  utils.save_frames writes the result as PNGs."""
+        cmap: a (256,3) uint8 table (default ops.jet_lut, RGB).  utils.save_frames writes the result as PNGs.
+        With empty space skipped: render_path_skip_empty (this method's parameter list is pinned by tests/test_render_path_refs.py)."""
+        return self._render_path(batch, c2ws_render, hw, intrinsic, near_far, depth_panel, crop, minmax, cmap, volume, None, 0)
+
+    @torch.no_grad()
+    def render_path_skip_empty(self, batch, c2ws_render, skip_empty, dilate=0, **render_path_kw):
+        """render_path with render_view's skip_empty (a density threshold): the scene is encoded once, its density volume is built ONCE per
+        path next to the encode (scene_density(batch, volume, dilate)), and both are handed to every render_view call.  render_path_kw: render_path's
+        keywords (hw, intrinsic, near_far, depth_panel, crop, minmax, cmap, volume).  `self.last_live_fraction` is the last frame's."""
+        skip_empty = float(skip_empty)
+        if skip_empty != skip_empty:
+            raise ValueError("render_path_skip_empty: skip_empty is NaN (a density threshold)")
+        names = ("hw", "intrinsic", "near_far", "depth_panel", "crop", "minmax", "cmap", "volume")
+        unknown = sorted(set(render_path_kw) - set(names))
+        if unknown:
+            raise TypeError(f"render_path_skip_empty: unexpected keyword(s) {unknown}; render_path's are {list(names)}")
+        kw = dict(hw=None, intrinsic=None, near_far=None, depth_panel=True, crop=False, minmax=None, cmap=None, volume=None)
+        kw.update(render_path_kw)
+        return self._render_path(batch, c2ws_render, *(kw[n] for n in names), skip_empty, dilate)
+
+    def _render_path(self, batch, c2ws_render, hw, intrinsic, near_far, depth_panel, crop, minmax, cmap, volume, skip_empty, dilate):
         batch = batch_to_device({k: v for k, v in batch.items() if k != "scan"}, self.device)
         _, pose_ref = self.decode_batch(batch)
         dev = self.device
@@ -318,8 +418,9 @@ class MVSSystem(_ModuleShim):
             c2ws = torch.cat([c2ws, torch.tensor([0.0, 0.0, 0.0, 1.0], device=dev).expand(c2ws.shape[0], 1, 4)], 1)
         crop, mm, lut, frames = _frame_setup(c2ws.shape[0], H, W, depth_panel, crop, minmax, cmap, pose_ref["near_fars"][0], dev)
         vol = self.encode_scene(batch) if volume is None else volume
+        sparse = {} if skip_empty is None else dict(skip_empty=skip_empty, density=self.scene_density(batch, volume=vol, dilate=dilate))
         for k in range(c2ws.shape[0]):
-            rgb, depth = self.render_view(batch, volume=vol, target=dict(hw=(H, W), intrinsic=intrinsic, c2w=c2ws[k], near_far=near_far))
+            rgb, depth = self.render_view(batch, volume=vol, target=dict(hw=(H, W), intrinsic=intrinsic, c2w=c2ws[k], near_far=near_far), **sparse)
             ops.frame_u8(rgb, depth if depth_panel else None, minmax=mm, lut=lut, crop=crop, out=frames[k])
         return frames
 
@@ -595,11 +696,32 @@ class MVSSystemFinetune(_ModuleShim):
         intrinsic[:2] /= 4
         return get_ptsvolume(Hv - 2 * self.args.pad, Wv - 2 * self.args.pad, Dv, self.args.pad, self.near_far_source, intrinsic, c2w).contiguous()
 
-    def update_density_volume(self):
+    def update_density_volume(self, render_space=False, dilate=0):
         """:91-99: sigma of every voxel centre from the current volume + MLP (forward_alpha queries), -> (D,H,W).
         Under --use_density_volume the voxel positions and colour features are the ones __init__ built.  Any other system builds what is missing
         on first use (render_rays(skip_empty=) needs the density of a scene that was fine-tuned without importance sampling); a colour volume's
-        feature rows are its own 8 + 4V channels - the colours were projected into it once, :79-80."""
+        feature rows are its own 8 + 4V channels - the colours were projected into it once, :79-80.
+        render_space=False (default) is that reference-faithful volume, bit for bit: like :76,98 it hands the MLP the WORLD positions of the voxel
+        centres as its point input, where the renderer hands it NDC coordinates (renderer.py:156) - so its values are not the sigma the ray march
+        sees at those voxels.  It is what the reference's importance sampling (args.N_importance) was trained and tuned with: keep it for that.
+        render_space=True builds the renderer-consistent volume instead (ops.node_density: the ray march's own lookups and MLP entry at the nodes'
+        NDC coordinates; dilate widens the occupied region, ops.max_dilate3d) - the one to use with render_rays(skip_empty=): a sample is dropped
+        because the density the renderer would compute around it is below the threshold, not because another function of the same weights is
+        (DESIGN.md 4e, 4f).  dilate is read with render_space=True only."""
+        if render_space:
+            V = self.imgs.shape[1]
+            vol = self.volume.feat_volume.detach()
+            color_vol = vol.shape[1] != 8
+            H, W = self.imgs.shape[-2:]
+            src = {} if color_vol else dict(imgs=self.imgs[0].contiguous(), intrinsics=self.pose_source["intrinsics"][:V].contiguous(),
+                                            camera=dict(K_ref=self.pose_source["intrinsics"][0], c2w_ref=self.pose_source["c2ws"][0],
+                                                        near_far=self.near_far_source, ref_hw=(int(H), int(W)), pad=self.args.pad,
+                                                        lindisp=bool(getattr(self.args, "use_disp", False))))
+            with torch.no_grad():
+                self.density_volume = ops.node_density(ops.channels_last_volume(vol), self.network_fn.packed(self.args.feat_dim),
+                                                       self.pose_source["w2cs"][:V].contiguous(), dilate=dilate, **src,
+                                                       **self.network_fn.packed_alt(self.args.feat_dim))
+            return
         from .renderer import render_density
         with torch.no_grad():
             Dv, Hv, Wv = self.volume.feat_volume.shape[-3:]
@@ -879,7 +1001,8 @@ class MVSSystemFusion(_ModuleShim):
     that volume becomes the learnable `RefVolume` (checkpoint key `volume.feat_volume`) which is fine-tuned and rendered with rays clipped to the
     box, through the colour-volume ray march.
     Left out: importance sampling (`args.N_importance > 0` raises - the reference's own calls, :259-260 and :312-313, hand `N_importance=` and
-    `density_volume=` to a ray_marcher without such parameters and raise TypeError as shipped) and `update_density_volume` with it."""
+    `density_volume=` to a ray_marcher without such parameters and raise TypeError as shipped) and the reference's `update_density_volume` with it;
+    the method of that name here is an extension - the renderer-consistent density render_rays(skip_empty=) tests samples against."""
 
     def __init__(self, args, views, bbox_3d, img_wh, focal, n_depth_planes=128):
         """views: one entry per scene camera, (imgs (1,3,3,H,W) normalised, proj_mats (1,3,3,4), near_far (2,), pose_source dict, c2w (4,4) | (3,4)) -
@@ -989,11 +1112,35 @@ class MVSSystemFusion(_ModuleShim):
 
     # -- rendering the fused scene -----------------------------------------------------------------
     @torch.no_grad()
-    def render_rays(self, rays, chunk=None, batch_rays=65536):
+    def update_density_volume(self, dilate=0):
+        """The density of the fused, fine-tuned scene in the renderer's frame: ops.node_density over the nodes of the box volume (a colour volume: one
+        lookup per node, no camera; the node coordinates are box coordinates, x -> W, y -> H, z -> D, as ops.ray_march_bbox forms them) ->
+        self.density_volume, in the (1,1,D,H,W) shape fuse_local_volumes leaves.  Until the first call that attribute is the FUSED density of the
+        splat (fusion.VolumeFuser.finish: the alpha sums over the weight sums of the per-view renders, with the reference's corner weights), which
+        knows nothing of what fine-tuning did to the volume since; dilate widens the occupied region (ops.max_dilate3d)."""
+        self._need_volume()
+        vol = self.volume.feat_volume.detach()
+        net = self.network_fn
+        F = self.args.feat_dim
+        dens = ops.node_density(ops.channels_last_volume(vol), net.packed(F), self.pose_source_ref["w2cs"][:(F - 8) // 4].contiguous(), dilate=dilate,
+                                **net.packed_alt(F))
+        self.density_volume = dens.view(1, 1, *dens.shape)
+        return self.density_volume
+
+    @torch.no_grad()
+    def render_rays(self, rays, chunk=None, batch_rays=65536, skip_empty=None):
         """The rendering part of validation_step (:307-324) for rays (N,8): per chunk ops.ray_march_bbox -> rendering, the chunks of up to batch_rays
         rays issued as one renderer.rendering_batched call; chunk ranges are sharded over the ranks as in MVSSystemFinetune.render_rays.
-        Returns (rgb (N,3), depth (N,))."""
+        Returns (rgb (N,3), depth (N,)).
+        skip_empty: None (default) is the dense render above, untouched.  A float is a density threshold: per sub-batch of batch_rays
+        rays ops.ray_march_bbox -> ops.raymarch_sparse against `self.density_volume` - the fused density of the splat, or the renderer-consistent one
+        after update_density_volume(); the sub-batches are sharded over the ranks and `self.last_live_fraction` is this rank's live samples over its
+        samples."""
         from .renderer import rendering_batched
+        if skip_empty is not None:          # refusals first: nothing below needs the library before them
+            skip_empty = float(skip_empty)
+            if skip_empty != skip_empty:
+                raise ValueError("render_rays: skip_empty is NaN (a density threshold, or None for the dense render)")
         self._need_volume()
         args = self.args
         chunk = int(chunk or args.chunk)
@@ -1002,6 +1149,32 @@ class MVSSystemFusion(_ModuleShim):
         N = rays.shape[0]
         if N == 0:
             return torch.empty((0, 3), device=dev), torch.empty((0,), device=dev)
+        if skip_empty is not None:
+            net, kw = self.network_fn, self.render_kwargs_train
+            if not (isinstance(net, MVSNeRF) and getattr(kw.get("network_query_fn"), "_mvsnerf_fused", False)):
+                raise NotImplementedError("render_rays: skip_empty needs the fused configuration (what create_nerf_mvs builds)")
+            vol = self.volume.feat_volume
+            density = self.density_volume.reshape(vol.shape[-3:]).to(dev, torch.float32).contiguous()      # (1,1,D,H,W) as finish() leaves it
+            vol_cl = ops.channels_last_volume(vol)
+            F = args.feat_dim
+            w2cs = self.pose_source_ref["w2cs"][:(F - 8) // 4].contiguous()
+            packed, alt = net.packed(F), net.packed_alt(F)
+            white = bool(kw.get("white_bkgd", getattr(args, "white_bkgd", False)))
+            lindisp = getattr(args, "use_disp", False)
+            B = max(int(batch_rays), 1)
+            t = torch.linspace(0, 1, args.N_samples, device=dev)
+            live = [0, 0]                   # live samples, samples
+
+            def render_batch(idx):
+                r = rays[idx * B:(idx + 1) * B]
+                pts, ndc, z = ops.ray_march_bbox(r, self.bbox_3d, args.N_samples, lindisp=lindisp, t=t)
+                o = ops.raymarch_sparse(vol_cl, None, w2cs, None, packed, pts, ndc, z, r[:, 3:6].contiguous(), density, skip_empty, white_bkgd=white, **alt)
+                live[0] += o["n_live"]
+                live[1] += z.numel()
+                return o["rgb_map"], o["depth"]
+            out = D.render_frame(render_batch, 1, N, B)
+            self.last_live_fraction = live[0] / live[1] if live[1] else 0.0
+            return out
         n_chunks = (N + chunk - 1) // chunk
         world, rank = D.world_rank()
         lo, hi = D.shard_range(n_chunks, world, rank)
