@@ -387,11 +387,19 @@ int mvsnerf_frame_u8_fwd(const float* rgb, const float* depth, int H, int W, con
  * expand_rows: dst[P][C] with dst[idx[j]] = src[j] for j < min(count[0], src_rows) and every other row zero; every element of dst is written by the call.
  *   idx ascending as live_samples leaves it (an entry can only ever select a row of dst: it is range-checked per tile); count is read on the device, so
  *   a caller that sized src from an earlier read of it needs no second one.  src / idx may be NULL with src_rows == 0.
- *   MVSNERF_EINVAL: NULL count / dst, src_rows < 0 or > P, P < 0, C < 1; MVSNERF_EUNSUPPORTED: C > 64, P >= 2^31; MVSNERF_EALIGN (4 bytes). */
+ *   MVSNERF_EINVAL: NULL count / dst, src_rows < 0 or > P, P < 0, C < 1; MVSNERF_EUNSUPPORTED: C > 64, P >= 2^31; MVSNERF_EALIGN (4 bytes).
+ * compact_rows: the inverse, dst[dst_rows][C] with dst[j] = src[idx[j]] for j < min(count[0], dst_rows), src [P][C], and every other row zero; every
+ *   element of dst is written by the call.  It brings the dense d_raw of the compositing backward down to the live rows of a training step that skips
+ *   empty space (ops.raymarch_sparse_train).  count is read on the device.  An idx[j] outside [0, P) gives a zero row: the entry is range-checked
+ *   before the load, src is never read outside its P rows, whatever idx holds.  C == 4 with 16-byte aligned src and dst moves one 16-byte load and
+ *   one 16-byte store per row (4 + 16 + 16 bytes per live row, 16 per dead one); other C one element per thread.  One launch, no atomics, no LDS.
+ *   src / idx may be NULL with dst_rows == 0, which launches nothing.
+ *   MVSNERF_EINVAL: NULL count / dst, P < 0, dst_rows < 0 or > P, C < 1; MVSNERF_EUNSUPPORTED: C > 64, P >= 2^31; MVSNERF_EALIGN (4 bytes). */
 size_t mvsnerf_live_samples_workspace_bytes(int64_t P);
 int mvsnerf_live_samples_fwd(const float* density, int D, int H, int W, float thr, const float* ndc, const float* pts, const float* rays_dir,
                              int64_t N, int S, int* count, int* idx, float* ndc_c, float* pts_c, float* dir_c, void* workspace, void* stream);
 int mvsnerf_expand_rows_fwd(const float* src, const int* idx, const int* count, int64_t src_rows, int64_t P, int C, float* dst, void* stream);
+int mvsnerf_compact_rows_fwd(const float* src, const int* idx, const int* count, int64_t P, int64_t dst_rows, int C, float* dst, void* stream);
 /* ---- a density volume in the renderer's own frame (no reference counterpart; csrc/occupancy.hip) ----
  * voxel_points: the nodes (k,j,i) of planes [d0, d1) of a [D][H][W] volume, rows in [k][j][i] order: ndc[(d1-d0) H W][3] = (i/(W-1), j/(H-1), k/(D-1)), IEEE
  *   divisions, 0 on an axis of size 1 - the coordinates whose trilinear cell starts exactly on the node, whether the volume is a reference frustum or a

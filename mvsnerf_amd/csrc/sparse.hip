@@ -17,6 +17,10 @@
 // expand_rows_kernel   dst[idx[j]] = src[j], every other row zero, every row written once: a workgroup owns ER_TILE consecutive rows of dst, finds
 //                      the first j with idx[j] >= its first row by one binary search (idx is ascending), and marks its rows' j in LDS.  An idx
 //                      entry can only ever select a row of the workgroup's own tile, whatever the buffer holds.
+// compact_rows_kernel  the inverse, for the backward of a training step that skips empty space: dst[j] = src[idx[j]] for j < count, every other row of
+//                      dst zero, every row written once.  A thread owns a row (C == 4: one 16-byte load and store) or an element (other C); idx[j] is
+//                      range-checked against [0, P) before the load, so a stale or foreign idx gives zero rows, never a read outside src.  The stores
+//                      are consecutive; the loads follow the ascending idx (a gather: 16 of every 64-byte line at a live fraction of 1/4).
 #include "common.h"
 #include "density_cell.h"
 #include <math.h>
@@ -166,6 +170,34 @@ __global__ __launch_bounds__(ER_THREADS) void expand_rows_kernel(const float* __
     }
 }
 
+template <bool VEC4>
+__global__ __launch_bounds__(ER_THREADS) void compact_rows_kernel(const float* __restrict__ src, const int* __restrict__ idx, const int* __restrict__ count,
+                                                                  int64_t P, int64_t dst_rows, int C, float* __restrict__ dst)
+{
+    int64_t n = *count;
+    n = n < 0 ? 0 : (n > dst_rows ? dst_rows : n);                      // never past what dst and idx hold
+    const int64_t t = (int64_t)blockIdx.x * ER_THREADS + threadIdx.x;
+    if (VEC4) {
+        if (t >= dst_rows) return;
+        f32x4 v = {0.f, 0.f, 0.f, 0.f};
+        if (t < n) {
+            const int64_t r = idx[t];
+            if (r >= 0 && r < P) v = reinterpret_cast<const f32x4*>(src)[r];
+        }
+        reinterpret_cast<f32x4*>(dst)[t] = v;
+    } else {
+        if (t >= dst_rows * C) return;
+        const int64_t j = t / C;
+        const int c = (int)(t - j * C);
+        float v = 0.f;
+        if (j < n) {
+            const int64_t r = idx[j];
+            if (r >= 0 && r < P) v = src[r * C + c];
+        }
+        dst[t] = v;
+    }
+}
+
 }  // namespace
 
 extern "C" size_t mvsnerf_live_samples_workspace_bytes(int64_t P)
@@ -219,6 +251,23 @@ extern "C" int mvsnerf_expand_rows_fwd(const float* src, const int* idx, const i
         expand_rows_kernel<true><<<grid, ER_THREADS, 0, st>>>(src, idx, count, src_rows, P, C, dst);
     else
         expand_rows_kernel<false><<<grid, ER_THREADS, 0, st>>>(src, idx, count, src_rows, P, C, dst);
+    MVS_LAUNCH_CHECK();
+    return MVSNERF_OK;
+}
+
+extern "C" int mvsnerf_compact_rows_fwd(const float* src, const int* idx, const int* count, int64_t P, int64_t dst_rows, int C, float* dst, void* stream)
+{
+    if (!count || !dst || P < 0 || dst_rows < 0 || C < 1 || dst_rows > P) return MVSNERF_EINVAL;
+    if (dst_rows > 0 && (!src || !idx)) return MVSNERF_EINVAL;
+    if (C > ER_MAX_C || P >= ((int64_t)1 << 31)) return MVSNERF_EUNSUPPORTED;
+    auto mis = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) != 0; };
+    if (mis(src) || mis(idx) || mis(count) || mis(dst)) return MVSNERF_EALIGN;
+    if (dst_rows == 0) return MVSNERF_OK;
+    hipStream_t st = (hipStream_t)stream;
+    if (C == 4 && mvs_aligned16(src) && mvs_aligned16(dst))
+        compact_rows_kernel<true><<<mvs_cdiv(dst_rows, ER_THREADS), ER_THREADS, 0, st>>>(src, idx, count, P, dst_rows, C, dst);
+    else
+        compact_rows_kernel<false><<<mvs_cdiv(dst_rows * C, ER_THREADS), ER_THREADS, 0, st>>>(src, idx, count, P, dst_rows, C, dst);     // fewer than 2^37 elements: the grid fits 32 bits
     MVS_LAUNCH_CHECK();
     return MVSNERF_OK;
 }

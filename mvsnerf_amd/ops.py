@@ -837,6 +837,29 @@ def expand_rows(src, idx, count, P, out=None):
     return dst
 
 
+def compact_rows(src, idx, count, n_rows, out=None):
+    """dst (n_rows,C) with dst[j] = src[idx[j]] for j < count and every other row zero (mvsnerf_compact_rows_fwd), the inverse of expand_rows:
+    src (P,C) fp32, idx / count as ops.live_samples returns them (count is read on the device and clamped to n_rows; an idx entry outside [0, P)
+    gives a zero row).  Every element of dst is written, whatever it held (out: a caller-owned contiguous fp32 (n_rows,C) tensor to write into)."""
+    _need_no_grad(src, op="compact_rows")
+    if src.dim() != 2:
+        raise RuntimeError(f"compact_rows: src must be (P,C), got {tuple(src.shape)}")
+    P, C = int(src.shape[0]), int(src.shape[1])
+    n = int(n_rows)
+    if not (idx.dtype == torch.int32 and idx.is_cuda and idx.is_contiguous() and count.dtype == torch.int32 and count.is_cuda and count.numel() == 1):
+        raise RuntimeError("compact_rows: idx and count are the int32 device tensors of ops.live_samples")
+    if n < 0 or n > P or idx.numel() < n:
+        raise RuntimeError(f"compact_rows: {P} source rows, {idx.numel()} indices, {n} destination rows")
+    c = _Keep()
+    dst = torch.empty((n, C), device=src.device, dtype=torch.float32) if out is None else out
+    if tuple(dst.shape) != (n, C):
+        raise RuntimeError(f"compact_rows: out must be ({n},{C}), got {tuple(dst.shape)}")
+    if n:               # an empty destination has no row to write (and an empty tensor no address to hand over)
+        dev_f32(dst, "compact_rows: out")
+        check(_lib.lib().mvsnerf_compact_rows_fwd(c(src, "src"), idx.data_ptr(), count.data_ptr(), P, n, C, dst.data_ptr(), stream_ptr()), "compact_rows_fwd")
+    return dst
+
+
 def raymarch_sparse(vol_cl, imgs, w2cs, intrinsics, packed, rays_pts, rays_ndc, z_vals, rays_dir, density, thr, white_bkgd=False, want=(), **packed_alt):
     """ops.raymarch's outputs with the radiance MLP run on the live samples only (ops.live_samples of `density` at `thr`): live_samples -> ONE host
     read of the count (the only synchronisation; at 0 neither a gather nor an MLP launch is enqueued) -> ops.gather (ops.gather_colorvol for an
@@ -1204,6 +1227,134 @@ def raymarch_train(volume, imgs, w2cs, intrinsics, net, rays_pts, rays_ndc, z_va
     rgb, feat, weights, depth, alpha, raw = RayMarchFunction.apply(
         volume, imgs, w2cs, intrinsics, rays_pts, rays_ndc, z_vals, rays_dir, white_bkgd, packed, dp_samples, *params)
     return {"rgb_map": rgb, "input_feat": feat, "weights": weights, "depth": depth, "alpha": alpha, "raw": raw}
+
+
+class SparseRayMarchFunction(torch.autograd.Function):
+    """RayMarchFunction with the radiance MLP - training forward, data gradient, weight gradients - run on the LIVE samples only (ops.live_samples
+    of `density` at `thr`).  A dead sample's raw is the constant (0,0,0,0): it hands no gradient to the MLP or the volume, and the live
+    rows' gradients are those of "dense compositing with the dead rows zeroed".  The stages are the stable-tier entries RayMarchFunction's two calls
+    chain, with N = n_live, S = 1, between live_samples / expand_rows (forward) and compact_rows (backward)."""
+
+    @staticmethod
+    def forward(ctx, volume, imgs, w2cs, intrinsics, rays_pts, rays_ndc, z_vals, rays_dir, density, thr, white_bkgd, packed, dp_samples, *mlp_params):
+        _need_narrow(packed, "raymarch_sparse_train")
+        lib = _lib.lib()
+        vol_cl = channels_last_volume(volume)
+        D, H, W, C = vol_cl.shape
+        N, S = z_vals.shape
+        P = N * S
+        F = 8 + 4 * w2cs.shape[0]
+        if C not in (8, F):
+            raise RuntimeError(f"ray march: the volume has {C} channels; expected 8 or 8 + 4V = {F}")
+        color_vol = C != 8
+        bf16 = training_mlp_mode() == "bf16"
+        dev = rays_ndc.device
+        f32 = dict(device=dev, dtype=torch.float32)
+        count, idx, ndc_c, pts_c, dir_c = live_samples(density, rays_ndc, thr, None if color_vol else rays_pts, rays_dir)
+        n_live = int(count.item())                      # the step's one host read
+        ndc_l = ndc_c[:n_live]
+        raw_c = torch.empty((n_live, 4), **f32)
+        saved = raw_c                                   # no live sample: nothing is stored, the backward reads nothing
+        if n_live:
+            ndc_g, dir_l = ndc_l.view(n_live, 1, 3), dir_c[:n_live]
+            if color_vol:
+                feat, dirs = gather_colorvol(vol_cl, ndc_g, dir_l, w2cs[0].contiguous())
+            else:
+                feat, dirs = gather(vol_cl, imgs, w2cs, intrinsics, pts_c[:n_live].view(n_live, 1, 3), ndc_g, dir_l)
+            saved = torch.empty(lib.mvsnerf_mlp_saved_floats(n_live) // (2 if bf16 else 1), **f32)      # per LIVE point; bf16 mode: two-byte slots
+            if bf16:
+                packed_b = mlp_pack_bf16([p.detach() for p in mlp_params[0::2]], F)
+                check(lib.mvsnerf_mlp_fwd_bf16_train(packed_b.data_ptr(), packed.data_ptr(), F, ndc_l.data_ptr(), 3, feat.data_ptr(), F, dirs.data_ptr(), 3,
+                                                     n_live, 1, raw_c.data_ptr(), saved.data_ptr(), stream_ptr()), "mlp_fwd_bf16_train")
+            else:
+                check(lib.mvsnerf_mlp_fwd_train(packed.data_ptr(), F, ndc_l.data_ptr(), 3, feat.data_ptr(), F, dirs.data_ptr(), 3,
+                                                n_live, 1, raw_c.data_ptr(), saved.data_ptr(), stream_ptr()), "mlp_fwd_train")
+        raw = expand_rows(raw_c, idx, count, P).view(N, S, 4)
+        rgb, disp, acc, depth = (torch.empty(sh, **f32) for sh in ((N, 3), (N,), (N,), (N,)))
+        weights, alpha = torch.empty((N, S), **f32), torch.empty((N, S), **f32)
+        check(lib.mvsnerf_composite_fwd(raw.data_ptr(), dev_f32(z_vals, "z_vals"), N, S, int(bool(white_bkgd)), rgb.data_ptr(), disp.data_ptr(), acc.data_ptr(),
+                                        weights.data_ptr(), depth.data_ptr(), alpha.data_ptr(), stream_ptr()), "composite_fwd")
+        ctx.save_for_backward(z_vals, raw, raw_c, ndc_l, idx, count, packed, saved, *mlp_params)
+        ctx.meta = (tuple(volume.shape), (D, H, W, C), N, S, F, bool(white_bkgd), bf16, bool(dp_samples), n_live)
+        ctx.mark_non_differentiable(raw)
+        return rgb, weights, depth, alpha, raw, n_live
+
+    @staticmethod
+    def backward(ctx, g_rgb, g_weights, g_depth, g_alpha, g_raw, _g_n_live):
+        lib = _lib.lib()
+        _cl_cache.pop("last", None)              # do not keep the step's volume storage past its backward (channels_last_volume)
+        z_vals, raw, raw_c, ndc_l, idx, count, packed, saved, *mlp_params = ctx.saved_tensors
+        vshape, (D, H, W, C), N, S, F, white, bf16, dp_samples, n_live = ctx.meta
+        dev = raw.device
+        f32 = dict(device=dev, dtype=torch.float32)
+        views = [torch.empty_like(p, memory_format=torch.contiguous_format) for p in mlp_params]
+        torch._foreach_zero_(views)
+        gws, gbs = views[0::2], views[1::2]
+        gvol_cl = torch.zeros((D, H, W, C), **f32) if ctx.needs_input_grad[0] else None
+        d_feat = torch.empty((n_live, C), **f32)
+        if n_live:
+            grads_in = [None if g is None else g.contiguous() for g in (g_rgb, g_depth, g_weights, g_alpha)]       # kept alive until the launch
+            ptr = lambda t: 0 if t is None else dev_f32(t, "grad")
+            d_raw = torch.empty((N * S, 4), **f32)
+            check(lib.mvsnerf_composite_bwd(raw.data_ptr(), z_vals.data_ptr(), N, S, int(white), ptr(grads_in[0]), ptr(grads_in[1]), 0, ptr(grads_in[2]),
+                                            ptr(grads_in[3]), d_raw.data_ptr(), stream_ptr()), "composite_bwd")
+            d_raw_c = compact_rows(d_raw, idx, count, n_live)
+            weights = [p.detach() for p in mlp_params[0::2]]
+            packed_bwd = mlp_pack_bwd_bf16(weights, F) if bf16 else mlp_pack_bwd(weights, F)
+            gslots = torch.empty(lib.mvsnerf_mlp_gradslot_floats(n_live) // (2 if bf16 else 1), **f32)
+            ws = torch.empty(lib.mvsnerf_mlp_bwd_workspace_floats(), **f32)
+            gwp = (ctypes.c_void_p * 11)(*[g.data_ptr() for g in gws])
+            gbp = (ctypes.c_void_p * 11)(*[g.data_ptr() for g in gbs])
+            maps = _mlp_bwd_maps(F, dev)
+            fn = lib.mvsnerf_mlp_bwd_bf16 if bf16 else lib.mvsnerf_mlp_bwd
+            check(fn(packed.data_ptr(), packed_bwd.data_ptr(), F, raw_c.data_ptr(), d_raw_c.data_ptr(), saved.data_ptr(), n_live, 1, gslots.data_ptr(),
+                     d_feat.data_ptr(), C, gwp, gbp, maps.data_ptr(), ws.data_ptr(), stream_ptr()), "mlp_bwd_bf16" if bf16 else "mlp_bwd")
+        if gvol_cl is not None:
+            from . import distributed as DD
+            if dp_samples and DD._collective_needed():
+                if not n_live:                  # a rank without a live sample enters the collective too: one row that scatters zeros
+                    d_feat, ndc_l = torch.zeros((1, C), **f32), torch.zeros((1, 3), **f32)
+                volume_grad_from_all_ranks(d_feat, ndc_l, gvol_cl)
+            elif n_live:
+                _scatter_hip(gvol_cl, ndc_l, d_feat)
+        g_vol = None
+        if gvol_cl is not None:
+            g_vol = gvol_cl.permute(3, 0, 1, 2)
+            if len(vshape) == 5:
+                g_vol = g_vol.unsqueeze(0)
+        return (g_vol, None, None, None, None, None, None, None, None, None, None, None, None, *views)
+
+
+def raymarch_sparse_train(volume, imgs, w2cs, intrinsics, net, rays_pts, rays_ndc, z_vals, rays_dir, density, thr, white_bkgd=False, dp_samples=False):
+    """Differentiable rendering() with empty space skipped: ops.raymarch_train's step with the MLP - training forward, data gradient and
+    the weight-gradient GEMMs - run on the samples that ops.live_samples(density, rays_ndc, thr) calls live.  `net` is a models.MVSNeRF (netwidth
+    128); volume (1,C,D,H,W) | (C,D,H,W) with C = 8 (imgs (V,3,H,W), w2cs (V,4,4), intrinsics (V,3,3) for the colour lookup) or C = 8 + 4V (a colour
+    volume: imgs / intrinsics / rays_pts are not read); density (D',H',W') fp32.  The 22 MLP tensors and the volume receive gradients; rays, images,
+    cameras and `density` do not.
+    Forward: live_samples -> ONE host read of the count (the step's only synchronisation) -> gather / gather_colorvol on the compact rows as
+    (n_live,1,3) -> mvsnerf_mlp_fwd_train (mvsnerf_mlp_fwd_bf16_train under training_mlp_mode() == "bf16") with N = n_live, S = 1, its activation
+    store sized for the live points -> expand_rows into raw (N,S,4) -> mvsnerf_composite_fwd.  Backward: mvsnerf_composite_bwd on the dense raw ->
+    compact_rows to (n_live,4) -> the MLP backward on the live rows -> the volume scatter on the compact NDC rows (float atomics,
+    VOLUME_BWD_DETERMINISTIC, or volume_grad_from_all_ranks under dp_samples).  A dead sample's raw is the constant (0,0,0,0); with no live sample at
+    all nothing but live_samples, expand_rows and the compositing is launched, and every gradient is zero.
+    Returns a dict: rgb_map (N,3), weights (N,S), depth (N,), alpha (N,S), raw (N,S,4; not differentiable), n_live (int).  There is no input_feat:
+    the dense (N,S,F) feature tensor is never formed."""
+    thr = _thr_f32(thr, "raymarch_sparse_train")
+    if not torch.is_tensor(density) or density.dim() != 3:
+        raise RuntimeError(f"raymarch_sparse_train: density must be (D,H,W), got {tuple(getattr(density, 'shape', ()))}")
+    if getattr(net.nerf, "W", 128) != 128:      # before packed(): nothing is packed or launched for a width that cannot be trained
+        raise _wide_refusal("raymarch_sparse_train")
+    if training_mlp_mode() not in ("fp32", "bf16"):
+        raise RuntimeError(f"training runs the MLP in 'fp32' or 'bf16' (ops.set_mlp_precision), not {MLP_PRECISION!r}")
+    net.nerf.need_fp32_mode(MLP_PRECISION)      # net_type v2 under bf16
+    V = w2cs.shape[0]
+    params = []
+    for l in net.nerf._linears():
+        params += [l.weight, l.bias]
+    packed = net.packed(8 + 4 * V)
+    rgb, weights, depth, alpha, raw, n_live = SparseRayMarchFunction.apply(
+        volume, imgs, w2cs, intrinsics, rays_pts, rays_ndc, z_vals, rays_dir, density.detach(), thr, white_bkgd, packed, dp_samples, *params)
+    return {"rgb_map": rgb, "weights": weights, "depth": depth, "alpha": alpha, "raw": raw, "n_live": n_live}
 
 
 # ------------------------------------------------------------------ frame metrics

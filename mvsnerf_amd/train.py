@@ -153,6 +153,9 @@ class MVSSystem(_ModuleShim):
     def training_step(self, batch, batch_nb):
         """:104-168.  Returns {'loss': loss}; gradients are left to the caller (Lightning or `fit_steps`)."""
         args = self.args
+        if getattr(args, "skip_empty_train", None) is not None:
+            raise ValueError("MVSSystem.training_step: args.skip_empty_train is set, but generalizable training encodes a new scene every step and "
+                             "holds no density volume to test samples against; the switch is for MVSSystemFinetune and MVSSystemFusion (DESIGN.md 4g)")
         batch = dict(batch)
         batch.pop("scan", None)
         data_mvs, pose_ref = self.decode_batch(batch)
@@ -616,6 +619,45 @@ def ray_marcher_fine(rays, density_volume, z_vals, pts_NDC, N_importance=64, lin
     return xyz, rays_o, rays_d, z
 
 
+def _skip_empty_train(args):
+    """The switch of DESIGN.md 4g, read from args so that default_args stays as it is: None (args.skip_empty_train unset or None: the dense step), or
+    (threshold, dilate, refresh): args.skip_empty_dilate (default 1 voxel, 4f's recommendation) and args.skip_empty_refresh (default 200 steps,
+    train_mvs_nerf_finetuning_pl.py:144-145's cadence)."""
+    thr = getattr(args, "skip_empty_train", None)
+    if thr is None:
+        return None
+    thr = float(thr)
+    if thr != thr:
+        raise ValueError("args.skip_empty_train is NaN (a density threshold, or None for the dense step)")
+    refresh = int(getattr(args, "skip_empty_refresh", 200))
+    if refresh < 1:
+        raise ValueError(f"args.skip_empty_refresh must be >= 1 step, got {refresh}")
+    return thr, int(getattr(args, "skip_empty_dilate", 1)), refresh
+
+
+def _refresh_train_density(system, sparse, build_density):
+    """The training density of a system with args.skip_empty_train set: `system.train_density` (D,H,W), build_density(dilate) on first use and at
+    every later multiple of args.skip_empty_refresh steps (an assigned tensor is kept until then).  system.density_volume is not touched."""
+    _, dilate, refresh = sparse
+    net, kw = system.network_fn, system.render_kwargs_train
+    if not (isinstance(net, MVSNeRF) and getattr(kw.get("network_query_fn"), "_mvsnerf_fused", False)):
+        raise NotImplementedError("args.skip_empty_train needs the fused configuration (what create_nerf_mvs builds)")
+    if getattr(system, "train_density", None) is None or (system.global_step > 0 and system.global_step % refresh == 0):
+        system.train_density = build_density(dilate)
+
+
+def _sparse_training_render(system, sparse, volume, imgs, w2cs, intrinsics, pts, ndc, z_vals, rays_d, dp_samples):
+    """The render call of a fine-tuning step with args.skip_empty_train set: ops.raymarch_sparse_train against system.train_density.  Sets
+    system.last_live_fraction (live samples over samples of this step).  Returns rgb_map."""
+    thr = sparse[0]
+    net, kw = system.network_fn, system.render_kwargs_train
+    white = bool(kw.get("white_bkgd", getattr(system.args, "white_bkgd", False)))
+    o = ops.raymarch_sparse_train(volume, imgs, w2cs, intrinsics, net, pts.contiguous(), ndc.contiguous(), z_vals.contiguous(), rays_d.contiguous(),
+                                  system.train_density, thr, white_bkgd=white, dp_samples=dp_samples)
+    system.last_live_fraction = o["n_live"] / z_vals.numel() if z_vals.numel() else 0.0
+    return o["rgb_map"]
+
+
 class MVSSystemFinetune(_ModuleShim):
     """reference train_mvs_nerf_finetuning_pl.py:32-189: the scene is encoded ONCE (`init_volume`), the 8-channel
     volume becomes a learnable `RefVolume` (checkpoint key `volume.feat_volume`) and only the ray march runs per step;
@@ -696,6 +738,22 @@ class MVSSystemFinetune(_ModuleShim):
         intrinsic[:2] /= 4
         return get_ptsvolume(Hv - 2 * self.args.pad, Wv - 2 * self.args.pad, Dv, self.args.pad, self.near_far_source, intrinsic, c2w).contiguous()
 
+    def _render_space_density(self, dilate=0):
+        """The renderer-consistent density of the current volume and MLP -> (D,H,W): what update_density_volume(render_space=True) assigns to
+        self.density_volume and what a step with args.skip_empty_train keeps in self.train_density."""
+        V = self.imgs.shape[1]
+        vol = self.volume.feat_volume.detach()
+        color_vol = vol.shape[1] != 8
+        H, W = self.imgs.shape[-2:]
+        src = {} if color_vol else dict(imgs=self.imgs[0].contiguous(), intrinsics=self.pose_source["intrinsics"][:V].contiguous(),
+                                        camera=dict(K_ref=self.pose_source["intrinsics"][0], c2w_ref=self.pose_source["c2ws"][0],
+                                                    near_far=self.near_far_source, ref_hw=(int(H), int(W)), pad=self.args.pad,
+                                                    lindisp=bool(getattr(self.args, "use_disp", False))))
+        with torch.no_grad():
+            return ops.node_density(ops.channels_last_volume(vol), self.network_fn.packed(self.args.feat_dim),
+                                    self.pose_source["w2cs"][:V].contiguous(), dilate=dilate, **src,
+                                    **self.network_fn.packed_alt(self.args.feat_dim))
+
     def update_density_volume(self, render_space=False, dilate=0):
         """:91-99: sigma of every voxel centre from the current volume + MLP (forward_alpha queries), -> (D,H,W).
         Under --use_density_volume the voxel positions and colour features are the ones __init__ built.  Any other system builds what is missing
@@ -709,18 +767,7 @@ class MVSSystemFinetune(_ModuleShim):
         because the density the renderer would compute around it is below the threshold, not because another function of the same weights is
         (DESIGN.md 4e, 4f).  dilate is read with render_space=True only."""
         if render_space:
-            V = self.imgs.shape[1]
-            vol = self.volume.feat_volume.detach()
-            color_vol = vol.shape[1] != 8
-            H, W = self.imgs.shape[-2:]
-            src = {} if color_vol else dict(imgs=self.imgs[0].contiguous(), intrinsics=self.pose_source["intrinsics"][:V].contiguous(),
-                                            camera=dict(K_ref=self.pose_source["intrinsics"][0], c2w_ref=self.pose_source["c2ws"][0],
-                                                        near_far=self.near_far_source, ref_hw=(int(H), int(W)), pad=self.args.pad,
-                                                        lindisp=bool(getattr(self.args, "use_disp", False))))
-            with torch.no_grad():
-                self.density_volume = ops.node_density(ops.channels_last_volume(vol), self.network_fn.packed(self.args.feat_dim),
-                                                       self.pose_source["w2cs"][:V].contiguous(), dilate=dilate, **src,
-                                                       **self.network_fn.packed_alt(self.args.feat_dim))
+            self.density_volume = self._render_space_density(dilate)
             return
         from .renderer import render_density
         with torch.no_grad():
@@ -740,8 +787,14 @@ class MVSSystemFinetune(_ModuleShim):
                                                  self.render_kwargs_train["network_query_fn"]).reshape(Dv, Hv, Wv)
 
     def training_step(self, batch, batch_nb):
-        """:140-189.  batch = {'rays': (1,B,8), 'rgbs': (1,B,3)} from the all-rays buffer."""
+        """:140-189.  batch = {'rays': (1,B,8), 'rgbs': (1,B,3)} from the all-rays buffer.
+        args.skip_empty_train (None / unset: the dense step below, untouched): a density threshold - the MLP's forward and backward run on the samples
+        that are live against self.train_density, the renderer-consistent density of the scene dilated by args.skip_empty_dilate voxels (default 1) and
+        rebuilt every args.skip_empty_refresh steps (default 200); ops.raymarch_sparse_train, DESIGN.md 4g.  self.last_live_fraction is the step's."""
         args = self.args
+        sparse = _skip_empty_train(args)
+        if sparse is not None:
+            _refresh_train_density(self, sparse, self._render_space_density)
         rays, target = batch["rays"].squeeze(0).to(self.imgs.device), batch["rgbs"].squeeze(0).to(self.imgs.device)
         if getattr(args, "use_density_volume", False) and 0 == self.global_step % 200:              # :144-145
             self.update_density_volume()
@@ -757,8 +810,15 @@ class MVSSystemFinetune(_ModuleShim):
             pts, rays_o, rays_d, z_vals = ray_marcher_fine(rays, self.density_volume, z_vals, ndc, N_importance=args.N_importance)
             pts, ndc = to_ndc(z_vals)
         with ops.mlp_precision("bf16" if getattr(args, "use_amp", False) else ops.MLP_PRECISION):
-            rgbs, _, _, depth_pred, _, _ = rendering(args, self.pose_source, pts, ndc, z_vals, rays_o, rays_d, self.volume, self.imgs,
-                                                     **self.render_kwargs_train)
+            if sparse is not None:
+                V = self.imgs.shape[1]
+                vol = self.volume.feat_volume
+                rgbs = _sparse_training_render(self, sparse, vol, self.imgs[0].contiguous(), self.pose_source["w2cs"][:V].contiguous(),
+                                               self.pose_source["intrinsics"][:V].contiguous(), pts, ndc, z_vals, rays_d,
+                                               getattr(args, "dp_volume_grad", "allreduce") == "samples" and vol.requires_grad)
+            else:
+                rgbs, _, _, depth_pred, _, _ = rendering(args, self.pose_source, pts, ndc, z_vals, rays_o, rays_d, self.volume, self.imgs,
+                                                         **self.render_kwargs_train)
         img_loss = img2mse(rgbs, target)
         with torch.no_grad():
             self.log("train/loss", img_loss, prog_bar=True)
@@ -1089,9 +1149,12 @@ class MVSSystemFusion(_ModuleShim):
 
     # -- the step ----------------------------------------------------------------------------------
     def training_step(self, batch, batch_nb):
-        """:251-291.  batch = {'rays': (1,B,8), 'rgbs': (1,B,3)}."""
+        """:251-291.  batch = {'rays': (1,B,8), 'rgbs': (1,B,3)}.
+        args.skip_empty_train (None / unset: the dense step below, untouched): as MVSSystemFinetune.training_step - the training density
+        self.train_density is ops.node_density of the box volume; self.density_volume, the (1,1,D,H,W) density of the splat, is not touched."""
         self._need_volume()
         args = self.args
+        sparse = _skip_empty_train(args)
         if int(getattr(args, "N_importance", 0) or 0) > 0:
             raise NotImplementedError("MVSSystemFusion: args.N_importance > 0 is not supported (see the class docstring)")
         dev = self.bbox_3d.device
@@ -1100,9 +1163,17 @@ class MVSSystemFusion(_ModuleShim):
             jitter = torch.rand((rays.shape[0], args.N_samples), device=dev) if args.perturb > 0 else None
             pts, ndc, z_vals = ops.ray_march_bbox(rays, self.bbox_3d, args.N_samples, lindisp=getattr(args, "use_disp", False),
                                                   perturb=args.perturb, jitter=jitter)
+        if sparse is not None:
+            _refresh_train_density(self, sparse, self._node_density)
         with ops.mlp_precision("bf16" if getattr(args, "use_amp", False) else ops.MLP_PRECISION):
-            rgbs, _, _, _, _, _ = rendering(args, self.pose_source_ref, pts, ndc, z_vals, rays[:, 0:3], rays[:, 3:6].contiguous(), self.volume,
-                                            self.imgs_ref, **self.render_kwargs_train)                       # :266-267
+            if sparse is not None:
+                vol = self.volume.feat_volume
+                rgbs = _sparse_training_render(self, sparse, vol, None, self.pose_source_ref["w2cs"][:(args.feat_dim - 8) // 4].contiguous(), None,
+                                               pts, ndc, z_vals, rays[:, 3:6],
+                                               getattr(args, "dp_volume_grad", "allreduce") == "samples" and vol.requires_grad)
+            else:
+                rgbs, _, _, _, _, _ = rendering(args, self.pose_source_ref, pts, ndc, z_vals, rays[:, 0:3], rays[:, 3:6].contiguous(), self.volume,
+                                                self.imgs_ref, **self.render_kwargs_train)                       # :266-267
         img_loss = img2mse(rgbs, target)
         with torch.no_grad():
             self.log("train/loss", img_loss, prog_bar=True)
@@ -1118,14 +1189,20 @@ class MVSSystemFusion(_ModuleShim):
         self.density_volume, in the (1,1,D,H,W) shape fuse_local_volumes leaves.  Until the first call that attribute is the FUSED density of the
         splat (fusion.VolumeFuser.finish: the alpha sums over the weight sums of the per-view renders, with the reference's corner weights), which
         knows nothing of what fine-tuning did to the volume since; dilate widens the occupied region (ops.max_dilate3d)."""
+        dens = self._node_density(dilate)
+        self.density_volume = dens.view(1, 1, *dens.shape)
+        return self.density_volume
+
+    @torch.no_grad()
+    def _node_density(self, dilate=0):
+        """ops.node_density over the nodes of the box volume -> (D,H,W): what update_density_volume reshapes into self.density_volume and what a step
+        with args.skip_empty_train keeps in self.train_density."""
         self._need_volume()
         vol = self.volume.feat_volume.detach()
         net = self.network_fn
         F = self.args.feat_dim
-        dens = ops.node_density(ops.channels_last_volume(vol), net.packed(F), self.pose_source_ref["w2cs"][:(F - 8) // 4].contiguous(), dilate=dilate,
+        return ops.node_density(ops.channels_last_volume(vol), net.packed(F), self.pose_source_ref["w2cs"][:(F - 8) // 4].contiguous(), dilate=dilate,
                                 **net.packed_alt(F))
-        self.density_volume = dens.view(1, 1, *dens.shape)
-        return self.density_volume
 
     @torch.no_grad()
     def render_rays(self, rays, chunk=None, batch_rays=65536, skip_empty=None):
