@@ -1,5 +1,6 @@
 """Python faces of the C-ABI entry points (include/mvsnerf_hip.h).  Tensors in, tensors out;
 all arithmetic happens in libmvsnerf_hip.so.  No fallbacks."""
+import collections
 import ctypes
 import weakref
 
@@ -344,6 +345,7 @@ def ray_marcher_fine_z(density_volume, rays_ndc, z_vals, u):
 
 # ------------------------------------------------------------------ MLP
 MLP_ORDER = [f"pts_linears.{i}" for i in range(6)] + ["pts_bias", "feature_linear", "alpha_linear", "views_linears.0", "rgb_linear"]
+_Ptr11 = ctypes.c_void_p * 11       # the C entries' `const float* const w[11]`: one pointer per linear, in MLP_ORDER
 
 
 def mlp_pack(weights, biases, F, variant=0):
@@ -362,8 +364,8 @@ def mlp_pack(weights, biases, F, variant=0):
             raise RuntimeError(f"mlp_pack: {name}.weight has shape {tuple(w.shape)}, kernel is specialised for {e} "
                                "(netdepth 6, netwidth 128, skips [4], multires 10, raw 3-d view dirs)")
     packed = torch.empty(n, device=weights[0].device, dtype=torch.float32)
-    wp = (ctypes.c_void_p * 11)(*[dev_f32(w, "weight") for w in weights])
-    bp = (ctypes.c_void_p * 11)(*[dev_f32(b, "bias") for b in biases])
+    wp = _Ptr11(*[dev_f32(w, "weight") for w in weights])
+    bp = _Ptr11(*[dev_f32(b, "bias") for b in biases])
     if variant:
         check(_lib.lib().mvsnerf_mlp_pack_fold_variant(wp, bp, F, int(variant), packed.data_ptr(), stream_ptr()), "mlp_pack")
     else:
@@ -424,8 +426,8 @@ def mlp_pack_wide(weights, biases, F, width=WIDE_WIDTH, variant=0):
     if n == 0:
         raise RuntimeError(f"mlp_pack_wide: feat_dim {F} unsupported (must be even, 4 <= F <= 40)")
     packed = torch.empty(n, device=weights[0].device, dtype=torch.float32)
-    wp = (ctypes.c_void_p * 11)(*[dev_f32(w, "weight") for w in weights])
-    bp = (ctypes.c_void_p * 11)(*[dev_f32(b, "bias") for b in biases])
+    wp = _Ptr11(*[dev_f32(w, "weight") for w in weights])
+    bp = _Ptr11(*[dev_f32(b, "bias") for b in biases])
     check(_lib.lib().mvsnerf_mlp_pack_wide(wp, bp, F, W, int(variant), packed.data_ptr(), stream_ptr()), "mlp_pack_wide")
     return WidePacked(packed, W, F, variant)
 
@@ -515,7 +517,7 @@ def mlp_pack_split(weights, F, n_split):
     if n == 0:
         raise RuntimeError(f"mlp_pack_split: feat_dim {F} / n_split {n_split} unsupported")
     packed = torch.empty(n, device=weights[0].device, dtype=torch.bfloat16)
-    wp = (ctypes.c_void_p * 11)(*[dev_f32(w, "weight") for w in weights])
+    wp = _Ptr11(*[dev_f32(w, "weight") for w in weights])
     check(_lib.lib().mvsnerf_mlp_pack_split(wp, F, n_split, packed.data_ptr(), stream_ptr()), "mlp_pack_split")
     return packed
 
@@ -523,7 +525,7 @@ def mlp_pack_split(weights, F, n_split):
 def mlp_pack_bf16(weights, F):
     n = _lib.lib().mvsnerf_mlp_packed_bf16_elems(F)
     packed = torch.empty(n, device=weights[0].device, dtype=torch.bfloat16)
-    wp = (ctypes.c_void_p * 11)(*[dev_f32(w, "weight") for w in weights])
+    wp = _Ptr11(*[dev_f32(w, "weight") for w in weights])
     check(_lib.lib().mvsnerf_mlp_pack_bf16(wp, F, packed.data_ptr(), stream_ptr()), "mlp_pack_bf16")
     return packed
 
@@ -860,35 +862,45 @@ def compact_rows(src, idx, count, n_rows, out=None):
     return dst
 
 
-def raymarch_sparse(vol_cl, imgs, w2cs, intrinsics, packed, rays_pts, rays_ndc, z_vals, rays_dir, density, thr, white_bkgd=False, want=(), **packed_alt):
-    """ops.raymarch's outputs with the radiance MLP run on the live samples only (ops.live_samples of `density` at `thr`): live_samples -> ONE host
-    read of the count (the only synchronisation; at 0 neither a gather nor an MLP launch is enqueued) -> ops.gather (ops.gather_colorvol for an
-    (8+4V)-channel colour volume, which needs no imgs / intrinsics / rays_pts) on the compact rows as (n_live,1,3) -> ops.mlp_forward(N=n_live, S=1)
-    -> expand_rows into raw (N,S,4) -> ops.composite.  Dead samples have raw = (0,0,0,0), so alpha = weight = 0; live ones the bits of the dense
-    sequence (a sample's MLP column does not depend on its neighbours in the tile).  packed: mlp_pack's buffer or a WidePacked; **packed_alt: the
-    kernel choice of ops.mlp_forward (MVSNeRF.packed_alt).  Returns raw, rgb_map, weights, depth, alpha, disp / acc when in `want`, and n_live (int)."""
-    _need_no_grad(vol_cl, imgs, rays_pts, rays_ndc, z_vals, rays_dir, density, op="raymarch_sparse")
-    thr = _thr_f32(thr, "raymarch_sparse")
+def _sparse_march(vol_cl, imgs, w2cs, intrinsics, rays_pts, rays_ndc, z_vals, rays_dir, density, thr, white_bkgd, mlp):
+    """The sparse ray march both faces run (ops.raymarch_sparse, SparseRayMarchFunction.forward): live_samples of `density` at `thr` -> ONE host read
+    of the count (the only synchronisation; at 0 neither a gather nor an MLP launch is enqueued and raw_c is empty) -> ops.gather (ops.gather_colorvol
+    for an (8+4V)-channel colour volume, which needs no imgs / intrinsics / rays_pts) on the compact rows as (n_live,1,3) -> the MLP stage with
+    N = n_live, S = 1: mlp(ndc_l (n_live,3), feat (n_live,1,F), dirs (n_live,3), n_live) -> raw_c (n_live,4) -> expand_rows into raw (N,S,4) ->
+    ops.composite (mvsnerf_composite_fwd).  Dead samples have raw = (0,0,0,0), so alpha = weight = 0; live ones the bits of the dense sequence (a
+    sample's MLP column does not depend on its neighbours in the tile).
+    Returns (idx, count, ndc_l, raw_c, raw, n_live) - what a backward has to keep - and ops.composite's (rgb_map, disp, acc, weights, depth, alpha)."""
     N, S = z_vals.shape
-    C = vol_cl.shape[-1]
-    color_vol = C != 8
-    F = C if color_vol else 8 + 4 * imgs.shape[0]
-    if color_vol and C != 8 + 4 * w2cs.shape[0]:
-        raise RuntimeError(f"raymarch_sparse: the volume has {C} channels, 8 + 4V is {8 + 4 * w2cs.shape[0]}")
-    dev = rays_ndc.device
+    color_vol = vol_cl.shape[-1] != 8
     count, idx, ndc_c, pts_c, dir_c = live_samples(density, rays_ndc, thr, None if color_vol else rays_pts, rays_dir)
     n_live = int(count.item())
+    ndc_l = ndc_c[:n_live]
     if n_live:
-        ndc_l, dir_l = ndc_c[:n_live].view(n_live, 1, 3), dir_c[:n_live]
+        ndc_g, dir_l = ndc_l.view(n_live, 1, 3), dir_c[:n_live]
         if color_vol:
-            feat, dirs = gather_colorvol(vol_cl, ndc_l, dir_l, w2cs[0].contiguous())
+            feat, dirs = gather_colorvol(vol_cl, ndc_g, dir_l, w2cs[0].contiguous())
         else:
-            feat, dirs = gather(vol_cl, imgs, w2cs, intrinsics, pts_c[:n_live].view(n_live, 1, 3), ndc_l, dir_l)
-        raw_c = mlp_forward(packed, F, ndc_l.data_ptr(), 3, feat.data_ptr(), F, dirs.data_ptr(), 3, n_live, 1, 0, dev, **packed_alt)
+            feat, dirs = gather(vol_cl, imgs, w2cs, intrinsics, pts_c[:n_live].view(n_live, 1, 3), ndc_g, dir_l)
+        raw_c = mlp(ndc_l, feat, dirs, n_live)
     else:
-        raw_c = torch.empty((0, 4), device=dev, dtype=torch.float32)
+        raw_c = torch.empty((0, 4), device=rays_ndc.device, dtype=torch.float32)
     raw = expand_rows(raw_c, idx, count, N * S).view(N, S, 4)
-    rgb, disp, acc, weights, depth, alpha = composite(raw, z_vals, white_bkgd)
+    return (idx, count, ndc_l, raw_c, raw, n_live), composite(raw, z_vals, white_bkgd)
+
+
+def raymarch_sparse(vol_cl, imgs, w2cs, intrinsics, packed, rays_pts, rays_ndc, z_vals, rays_dir, density, thr, white_bkgd=False, want=(), **packed_alt):
+    """ops.raymarch's outputs with the radiance MLP run on the live samples only (ops.live_samples of `density` at `thr`): the sequence of
+    _sparse_march with ops.mlp_forward as its MLP stage.  packed: mlp_pack's buffer or a WidePacked; **packed_alt: the kernel choice of
+    ops.mlp_forward (MVSNeRF.packed_alt).  Returns raw, rgb_map, weights, depth, alpha, disp / acc when in `want`, and n_live (int)."""
+    _need_no_grad(vol_cl, imgs, rays_pts, rays_ndc, z_vals, rays_dir, density, op="raymarch_sparse")
+    thr = _thr_f32(thr, "raymarch_sparse")
+    C = vol_cl.shape[-1]
+    F = C if C != 8 else 8 + 4 * imgs.shape[0]
+    if C != 8 and C != 8 + 4 * w2cs.shape[0]:
+        raise RuntimeError(f"raymarch_sparse: the volume has {C} channels, 8 + 4V is {8 + 4 * w2cs.shape[0]}")
+    (_, _, _, _, raw, n_live), (rgb, disp, acc, weights, depth, alpha) = _sparse_march(
+        vol_cl, imgs, w2cs, intrinsics, rays_pts, rays_ndc, z_vals, rays_dir, density, thr, white_bkgd,
+        lambda ndc_l, feat, dirs, n: mlp_forward(packed, F, ndc_l.data_ptr(), 3, feat.data_ptr(), F, dirs.data_ptr(), 3, n, 1, 0, rays_ndc.device, **packed_alt))
     out = {"raw": raw, "rgb_map": rgb, "weights": weights, "depth": depth, "alpha": alpha, "n_live": n_live}
     out.update({k: v for k, v in (("disp", disp), ("acc", acc)) if k in want})
     return out
@@ -1047,7 +1059,7 @@ def mlp_pack_bwd_bf16(weights, F):
     _need_narrow(weights, "mlp_pack_bwd_bf16")
     n = _lib.lib().mvsnerf_mlp_packed_bwd_bf16_elems()
     packed = torch.empty(n, device=weights[0].device, dtype=torch.bfloat16)
-    wp = (ctypes.c_void_p * 11)(*[dev_f32(w, "weight") for w in weights])
+    wp = _Ptr11(*[dev_f32(w, "weight") for w in weights])
     check(_lib.lib().mvsnerf_mlp_pack_bwd_bf16(wp, F, packed.data_ptr(), stream_ptr()), "mlp_pack_bwd_bf16")
     return packed
 
@@ -1056,9 +1068,34 @@ def mlp_pack_bwd(weights, F):
     _need_narrow(weights, "mlp_pack_bwd")
     n = _lib.lib().mvsnerf_mlp_packed_bwd_floats()
     packed = torch.empty(n, device=weights[0].device, dtype=torch.float32)
-    wp = (ctypes.c_void_p * 11)(*[dev_f32(w, "weight") for w in weights])
+    wp = _Ptr11(*[dev_f32(w, "weight") for w in weights])
     check(_lib.lib().mvsnerf_mlp_pack_bwd(wp, F, packed.data_ptr(), stream_ptr()), "mlp_pack_bwd")
     return packed
+
+
+_BwdSetup = collections.namedtuple("_BwdSetup", "grads packed_bwd gslots ws maps gwp gbp g_in g_ptr")
+
+
+def _bwd_setup(mlp_params, F, bf16, n_points, g_in, dev):
+    """What both ray-march backwards hold before their MLP stage on n_points points: grads (the 22 gradient tensors, in mlp_params' order), packed_bwd
+    (the weight re-pack for the transposed products), gslots, ws, maps, the pointer arrays gwp / gbp into grads, and g_in with g_ptr - the incoming
+    gradients, contiguous and kept alive until the launch, and their addresses (0 for None).  n_points = 0: grads only, every other field None."""
+    _cl_cache.pop("last", None)              # do not keep the step's volume storage past its backward (channels_last_volume)
+    # 22 gradient tensors of their own, zeroed by ONE multi-tensor launch.  (They used to be views of one zero-filled buffer: autograd's
+    # AccumulateGrad clones a gradient that does not own its storage - 22 device copies per step in the kernel trace.)
+    grads = [torch.empty_like(p, memory_format=torch.contiguous_format) for p in mlp_params]
+    torch._foreach_zero_(grads)
+    if not n_points:
+        return _BwdSetup(grads, *[None] * 8)
+    lib = _lib.lib()
+    f32 = dict(device=dev, dtype=torch.float32)
+    g_in = [None if g is None else g.contiguous() for g in g_in]
+    weights = [p.detach() for p in mlp_params[0::2]]
+    return _BwdSetup(grads, mlp_pack_bwd_bf16(weights, F) if bf16 else mlp_pack_bwd(weights, F),
+                     torch.empty(lib.mvsnerf_mlp_gradslot_floats(n_points) // (2 if bf16 else 1), **f32),
+                     torch.empty(lib.mvsnerf_mlp_bwd_workspace_floats(), **f32), _mlp_bwd_maps(F, dev),
+                     _Ptr11(*[g.data_ptr() for g in grads[0::2]]), _Ptr11(*[g.data_ptr() for g in grads[1::2]]),
+                     g_in, [0 if g is None else dev_f32(g, "grad") for g in g_in])
 
 
 class RayMarchFunction(torch.autograd.Function):
@@ -1077,9 +1114,7 @@ class RayMarchFunction(torch.autograd.Function):
         F = 8 + 4 * V
         if C not in (8, F):
             raise RuntimeError(f"ray march: the volume has {C} channels; expected 8 or 8 + 4V = {F}")
-        if training_mlp_mode() not in ("fp32", "bf16"):
-            raise RuntimeError(f"training runs the MLP in 'fp32' or 'bf16' (ops.set_mlp_precision), not {MLP_PRECISION!r}")
-        bf16 = training_mlp_mode() == "bf16"
+        bf16 = training_mlp_mode() == "bf16"            # 'fp32' or 'bf16': _train_entry has refused every other mode
         dev = rays_pts.device
         f32 = dict(device=dev, dtype=torch.float32)
         feat = torch.empty((N, S, F), **f32)
@@ -1110,56 +1145,27 @@ class RayMarchFunction(torch.autograd.Function):
     def backward(ctx, g_rgb, g_feat, g_weights, g_depth, g_alpha, g_raw):
         """The weight re-pack for the transposed products + ONE FFI call (mvsnerf_raymarch_bwd): compositing backward -> MLP data and
         weight gradients -> trilinear scatter into the volume gradient."""
-        lib = _lib.lib()
-        _cl_cache.pop("last", None)              # do not keep the step's volume storage past its backward (channels_last_volume)
         rays_ndc, z_vals, raw, saved, packed, *mlp_params = ctx.saved_tensors
         vshape, (D, H, W, C), N, S, F, white, bf16, dp_samples = ctx.meta
-        dev = raw.device
-        f32 = dict(device=dev, dtype=torch.float32)
-        grads_in = [None if g is None else g.contiguous() for g in (g_rgb, g_depth, g_weights, g_alpha)]       # kept alive until the launch
-        ptr = lambda t: 0 if t is None else dev_f32(t, "grad")
-        weights = [p.detach() for p in mlp_params[0::2]]
-        packed_bwd = mlp_pack_bwd_bf16(weights, F) if bf16 else mlp_pack_bwd(weights, F)
+        f32 = dict(device=raw.device, dtype=torch.float32)
+        b = _bwd_setup(mlp_params, F, bf16, N * S, (g_rgb, g_depth, g_weights, g_alpha), raw.device)
         d_raw = torch.empty((N, S, 4), **f32)
-        gslots = torch.empty(lib.mvsnerf_mlp_gradslot_floats(N * S) // (2 if bf16 else 1), **f32)
-        ws = torch.empty(lib.mvsnerf_mlp_bwd_workspace_floats(), **f32)
         d_feat = torch.empty((N * S, C), **f32)         # C = 8: the volume features only; C = F: the colour volume is a parameter too
-        # 22 gradient tensors of their own, zeroed by ONE multi-tensor launch.  (They used to be views of one zero-filled buffer: autograd's
-        # AccumulateGrad clones a gradient that does not own its storage - 22 device copies per step in the kernel trace.)
-        views = [torch.empty_like(p, memory_format=torch.contiguous_format) for p in mlp_params]
-        torch._foreach_zero_(views)
-        gws, gbs = views[0::2], views[1::2]
-        gwp = (ctypes.c_void_p * 11)(*[g.data_ptr() for g in gws])
-        gbp = (ctypes.c_void_p * 11)(*[g.data_ptr() for g in gbs])
-        maps = _mlp_bwd_maps(F, dev)
         gvol_cl = torch.zeros((D, H, W, C), **f32) if ctx.needs_input_grad[0] else None
-        from . import distributed as DD
-        # data-parallel fine-tuning of the volume: see volume_grad_from_all_ranks below (the scatter then runs after the call)
-        exchange = dp_samples and gvol_cl is not None and DD._collective_needed()
-        # VOLUME_BWD_DETERMINISTIC: the scatter runs behind the call too, through the fixed-point accumulators (mvsnerf_volume_sample_bwd_det)
-        gvol_arg = None if (exchange or VOLUME_BWD_DETERMINISTIC) else gvol_cl
+        # The call scatters into the volume gradient itself unless the scatter has to run behind it (_volume_grad): on the sample gradients of all
+        # ranks (data-parallel fine-tuning), or through the fixed-point accumulators of VOLUME_BWD_DETERMINISTIC (mvsnerf_volume_sample_bwd_det)
+        in_call = gvol_cl is not None and not (_exchange_samples(dp_samples) or VOLUME_BWD_DETERMINISTIC)
         a = _lib.RaymarchBwdArgs(
-            packed_mlp=packed.data_ptr(), packed_bwd=packed_bwd.data_ptr(), bf16=int(bf16), F=F,
+            packed_mlp=packed.data_ptr(), packed_bwd=b.packed_bwd.data_ptr(), bf16=int(bf16), F=F,
             raw=raw.data_ptr(), saved=saved.data_ptr(), z_vals=z_vals.data_ptr(), rays_ndc=rays_ndc.data_ptr(), N=N, S=S, white_bkgd=int(white),
-            g_rgb=ptr(grads_in[0]), g_depth=ptr(grads_in[1]), g_weights=ptr(grads_in[2]), g_alpha=ptr(grads_in[3]),
-            d_raw=d_raw.data_ptr(), gslots=gslots.data_ptr(), d_feat=d_feat.data_ptr(), n_feat_out=C,
-            gw=ctypes.cast(gwp, ctypes.POINTER(ctypes.c_void_p)), gb=ctypes.cast(gbp, ctypes.POINTER(ctypes.c_void_p)),
-            maps=maps.data_ptr(), workspace=ws.data_ptr(),
-            gvol=0 if gvol_arg is None else gvol_arg.data_ptr(), D=D, H=H, W=W, C=C)
-        check(lib.mvsnerf_raymarch_bwd(ctypes.byref(a), stream_ptr()), "raymarch_bwd")
-        if exchange:
-            volume_grad_from_all_ranks(d_feat, rays_ndc.reshape(-1, 3), gvol_cl)
-        elif VOLUME_BWD_DETERMINISTIC and gvol_cl is not None:
-            _scatter_hip(gvol_cl, rays_ndc.reshape(-1, 3), d_feat)
-        g_vol = None
-        if gvol_cl is not None:
-            g_vol = gvol_cl.permute(3, 0, 1, 2)
-            if len(vshape) == 5:
-                g_vol = g_vol.unsqueeze(0)
-        param_grads = []
-        for gw, gb in zip(gws, gbs):
-            param_grads += [gw, gb]
-        return (g_vol, None, None, None, None, None, None, None, None, None, None, *param_grads)
+            g_rgb=b.g_ptr[0], g_depth=b.g_ptr[1], g_weights=b.g_ptr[2], g_alpha=b.g_ptr[3],
+            d_raw=d_raw.data_ptr(), gslots=b.gslots.data_ptr(), d_feat=d_feat.data_ptr(), n_feat_out=C,
+            gw=ctypes.cast(b.gwp, ctypes.POINTER(ctypes.c_void_p)), gb=ctypes.cast(b.gbp, ctypes.POINTER(ctypes.c_void_p)),
+            maps=b.maps.data_ptr(), workspace=b.ws.data_ptr(),
+            gvol=gvol_cl.data_ptr() if in_call else 0, D=D, H=H, W=W, C=C)
+        check(_lib.lib().mvsnerf_raymarch_bwd(ctypes.byref(a), stream_ptr()), "raymarch_bwd")
+        g_vol = _volume_grad(gvol_cl, d_feat, rays_ndc.reshape(-1, 3), dp_samples, vshape, have_rows=not in_call)
+        return (g_vol, None, None, None, None, None, None, None, None, None, None, *b.grads)
 
 
 VOLUME_BWD_DETERMINISTIC = False   # True: the volume gradient's scatter through 64-bit fixed-point accumulators (integer atomics commute: two runs, and N ranks
@@ -1213,17 +1219,44 @@ def volume_grad_from_all_ranks(d_feat, ndc, gvol_cl, group=None, scatter=_scatte
     return gvol_cl
 
 
+def _exchange_samples(dp_samples):
+    """dp_samples with a collective to run: the volume scatter runs on the sample gradients of ALL ranks (volume_grad_from_all_ranks)."""
+    from . import distributed as DD
+    return bool(dp_samples) and DD._collective_needed()
+
+
+def _volume_grad(gvol_cl, d_feat, ndc_rows, dp_samples, vshape, have_rows, scatter=_scatter_hip):
+    """The end of both ray-march backwards: gvol_cl (D,H,W,C; None: the volume takes no gradient, and None is returned) in the caller's layout -
+    (C,D,H,W), or (1,C,D,H,W) for a five-entry vshape - after the rows d_feat (P,C) at ndc_rows (P,3) have been scattered into it when have_rows.
+    Under dp_samples with a collective to run that is volume_grad_from_all_ranks, which a rank without rows enters with one row that scatters zeros;
+    otherwise `scatter` (replaceable for the CPU tests), and without rows nothing is left to do: mvsnerf_raymarch_bwd scattered inside the call."""
+    if gvol_cl is None:
+        return None
+    if _exchange_samples(dp_samples):
+        if not have_rows:
+            d_feat, ndc_rows = gvol_cl.new_zeros((1, gvol_cl.shape[-1])), gvol_cl.new_zeros((1, 3))
+        volume_grad_from_all_ranks(d_feat, ndc_rows, gvol_cl, scatter=scatter)
+    elif have_rows:
+        scatter(gvol_cl, ndc_rows, d_feat)
+    g_vol = gvol_cl.permute(3, 0, 1, 2)
+    return g_vol.unsqueeze(0) if len(vshape) == 5 else g_vol
+
+
+def _train_entry(net, views, op):
+    """(the 22 MLP tensors as [weight, bias] * 11 in MLP_ORDER, net.packed(8 + 4V)) of a differentiable ray march, V = views.shape[0], after the refusals
+    that come before anything is packed or launched: netwidth 256, a precision mode training does not run; net.packed refuses net_type v2 under bf16."""
+    if getattr(net.nerf, "W", 128) != 128:
+        raise _wide_refusal(op)
+    if training_mlp_mode() not in ("fp32", "bf16"):
+        raise RuntimeError(f"training runs the MLP in 'fp32' or 'bf16' (ops.set_mlp_precision), not {MLP_PRECISION!r}")
+    params = [t for l in net.nerf._linears() for t in (l.weight, l.bias)]
+    return params, net.packed(8 + 4 * views.shape[0])
+
+
 def raymarch_train(volume, imgs, w2cs, intrinsics, net, rays_pts, rays_ndc, z_vals, rays_dir, white_bkgd=False, dp_samples=False):
     """Differentiable rendering(): `net` is a models.MVSNeRF; returns the dict of ops.raymarch.
     dp_samples: data-parallel volume gradient by exchanging sample gradients (volume_grad_from_all_ranks)."""
-    if getattr(net.nerf, "W", 128) != 128:      # before packed(): nothing is packed or launched for a width that cannot be trained
-        raise _wide_refusal("raymarch_train")
-    V = imgs.shape[0]
-    lins = net.nerf._linears()
-    params = []
-    for l in lins:
-        params += [l.weight, l.bias]
-    packed = net.packed(8 + 4 * V)
+    params, packed = _train_entry(net, imgs, "raymarch_train")
     rgb, feat, weights, depth, alpha, raw = RayMarchFunction.apply(
         volume, imgs, w2cs, intrinsics, rays_pts, rays_ndc, z_vals, rays_dir, white_bkgd, packed, dp_samples, *params)
     return {"rgb_map": rgb, "input_feat": feat, "weights": weights, "depth": depth, "alpha": alpha, "raw": raw}
@@ -1237,43 +1270,33 @@ class SparseRayMarchFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, volume, imgs, w2cs, intrinsics, rays_pts, rays_ndc, z_vals, rays_dir, density, thr, white_bkgd, packed, dp_samples, *mlp_params):
+        """_sparse_march on mvsnerf_mlp_fwd_train (mvsnerf_mlp_fwd_bf16_train under training_mlp_mode() == "bf16"), its activation store sized for the live points."""
         _need_narrow(packed, "raymarch_sparse_train")
         lib = _lib.lib()
         vol_cl = channels_last_volume(volume)
         D, H, W, C = vol_cl.shape
         N, S = z_vals.shape
-        P = N * S
         F = 8 + 4 * w2cs.shape[0]
         if C not in (8, F):
             raise RuntimeError(f"ray march: the volume has {C} channels; expected 8 or 8 + 4V = {F}")
-        color_vol = C != 8
         bf16 = training_mlp_mode() == "bf16"
-        dev = rays_ndc.device
-        f32 = dict(device=dev, dtype=torch.float32)
-        count, idx, ndc_c, pts_c, dir_c = live_samples(density, rays_ndc, thr, None if color_vol else rays_pts, rays_dir)
-        n_live = int(count.item())                      # the step's one host read
-        ndc_l = ndc_c[:n_live]
-        raw_c = torch.empty((n_live, 4), **f32)
-        saved = raw_c                                   # no live sample: nothing is stored, the backward reads nothing
-        if n_live:
-            ndc_g, dir_l = ndc_l.view(n_live, 1, 3), dir_c[:n_live]
-            if color_vol:
-                feat, dirs = gather_colorvol(vol_cl, ndc_g, dir_l, w2cs[0].contiguous())
-            else:
-                feat, dirs = gather(vol_cl, imgs, w2cs, intrinsics, pts_c[:n_live].view(n_live, 1, 3), ndc_g, dir_l)
+        f32 = dict(device=rays_ndc.device, dtype=torch.float32)
+        kept = []
+
+        def mlp(ndc_l, feat, dirs, n_live):
+            raw_c = torch.empty((n_live, 4), **f32)
             saved = torch.empty(lib.mvsnerf_mlp_saved_floats(n_live) // (2 if bf16 else 1), **f32)      # per LIVE point; bf16 mode: two-byte slots
+            kept.append(saved)
+            io = (F, ndc_l.data_ptr(), 3, feat.data_ptr(), F, dirs.data_ptr(), 3, n_live, 1, raw_c.data_ptr(), saved.data_ptr(), stream_ptr())
             if bf16:
                 packed_b = mlp_pack_bf16([p.detach() for p in mlp_params[0::2]], F)
-                check(lib.mvsnerf_mlp_fwd_bf16_train(packed_b.data_ptr(), packed.data_ptr(), F, ndc_l.data_ptr(), 3, feat.data_ptr(), F, dirs.data_ptr(), 3,
-                                                     n_live, 1, raw_c.data_ptr(), saved.data_ptr(), stream_ptr()), "mlp_fwd_bf16_train")
+                check(lib.mvsnerf_mlp_fwd_bf16_train(packed_b.data_ptr(), packed.data_ptr(), *io), "mlp_fwd_bf16_train")
             else:
-                check(lib.mvsnerf_mlp_fwd_train(packed.data_ptr(), F, ndc_l.data_ptr(), 3, feat.data_ptr(), F, dirs.data_ptr(), 3,
-                                                n_live, 1, raw_c.data_ptr(), saved.data_ptr(), stream_ptr()), "mlp_fwd_train")
-        raw = expand_rows(raw_c, idx, count, P).view(N, S, 4)
-        rgb, disp, acc, depth = (torch.empty(sh, **f32) for sh in ((N, 3), (N,), (N,), (N,)))
-        weights, alpha = torch.empty((N, S), **f32), torch.empty((N, S), **f32)
-        check(lib.mvsnerf_composite_fwd(raw.data_ptr(), dev_f32(z_vals, "z_vals"), N, S, int(bool(white_bkgd)), rgb.data_ptr(), disp.data_ptr(), acc.data_ptr(),
-                                        weights.data_ptr(), depth.data_ptr(), alpha.data_ptr(), stream_ptr()), "composite_fwd")
+                check(lib.mvsnerf_mlp_fwd_train(packed.data_ptr(), *io), "mlp_fwd_train")
+            return raw_c
+        (idx, count, ndc_l, raw_c, raw, n_live), (rgb, _, _, weights, depth, alpha) = _sparse_march(
+            vol_cl, imgs, w2cs, intrinsics, rays_pts, rays_ndc, z_vals, rays_dir, density, thr, white_bkgd, mlp)
+        saved = kept[0] if kept else raw_c              # no live sample: nothing is stored, the backward reads nothing
         ctx.save_for_backward(z_vals, raw, raw_c, ndc_l, idx, count, packed, saved, *mlp_params)
         ctx.meta = (tuple(volume.shape), (D, H, W, C), N, S, F, bool(white_bkgd), bf16, bool(dp_samples), n_live)
         ctx.mark_non_differentiable(raw)
@@ -1281,48 +1304,26 @@ class SparseRayMarchFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_rgb, g_weights, g_depth, g_alpha, g_raw, _g_n_live):
+        """mvsnerf_composite_bwd on the dense raw -> compact_rows to (n_live,4) -> the MLP backward on the live rows -> the volume scatter on the
+        compact NDC rows (_volume_grad: float atomics, VOLUME_BWD_DETERMINISTIC, or volume_grad_from_all_ranks under dp_samples).  Without a live
+        sample none of these is launched and every gradient is zero."""
         lib = _lib.lib()
-        _cl_cache.pop("last", None)              # do not keep the step's volume storage past its backward (channels_last_volume)
         z_vals, raw, raw_c, ndc_l, idx, count, packed, saved, *mlp_params = ctx.saved_tensors
         vshape, (D, H, W, C), N, S, F, white, bf16, dp_samples, n_live = ctx.meta
-        dev = raw.device
-        f32 = dict(device=dev, dtype=torch.float32)
-        views = [torch.empty_like(p, memory_format=torch.contiguous_format) for p in mlp_params]
-        torch._foreach_zero_(views)
-        gws, gbs = views[0::2], views[1::2]
+        f32 = dict(device=raw.device, dtype=torch.float32)
+        b = _bwd_setup(mlp_params, F, bf16, n_live, (g_rgb, g_depth, g_weights, g_alpha), raw.device)
         gvol_cl = torch.zeros((D, H, W, C), **f32) if ctx.needs_input_grad[0] else None
         d_feat = torch.empty((n_live, C), **f32)
         if n_live:
-            grads_in = [None if g is None else g.contiguous() for g in (g_rgb, g_depth, g_weights, g_alpha)]       # kept alive until the launch
-            ptr = lambda t: 0 if t is None else dev_f32(t, "grad")
             d_raw = torch.empty((N * S, 4), **f32)
-            check(lib.mvsnerf_composite_bwd(raw.data_ptr(), z_vals.data_ptr(), N, S, int(white), ptr(grads_in[0]), ptr(grads_in[1]), 0, ptr(grads_in[2]),
-                                            ptr(grads_in[3]), d_raw.data_ptr(), stream_ptr()), "composite_bwd")
+            check(lib.mvsnerf_composite_bwd(raw.data_ptr(), z_vals.data_ptr(), N, S, int(white), b.g_ptr[0], b.g_ptr[1], 0, b.g_ptr[2], b.g_ptr[3],
+                                            d_raw.data_ptr(), stream_ptr()), "composite_bwd")
             d_raw_c = compact_rows(d_raw, idx, count, n_live)
-            weights = [p.detach() for p in mlp_params[0::2]]
-            packed_bwd = mlp_pack_bwd_bf16(weights, F) if bf16 else mlp_pack_bwd(weights, F)
-            gslots = torch.empty(lib.mvsnerf_mlp_gradslot_floats(n_live) // (2 if bf16 else 1), **f32)
-            ws = torch.empty(lib.mvsnerf_mlp_bwd_workspace_floats(), **f32)
-            gwp = (ctypes.c_void_p * 11)(*[g.data_ptr() for g in gws])
-            gbp = (ctypes.c_void_p * 11)(*[g.data_ptr() for g in gbs])
-            maps = _mlp_bwd_maps(F, dev)
             fn = lib.mvsnerf_mlp_bwd_bf16 if bf16 else lib.mvsnerf_mlp_bwd
-            check(fn(packed.data_ptr(), packed_bwd.data_ptr(), F, raw_c.data_ptr(), d_raw_c.data_ptr(), saved.data_ptr(), n_live, 1, gslots.data_ptr(),
-                     d_feat.data_ptr(), C, gwp, gbp, maps.data_ptr(), ws.data_ptr(), stream_ptr()), "mlp_bwd_bf16" if bf16 else "mlp_bwd")
-        if gvol_cl is not None:
-            from . import distributed as DD
-            if dp_samples and DD._collective_needed():
-                if not n_live:                  # a rank without a live sample enters the collective too: one row that scatters zeros
-                    d_feat, ndc_l = torch.zeros((1, C), **f32), torch.zeros((1, 3), **f32)
-                volume_grad_from_all_ranks(d_feat, ndc_l, gvol_cl)
-            elif n_live:
-                _scatter_hip(gvol_cl, ndc_l, d_feat)
-        g_vol = None
-        if gvol_cl is not None:
-            g_vol = gvol_cl.permute(3, 0, 1, 2)
-            if len(vshape) == 5:
-                g_vol = g_vol.unsqueeze(0)
-        return (g_vol, None, None, None, None, None, None, None, None, None, None, None, None, *views)
+            check(fn(packed.data_ptr(), b.packed_bwd.data_ptr(), F, raw_c.data_ptr(), d_raw_c.data_ptr(), saved.data_ptr(), n_live, 1, b.gslots.data_ptr(),
+                     d_feat.data_ptr(), C, b.gwp, b.gbp, b.maps.data_ptr(), b.ws.data_ptr(), stream_ptr()), "mlp_bwd_bf16" if bf16 else "mlp_bwd")
+        g_vol = _volume_grad(gvol_cl, d_feat, ndc_l, dp_samples, vshape, have_rows=bool(n_live))
+        return (g_vol, None, None, None, None, None, None, None, None, None, None, None, None, *b.grads)
 
 
 def raymarch_sparse_train(volume, imgs, w2cs, intrinsics, net, rays_pts, rays_ndc, z_vals, rays_dir, density, thr, white_bkgd=False, dp_samples=False):
@@ -1331,27 +1332,15 @@ def raymarch_sparse_train(volume, imgs, w2cs, intrinsics, net, rays_pts, rays_nd
     128); volume (1,C,D,H,W) | (C,D,H,W) with C = 8 (imgs (V,3,H,W), w2cs (V,4,4), intrinsics (V,3,3) for the colour lookup) or C = 8 + 4V (a colour
     volume: imgs / intrinsics / rays_pts are not read); density (D',H',W') fp32.  The 22 MLP tensors and the volume receive gradients; rays, images,
     cameras and `density` do not.
-    Forward: live_samples -> ONE host read of the count (the step's only synchronisation) -> gather / gather_colorvol on the compact rows as
-    (n_live,1,3) -> mvsnerf_mlp_fwd_train (mvsnerf_mlp_fwd_bf16_train under training_mlp_mode() == "bf16") with N = n_live, S = 1, its activation
-    store sized for the live points -> expand_rows into raw (N,S,4) -> mvsnerf_composite_fwd.  Backward: mvsnerf_composite_bwd on the dense raw ->
-    compact_rows to (n_live,4) -> the MLP backward on the live rows -> the volume scatter on the compact NDC rows (float atomics,
-    VOLUME_BWD_DETERMINISTIC, or volume_grad_from_all_ranks under dp_samples).  A dead sample's raw is the constant (0,0,0,0); with no live sample at
-    all nothing but live_samples, expand_rows and the compositing is launched, and every gradient is zero.
+    The forward is _sparse_march's sequence - ONE host read of the live count, the step's only synchronisation - and the backward
+    SparseRayMarchFunction.backward's.  A dead sample's raw is the constant (0,0,0,0); with no live sample at all nothing but live_samples,
+    expand_rows and the compositing is launched, and every gradient is zero.
     Returns a dict: rgb_map (N,3), weights (N,S), depth (N,), alpha (N,S), raw (N,S,4; not differentiable), n_live (int).  There is no input_feat:
     the dense (N,S,F) feature tensor is never formed."""
     thr = _thr_f32(thr, "raymarch_sparse_train")
     if not torch.is_tensor(density) or density.dim() != 3:
         raise RuntimeError(f"raymarch_sparse_train: density must be (D,H,W), got {tuple(getattr(density, 'shape', ()))}")
-    if getattr(net.nerf, "W", 128) != 128:      # before packed(): nothing is packed or launched for a width that cannot be trained
-        raise _wide_refusal("raymarch_sparse_train")
-    if training_mlp_mode() not in ("fp32", "bf16"):
-        raise RuntimeError(f"training runs the MLP in 'fp32' or 'bf16' (ops.set_mlp_precision), not {MLP_PRECISION!r}")
-    net.nerf.need_fp32_mode(MLP_PRECISION)      # net_type v2 under bf16
-    V = w2cs.shape[0]
-    params = []
-    for l in net.nerf._linears():
-        params += [l.weight, l.bias]
-    packed = net.packed(8 + 4 * V)
+    params, packed = _train_entry(net, w2cs, "raymarch_sparse_train")
     rgb, weights, depth, alpha, raw, n_live = SparseRayMarchFunction.apply(
         volume, imgs, w2cs, intrinsics, rays_pts, rays_ndc, z_vals, rays_dir, density.detach(), thr, white_bkgd, packed, dp_samples, *params)
     return {"rgb_map": rgb, "weights": weights, "depth": depth, "alpha": alpha, "raw": raw, "n_live": n_live}

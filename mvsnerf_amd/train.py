@@ -102,6 +102,68 @@ class _ModuleShim(nn.Module):
         return next(self.parameters()).device
 
 
+# ------------------------------------------------------------------ empty-space skipping: what the three systems share
+def _threshold(value, who):
+    """A density threshold (skip_empty=, args.skip_empty_train) as a float; NaN is refused - by ops._thr_f32, the package's one NaN test."""
+    return ops._thr_f32(value, who)
+
+
+def _need_fused(net, kw, who):
+    """The sparse paths run the fused configuration only: an MVSNeRF whose network query the ray-march kernels embed (what create_nerf_mvs builds)."""
+    if not (isinstance(net, MVSNeRF) and getattr(kw.get("network_query_fn"), "_mvsnerf_fused", False)):
+        raise NotImplementedError(f"{who}: the fused configuration only (what create_nerf_mvs builds)")
+
+
+def _sparse_config(system, vol, V, who):
+    """(network, colour volume?) of a system's sparse paths (ops.node_density, ops.raymarch_sparse) on `vol` with V source views, after the refusals:
+    the fused configuration, and a volume whose channels are what args.feat_dim and args.use_color_volume say."""
+    args, kw = system.args, system.render_kwargs_train
+    net = kw.get("network_fn")
+    _need_fused(net, kw, who)
+    color_vol = bool(getattr(args, "use_color_volume", False))
+    if args.feat_dim != 8 + 4 * V or vol.shape[-4] != (args.feat_dim if color_vol else 8):
+        raise RuntimeError(f"{who}: volume with {vol.shape[-4]} channels, feat_dim {args.feat_dim}, {V} source views")
+    return net, color_vol
+
+
+def _sparse_sources(system, vol, pose, V, imgs, who):
+    """The scene arguments of ops.raymarch_sparse, as its keywords, for a system that renders `vol` from V source views (after _sparse_config's
+    refusals): imgs and intrinsics (None for a colour volume, which holds the colours itself), w2cs, packed, white_bkgd and the kernel choice of
+    MVSNeRF.packed_alt."""
+    args, kw = system.args, system.render_kwargs_train
+    net, color_vol = _sparse_config(system, vol, V, who)
+    return dict(imgs=None if color_vol else imgs.contiguous(), w2cs=pose["w2cs"][:V].contiguous(),
+                intrinsics=None if color_vol else pose["intrinsics"][:V].contiguous(), packed=net.packed(args.feat_dim),
+                white_bkgd=bool(kw.get("white_bkgd", getattr(args, "white_bkgd", False))), **net.packed_alt(args.feat_dim))
+
+
+def _density_sources(net, F, vol, pose, V, imgs=None, **camera):
+    """Every argument of ops.node_density but dilate, as keywords, for the nodes of a system's volume `vol`.  imgs: the V source images of an
+    8-channel volume, with `camera` - near_far, ref_hw, pad[, lindisp] of the reference view the volume is aligned with; its intrinsics and pose are
+    pose's first - for the nodes' world positions; None for a colour volume (one lookup per node, no camera)."""
+    src = {} if imgs is None else dict(imgs=imgs.contiguous(), intrinsics=pose["intrinsics"][:V].contiguous(),
+                                       camera=dict(K_ref=pose["intrinsics"][0], c2w_ref=pose["c2ws"][0], **camera))
+    return dict(vol_cl=ops.channels_last_volume(vol), packed=net.packed(F), w2cs=pose["w2cs"][:V].contiguous(), **src, **net.packed_alt(F))
+
+
+def _render_sparse_batches(system, n_rows, B, make_batch, march_kw):
+    """A frame of n_rows rays with empty space skipped, per sub-batch of B rays: make_batch(idx) -> (pts, ndc, z, dirs) of rays [idx * B, (idx + 1) * B)
+    -> ops.raymarch_sparse(**march_kw: vol_cl, imgs, w2cs, intrinsics, packed, density, thr, white_bkgd and the kernel choice) - one host read of
+    the live count per sub-batch.  The sub-batches are sharded over the ranks (distributed.render_frame); system.last_live_fraction is this rank's
+    live samples over its samples.  Returns (rgb (n_rows,3), depth (n_rows,))."""
+    live = [0, 0]                   # live samples, samples
+
+    def render_batch(idx):
+        pts, ndc, z, dirs = make_batch(idx)
+        o = ops.raymarch_sparse(rays_pts=pts, rays_ndc=ndc, z_vals=z, rays_dir=dirs, **march_kw)
+        live[0] += o["n_live"]
+        live[1] += z.numel()
+        return o["rgb_map"], o["depth"]
+    out = D.render_frame(render_batch, 1, n_rows, B)
+    system.last_live_fraction = live[0] / live[1] if live[1] else 0.0
+    return out
+
+
 class MVSSystem(_ModuleShim):
     """reference train_mvs_nerf_pl.py:34-288 (generalizable training)."""
 
@@ -247,23 +309,9 @@ class MVSSystem(_ModuleShim):
         H, W = int(imgs.shape[-2]), int(imgs.shape[-1])
         V = imgs.shape[1] - 1
         vol = self.encode_scene(batch) if volume is None else volume
-        net, color_vol = self._sparse_net(V, vol)
-        src = {} if color_vol else dict(imgs=self.unpreprocess(imgs)[0, :V].contiguous(), intrinsics=pose_ref["intrinsics"][:V].contiguous(),
-                                        camera=dict(K_ref=pose_ref["intrinsics"][0], c2w_ref=pose_ref["c2ws"][0], near_far=near_fars[0], ref_hw=(H, W),
-                                                    pad=args.pad))
-        return ops.node_density(ops.channels_last_volume(vol), net.packed(args.feat_dim), pose_ref["w2cs"][:V].contiguous(), dilate=dilate, **src,
-                                **net.packed_alt(args.feat_dim))
-
-    def _sparse_net(self, V, vol):
-        """(network, colour volume?) of the per-sub-batch sparse path (ops.node_density, ops.raymarch_sparse): the fused configuration only."""
-        args, kw = self.args, self.render_kwargs_train
-        net = kw["network_fn"]
-        if not (isinstance(net, MVSNeRF) and getattr(kw.get("network_query_fn"), "_mvsnerf_fused", False)):
-            raise NotImplementedError("skip_empty / scene_density: the fused configuration only (what create_nerf_mvs builds)")
-        color_vol = bool(getattr(args, "use_color_volume", False))
-        if args.feat_dim != 8 + 4 * V or vol.shape[-4] != (args.feat_dim if color_vol else 8):
-            raise RuntimeError(f"skip_empty / scene_density: volume with {vol.shape[-4]} channels, feat_dim {args.feat_dim}, {V} source views")
-        return net, color_vol
+        net, color_vol = _sparse_config(self, vol, V, "skip_empty / scene_density")
+        return ops.node_density(dilate=dilate, **_density_sources(net, args.feat_dim, vol, pose_ref, V, None if color_vol else self.unpreprocess(imgs)[0, :V],
+                                                                  near_far=near_fars[0], ref_hw=(H, W), pad=args.pad))
 
     @torch.no_grad()
     def render_view(self, batch, chunk=None, whole_frame_off=False, target=None, batch_rays=16384, volume=None, skip_empty=None, density=None, dilate=0):
@@ -280,7 +328,7 @@ class MVSSystem(_ModuleShim):
         volume: the result of encode_scene(batch) - the encode is skipped (a camera path over one scene; the pixels are the same).
         skip_empty: None (default) is the dense render above, untouched.  A float is the density threshold of DESIGN.md 4e: samples whose trilinear
         cell in `density` holds no value above it are not sent through the MLP - their raw is (0,0,0,0), the others have the bits of the dense
-        sequence (ops.raymarch_sparse).  The frame then runs per sub-batch of batch_rays pixels (ops.raygen -> ops.raymarch_sparse), the sub-batches
+        sequence (ops.raymarch_sparse).  The frame then runs per sub-batch of batch_rays pixels (_render_sparse_batches on ops.raygen), the sub-batches
         sharded over the ranks, one host read of the live count per sub-batch; `self.last_live_fraction` is this rank's live samples over its samples.
         netwidth 256, net_type v2 and colour volumes take the same path.  density: (D,h,w) of the volume in use - default
         scene_density(batch, volume, dilate), built on every call: a camera path should build it once (render_path_skip_empty does) and pass it.  dilate is
@@ -288,9 +336,7 @@ class MVSSystem(_ModuleShim):
         if skip_empty is not None:          # refusals first: nothing below needs the library before them
             if whole_frame_off:
                 raise ValueError("render_view: skip_empty runs its own per-sub-batch loop; it cannot be combined with whole_frame_off=True")
-            skip_empty = float(skip_empty)
-            if skip_empty != skip_empty:
-                raise ValueError("render_view: skip_empty is NaN (a density threshold, or None for the dense render)")
+            skip_empty = _threshold(skip_empty, "render_view(skip_empty=)")
             if density is not None and (density.dim() != 3 or (volume is not None and tuple(density.shape) != tuple(volume.shape[-3:]))):
                 raise RuntimeError(f"render_view: density must be the (D,h,w) of the volume in use, got {tuple(density.shape)}"
                                    + ("" if volume is None else f" for a volume {tuple(volume.shape)}"))
@@ -321,7 +367,7 @@ class MVSSystem(_ModuleShim):
         kw = self.render_kwargs_train
         net = kw["network_fn"]
         if skip_empty is not None:
-            net, color_vol = self._sparse_net(V, volume_feature)
+            src = _sparse_sources(self, volume_feature, pose_ref, V, imgs[0, :-1], "skip_empty / scene_density")
             if density is None:
                 density = self.scene_density(batch, volume=volume_feature, dilate=dilate)
             if tuple(density.shape) != tuple(volume_feature.shape[-3:]):
@@ -330,25 +376,15 @@ class MVSSystem(_ModuleShim):
             k_render = intrinsic if intrinsic.dim() == 2 else intrinsic.mean(0)
             k_ndc = k_render if k_ref is None else k_ref
             nf_t, nf_r = nf_tgt.reshape(-1)[:2].contiguous(), near_fars[0].reshape(-1)[:2].contiguous()
-            vol_cl = ops.channels_last_volume(volume_feature)
-            src = None if color_vol else imgs[0, :-1].contiguous()
-            w2cs = pose_ref["w2cs"][:V].contiguous()
-            Ks = None if color_vol else pose_ref["intrinsics"][:V].contiguous()
-            packed, alt = net.packed(args.feat_dim), net.packed_alt(args.feat_dim)
-            white = bool(kw.get("white_bkgd", False))
             B = max(int(batch_rays), 1)
-            live = [0, 0]                   # live samples, samples
 
-            def render_batch(idx):
+            def make_batch(idx):
                 first = idx * B
                 pts, dirs, ndc, z, _ = ops.raygen(H, W, k_render, tgt_to_world, k_ndc, world_to_ref, nf_t, nf_r, args.N_samples, pad=args.pad,
                                                   first_pixel=first, n_rays=min(B, H * W - first), ref_hw=ref_hw)
-                o = ops.raymarch_sparse(vol_cl, src, w2cs, Ks, packed, pts, ndc, z, dirs, density, skip_empty, white_bkgd=white, **alt)
-                live[0] += o["n_live"]
-                live[1] += z.numel()
-                return o["rgb_map"], o["depth"]
-            rgb, depth = D.render_frame(render_batch, H, W, B)
-            self.last_live_fraction = live[0] / live[1] if live[1] else 0.0
+                return pts, ndc, z, dirs
+            rgb, depth = _render_sparse_batches(self, H * W, B, make_batch,
+                                                dict(src, vol_cl=ops.channels_last_volume(volume_feature), density=density, thr=skip_empty))
             return rgb.reshape(H, W, 3), depth.reshape(H, W)
         fused = (isinstance(net, MVSNeRF) and getattr(kw.get("network_query_fn"), "_mvsnerf_fused", False)
                  and not getattr(args, "use_color_volume", False) and args.feat_dim == 8 + 4 * V and not whole_frame_off
@@ -398,9 +434,7 @@ class MVSSystem(_ModuleShim):
         """render_path with render_view's skip_empty (a density threshold): the scene is encoded once, its density volume is built ONCE per
         path next to the encode (scene_density(batch, volume, dilate)), and both are handed to every render_view call.  render_path_kw: render_path's
         keywords (hw, intrinsic, near_far, depth_panel, crop, minmax, cmap, volume).  `self.last_live_fraction` is the last frame's."""
-        skip_empty = float(skip_empty)
-        if skip_empty != skip_empty:
-            raise ValueError("render_path_skip_empty: skip_empty is NaN (a density threshold)")
+        skip_empty = _threshold(skip_empty, "render_path_skip_empty(skip_empty=)")       # before the encode; render_view parses it again per frame
         names = ("hw", "intrinsic", "near_far", "depth_panel", "crop", "minmax", "cmap", "volume")
         unknown = sorted(set(render_path_kw) - set(names))
         if unknown:
@@ -626,9 +660,7 @@ def _skip_empty_train(args):
     thr = getattr(args, "skip_empty_train", None)
     if thr is None:
         return None
-    thr = float(thr)
-    if thr != thr:
-        raise ValueError("args.skip_empty_train is NaN (a density threshold, or None for the dense step)")
+    thr = _threshold(thr, "args.skip_empty_train")
     refresh = int(getattr(args, "skip_empty_refresh", 200))
     if refresh < 1:
         raise ValueError(f"args.skip_empty_refresh must be >= 1 step, got {refresh}")
@@ -639,9 +671,7 @@ def _refresh_train_density(system, sparse, build_density):
     """The training density of a system with args.skip_empty_train set: `system.train_density` (D,H,W), build_density(dilate) on first use and at
     every later multiple of args.skip_empty_refresh steps (an assigned tensor is kept until then).  system.density_volume is not touched."""
     _, dilate, refresh = sparse
-    net, kw = system.network_fn, system.render_kwargs_train
-    if not (isinstance(net, MVSNeRF) and getattr(kw.get("network_query_fn"), "_mvsnerf_fused", False)):
-        raise NotImplementedError("args.skip_empty_train needs the fused configuration (what create_nerf_mvs builds)")
+    _need_fused(system.network_fn, system.render_kwargs_train, "args.skip_empty_train")
     if getattr(system, "train_density", None) is None or (system.global_step > 0 and system.global_step % refresh == 0):
         system.train_density = build_density(dilate)
 
@@ -743,16 +773,11 @@ class MVSSystemFinetune(_ModuleShim):
         self.density_volume and what a step with args.skip_empty_train keeps in self.train_density."""
         V = self.imgs.shape[1]
         vol = self.volume.feat_volume.detach()
-        color_vol = vol.shape[1] != 8
         H, W = self.imgs.shape[-2:]
-        src = {} if color_vol else dict(imgs=self.imgs[0].contiguous(), intrinsics=self.pose_source["intrinsics"][:V].contiguous(),
-                                        camera=dict(K_ref=self.pose_source["intrinsics"][0], c2w_ref=self.pose_source["c2ws"][0],
-                                                    near_far=self.near_far_source, ref_hw=(int(H), int(W)), pad=self.args.pad,
-                                                    lindisp=bool(getattr(self.args, "use_disp", False))))
         with torch.no_grad():
-            return ops.node_density(ops.channels_last_volume(vol), self.network_fn.packed(self.args.feat_dim),
-                                    self.pose_source["w2cs"][:V].contiguous(), dilate=dilate, **src,
-                                    **self.network_fn.packed_alt(self.args.feat_dim))
+            return ops.node_density(dilate=dilate, **_density_sources(
+                self.network_fn, self.args.feat_dim, vol, self.pose_source, V, self.imgs[0] if vol.shape[1] == 8 else None, near_far=self.near_far_source,
+                ref_hw=(int(H), int(W)), pad=self.args.pad, lindisp=bool(getattr(self.args, "use_disp", False))))
 
     def update_density_volume(self, render_space=False, dilate=0):
         """:91-99: sigma of every voxel centre from the current volume + MLP (forward_alpha queries), -> (D,H,W).
@@ -839,14 +864,12 @@ class MVSSystemFinetune(_ModuleShim):
         skip_empty: None (default) is the dense render above, untouched.  A float is a density threshold: samples whose trilinear cell in
         `self.density_volume` (update_density_volume()) holds no value above it are not sent through the MLP - their raw is (0,0,0,0), the
         others have the bits of the dense sequence (ops.raymarch_sparse).  The frame then runs per sub-batch of batch_rays rays (ray_marcher ->
-        ops.ray_points -> [ray_marcher_fine] -> ops.raymarch_sparse), the sub-batches sharded over the ranks, one host read of the live count per
+        ops.ray_points -> [ray_marcher_fine] -> ops.raymarch_sparse: _render_sparse_batches), the sub-batches sharded over the ranks, one host read of the live count per
         sub-batch; `self.last_live_fraction` is this rank's live samples over its samples."""
         if skip_empty is not None:          # refusals first: nothing below needs the library before them
             if whole_frame_off:
                 raise ValueError("render_rays: skip_empty runs its own per-sub-batch loop; it cannot be combined with whole_frame_off=True")
-            skip_empty = float(skip_empty)
-            if skip_empty != skip_empty:
-                raise ValueError("render_rays: skip_empty is NaN (a density threshold, or None for the dense render)")
+            skip_empty = _threshold(skip_empty, "render_rays(skip_empty=)")
             if getattr(self, "density_volume", None) is None:
                 raise RuntimeError("render_rays: skip_empty needs the scene's density volume; call update_density_volume() first")
         args = self.args
@@ -867,51 +890,37 @@ class MVSSystemFinetune(_ModuleShim):
             if tuple(u.shape) != (N, NI):
                 raise RuntimeError(f"render_rays: u must be ({N}, {NI}), got {tuple(u.shape)}")
         kw = self.render_kwargs_train
-        net = kw["network_fn"]
         V = self.imgs.shape[1]
         vol = self.volume.feat_volume
-        color_vol = bool(getattr(args, "use_color_volume", False))
+        who = "render_rays (whole_frame_off=True runs the per-chunk loop)"
+
+        def march(idx, n):          # rays [idx * n, (idx + 1) * n) -> (pts, ndc, z, rays_o, rays_d): the per-chunk Python loop's and the sparse loop's samples
+            r = rays[idx * n:(idx + 1) * n]
+            _, rays_o, rays_d, z = ray_marcher(r, N_samples=args.N_samples, lindisp=lindisp)
+            pts, ndc = ops.ray_points(rays_o, rays_d, z, w2c_ref, K_ref, self.near_far_source, ref_hw=(H, W), pad=args.pad, lindisp=lindisp)
+            if fine:
+                pts, rays_o, rays_d, z = ray_marcher_fine(r, self.density_volume, z, ndc, N_importance=NI, u=u[idx * n:(idx + 1) * n].contiguous())
+                pts, ndc = ops.ray_points(rays_o, rays_d, z, w2c_ref, K_ref, self.near_far_source, ref_hw=(H, W), pad=args.pad, lindisp=lindisp)
+            return pts, ndc, z, rays_o, rays_d
 
         if whole_frame_off:
             def render_chunk(idx):
-                r = rays[idx * chunk:(idx + 1) * chunk]
-                _, rays_o, rays_d, z = ray_marcher(r, N_samples=args.N_samples, lindisp=lindisp)
-                pts, ndc = ops.ray_points(rays_o, rays_d, z, w2c_ref, K_ref, self.near_far_source, ref_hw=(H, W), pad=args.pad, lindisp=lindisp)
-                if fine:
-                    pts, rays_o, rays_d, z = ray_marcher_fine(r, self.density_volume, z, ndc, N_importance=NI, u=u[idx * chunk:(idx + 1) * chunk].contiguous())
-                    pts, ndc = ops.ray_points(rays_o, rays_d, z, w2c_ref, K_ref, self.near_far_source, ref_hw=(H, W), pad=args.pad, lindisp=lindisp)
+                pts, ndc, z, rays_o, rays_d = march(idx, chunk)
                 rgb, _, _, depth, _, _ = rendering(args, self.pose_source, pts, ndc, z, rays_o, rays_d.contiguous(), self.volume, self.imgs, **kw)
                 return rgb, depth
             return D.render_frame(render_chunk, 1, N, chunk)
 
-        if not (isinstance(net, MVSNeRF) and getattr(kw.get("network_query_fn"), "_mvsnerf_fused", False)):
-            raise NotImplementedError("render_rays: the fused configuration only (what create_nerf_mvs builds); whole_frame_off=True runs the per-chunk loop")
-        if args.feat_dim != 8 + 4 * V or vol.shape[1] != (args.feat_dim if color_vol else 8):
-            raise RuntimeError(f"render_rays: volume with {vol.shape[1]} channels, feat_dim {args.feat_dim}, {V} source views")
-        vol_cl = ops.channels_last_volume(vol)
         if skip_empty is not None:
+            src = _sparse_sources(self, vol, self.pose_source, V, self.imgs[0], who)
             B = max(int(batch_rays), 1)
-            imgs0 = None if color_vol else self.imgs[0].contiguous()
-            w2cs = self.pose_source["w2cs"][:V].contiguous()
-            Ks = None if color_vol else self.pose_source["intrinsics"][:V].contiguous()
-            packed, alt = net.packed(args.feat_dim), net.packed_alt(args.feat_dim)
-            live = [0, 0]                   # live samples, samples
 
-            def render_batch(idx):
-                r = rays[idx * B:(idx + 1) * B]
-                _, rays_o, rays_d, z = ray_marcher(r, N_samples=args.N_samples, lindisp=lindisp)
-                pts, ndc = ops.ray_points(rays_o, rays_d, z, w2c_ref, K_ref, self.near_far_source, ref_hw=(H, W), pad=args.pad, lindisp=lindisp)
-                if fine:
-                    pts, rays_o, rays_d, z = ray_marcher_fine(r, self.density_volume, z, ndc, N_importance=NI, u=u[idx * B:(idx + 1) * B].contiguous())
-                    pts, ndc = ops.ray_points(rays_o, rays_d, z, w2c_ref, K_ref, self.near_far_source, ref_hw=(H, W), pad=args.pad, lindisp=lindisp)
-                o = ops.raymarch_sparse(vol_cl, imgs0, w2cs, Ks, packed, pts, ndc, z.contiguous(), rays_d.contiguous(), self.density_volume, skip_empty,
-                                        white_bkgd=white, **alt)
-                live[0] += o["n_live"]
-                live[1] += z.numel()
-                return o["rgb_map"], o["depth"]
-            out = D.render_frame(render_batch, 1, N, B)
-            self.last_live_fraction = live[0] / live[1] if live[1] else 0.0
-            return out
+            def make_batch(idx):
+                pts, ndc, z, _, rays_d = march(idx, B)
+                return pts, ndc, z.contiguous(), rays_d.contiguous()
+            return _render_sparse_batches(self, N, B, make_batch,
+                                          dict(src, vol_cl=ops.channels_last_volume(vol), density=self.density_volume, thr=skip_empty))
+        net, color_vol = _sparse_config(self, vol, V, who)
+        vol_cl = ops.channels_last_volume(vol)
         t = torch.linspace(0, 1, args.N_samples, device=dev)
         src = {} if color_vol else dict(imgs=self.imgs[0].contiguous(), w2cs=self.pose_source["w2cs"][:V].contiguous(),
                                         intrinsics=self.pose_source["intrinsics"][:V].contiguous())
@@ -1198,11 +1207,8 @@ class MVSSystemFusion(_ModuleShim):
         """ops.node_density over the nodes of the box volume -> (D,H,W): what update_density_volume reshapes into self.density_volume and what a step
         with args.skip_empty_train keeps in self.train_density."""
         self._need_volume()
-        vol = self.volume.feat_volume.detach()
-        net = self.network_fn
         F = self.args.feat_dim
-        return ops.node_density(ops.channels_last_volume(vol), net.packed(F), self.pose_source_ref["w2cs"][:(F - 8) // 4].contiguous(), dilate=dilate,
-                                **net.packed_alt(F))
+        return ops.node_density(dilate=dilate, **_density_sources(self.network_fn, F, self.volume.feat_volume.detach(), self.pose_source_ref, (F - 8) // 4))
 
     @torch.no_grad()
     def render_rays(self, rays, chunk=None, batch_rays=65536, skip_empty=None):
@@ -1210,14 +1216,12 @@ class MVSSystemFusion(_ModuleShim):
         rays issued as one renderer.rendering_batched call; chunk ranges are sharded over the ranks as in MVSSystemFinetune.render_rays.
         Returns (rgb (N,3), depth (N,)).
         skip_empty: None (default) is the dense render above, untouched.  A float is a density threshold: per sub-batch of batch_rays
-        rays ops.ray_march_bbox -> ops.raymarch_sparse against `self.density_volume` - the fused density of the splat, or the renderer-consistent one
+        rays ops.ray_march_bbox -> ops.raymarch_sparse (_render_sparse_batches) against `self.density_volume` - the fused density of the splat, or the renderer-consistent one
         after update_density_volume(); the sub-batches are sharded over the ranks and `self.last_live_fraction` is this rank's live samples over its
         samples."""
         from .renderer import rendering_batched
         if skip_empty is not None:          # refusals first: nothing below needs the library before them
-            skip_empty = float(skip_empty)
-            if skip_empty != skip_empty:
-                raise ValueError("render_rays: skip_empty is NaN (a density threshold, or None for the dense render)")
+            skip_empty = _threshold(skip_empty, "render_rays(skip_empty=)")
         self._need_volume()
         args = self.args
         chunk = int(chunk or args.chunk)
@@ -1227,31 +1231,18 @@ class MVSSystemFusion(_ModuleShim):
         if N == 0:
             return torch.empty((0, 3), device=dev), torch.empty((0,), device=dev)
         if skip_empty is not None:
-            net, kw = self.network_fn, self.render_kwargs_train
-            if not (isinstance(net, MVSNeRF) and getattr(kw.get("network_query_fn"), "_mvsnerf_fused", False)):
-                raise NotImplementedError("render_rays: skip_empty needs the fused configuration (what create_nerf_mvs builds)")
             vol = self.volume.feat_volume
+            src = _sparse_sources(self, vol, self.pose_source_ref, (args.feat_dim - 8) // 4, None, "render_rays(skip_empty=)")
             density = self.density_volume.reshape(vol.shape[-3:]).to(dev, torch.float32).contiguous()      # (1,1,D,H,W) as finish() leaves it
-            vol_cl = ops.channels_last_volume(vol)
-            F = args.feat_dim
-            w2cs = self.pose_source_ref["w2cs"][:(F - 8) // 4].contiguous()
-            packed, alt = net.packed(F), net.packed_alt(F)
-            white = bool(kw.get("white_bkgd", getattr(args, "white_bkgd", False)))
             lindisp = getattr(args, "use_disp", False)
             B = max(int(batch_rays), 1)
             t = torch.linspace(0, 1, args.N_samples, device=dev)
-            live = [0, 0]                   # live samples, samples
 
-            def render_batch(idx):
+            def make_batch(idx):
                 r = rays[idx * B:(idx + 1) * B]
                 pts, ndc, z = ops.ray_march_bbox(r, self.bbox_3d, args.N_samples, lindisp=lindisp, t=t)
-                o = ops.raymarch_sparse(vol_cl, None, w2cs, None, packed, pts, ndc, z, r[:, 3:6].contiguous(), density, skip_empty, white_bkgd=white, **alt)
-                live[0] += o["n_live"]
-                live[1] += z.numel()
-                return o["rgb_map"], o["depth"]
-            out = D.render_frame(render_batch, 1, N, B)
-            self.last_live_fraction = live[0] / live[1] if live[1] else 0.0
-            return out
+                return pts, ndc, z, r[:, 3:6].contiguous()
+            return _render_sparse_batches(self, N, B, make_batch, dict(src, vol_cl=ops.channels_last_volume(vol), density=density, thr=skip_empty))
         n_chunks = (N + chunk - 1) // chunk
         world, rank = D.world_rank()
         lo, hi = D.shard_range(n_chunks, world, rank)

@@ -230,3 +230,49 @@ def test_volume_grad_from_all_ranks_world2():
     expect /= 2
     for rank, gv in res:
         assert torch.allclose(torch.tensor(gv), expect, atol=1e-6), f"rank {rank}"
+
+
+def _epilogue_rows():
+    g = torch.Generator().manual_seed(77)
+    return torch.randn(5, 8, generator=g), torch.rand(5, 3, generator=g)
+
+
+def _epilogue_worker(rank, world, port, q):
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
+    D.init_from_env(device="cpu")
+    from mvsnerf_amd import ops
+    d_feat, ndc = _epilogue_rows() if rank == 0 else (torch.empty(0, 8), torch.empty(0, 3))       # rank 1: a sparse step without a live sample
+    with D.force_collectives():
+        g_vol = ops._volume_grad(torch.zeros(3, 4, 5, 8), d_feat, ndc, True, (1, 8, 3, 4, 5), have_rows=rank == 0, scatter=_cpu_scatter)
+    q.put((rank, list(g_vol.shape), g_vol.tolist()))
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+def test_volume_grad_epilogue_world2_with_an_empty_rank():
+    """The end of the sparse backward under dp_samples: a rank without rows still enters the collective (one row that scatters zeros), and both ranks
+    end with (1/world) * the scatter of rank 0's rows, in the caller's 5-D layout.  Outside the exchange, no rows means nothing is scattered."""
+    from mvsnerf_amd import ops
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=_epilogue_worker, args=(r, 2, port, q)) for r in range(2)]
+    [p.start() for p in procs]
+    res = sorted([q.get(timeout=120) for _ in procs], key=lambda t: t[0])
+    [p.join(timeout=60) for p in procs]
+    assert all(p.exitcode == 0 for p in procs)
+    d_feat, ndc = _epilogue_rows()
+    expect = torch.zeros(3, 4, 5, 8)
+    _cpu_scatter(expect, ndc, d_feat)
+    expect = (expect / 2).permute(3, 0, 1, 2).unsqueeze(0)
+    assert expect.abs().max() > 0
+    for rank, shape, gv in res:
+        assert shape == [1, 8, 3, 4, 5], f"rank {rank}"
+        assert torch.allclose(torch.tensor(gv), expect, atol=1e-6), f"rank {rank}"
+    assert torch.equal(torch.tensor(res[0][2]), torch.tensor(res[1][2]))
+
+    def no_scatter(*a):
+        raise AssertionError("scatter was called without rows")
+    for vshape, shape in (((1, 8, 3, 4, 5), (1, 8, 3, 4, 5)), ((8, 3, 4, 5), (8, 3, 4, 5))):
+        g_vol = ops._volume_grad(torch.zeros(3, 4, 5, 8), torch.empty(0, 8), torch.empty(0, 3), False, vshape, have_rows=False, scatter=no_scatter)
+        assert tuple(g_vol.shape) == shape and torch.equal(g_vol, torch.zeros(shape))
