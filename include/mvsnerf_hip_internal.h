@@ -183,6 +183,11 @@ int mvsnerf_mlp_fwd_census(const float* packed, int F,
                            const float* ndc, int ndc_stride, const float* feat, int feat_stride,
                            const float* dirs, int dirs_stride, int64_t N, int S, int alpha_only,
                            float* raw, long long* census, void* stream);
+/* Test entry: the 32 positional-encoding B operands of the fp32 MLP tiles (csrc/mlp_fp32_dev.h) for both lane halves of every point,
+ * out[P][32][2] from ndc[P][3] (contiguous).  variant 0: one evaluation per lane and k-step (pe_operand, what mvsnerf_mlp_fwd_wide runs);
+ * variant 1: the half-shared packed evaluation (pe_all, what mvsnerf_mlp_fwd, mvsnerf_mlp_fwd_train and mvsnerf_raymarch_fwd run).  The two
+ * must agree bit for bit (tests/test_gpu_pe_packed.py).  One wave per 32 points: P must be a multiple of 32 (nothing is padded), else -1. */
+int mvsnerf_pe_operands_fwd(const float* ndc, int64_t P, int variant, float* out, void* stream);
 /* Folded pack.  feature_linear and views_linears.0 have no activation between them, so a no-grad forward may run them as one affine map
  * (W' = Wv[:, :128] * Wf, b' = bv + Wv[:, :128] * bf, formed on the device in double and rounded to fp32 once).  mvsnerf_mlp_pack_fold writes
  * everything mvsnerf_mlp_pack writes - the standard layout, same offsets, same bits - sets one of the vector block's pad floats to 1.0f and appends

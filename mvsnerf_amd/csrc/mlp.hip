@@ -186,8 +186,8 @@ __device__ __forceinline__ void stage_weights(float* __restrict__ wbuf, const fl
 // Measured on MI355X: 0.237 ms per 1024x128 batch = 139 TFLOP/s = 88 % of the 157.3 TFLOP/s fp32-MFMA peak; PMC:
 // matrix pipes busy 85 % of the kernel's duration (folded: 1 720 MFMAs per wave, 83-85 % busy).  What the rest is: DESIGN.md section 4, "Where the fp32 tile's
 // idle matrix-pipe time is" - stretches of a wave's own stream without an MFMA that the partner wave of its SIMD is not there to fill (layer boundaries, the
-// start, the lone tail of the two-round grid), not the VALU instruction count: the positional encoding is evaluated once per point and stays in registers across
-// the layer loop.  Negative results kept out of the code: (i) staggering /
+// start, the lone tail of the two-round grid), and the wave's own VALU instructions, ~5 cycles each wherever they stand: the positional encoding is evaluated once
+// per point, shared between the two lanes that hold it (pe_all), and stays in registers across the layer loop.  Negative results kept out of the code: (i) staggering /
 // prioritising the two co-resident workgroups of a CU: no change; (ii) reading A fragments straight from L2 (no LDS stage, no
 // barriers): 114 TFLOP/s; (iii) 64 points per wave at one wave per SIMD: 114 TFLOP/s.
 // Same arithmetic as mlp_fwd_kernel<.., G=1, ..>, different weight logistics: the packed weights are cut into 16 slabs (folded: 14 - feature_linear's two are not
@@ -346,8 +346,8 @@ __device__ __forceinline__ void mlp_fwd_pipe_tile(
 #pragma unroll
         for (int i = 0; i < MAX_F / 2; ++i) fv[i] = i < F / 2 ? fp[i] : 0.0f;
     }
-    float bias[64], h[64];
-    auto pe = [&](int g, int t) { return pe_operand(t, half, px, py, pz); };
+    float bias[64], h[64], pe_e[PE_STEPS];
+    auto pe = [&](int g, int t) { return pe_e[t]; };
     auto hlo = [&](int g, int t) { return h[t]; };
     auto hhi = [&](int g, int t) { return h[32 + t]; };
 
@@ -388,11 +388,22 @@ __device__ __forceinline__ void mlp_fwd_pipe_tile(
 #pragma unroll
                 for (int t = 16; t < MAX_F / 2; ++t) save(S_FV_HI + t - 16, fv[t]);
             }
-#pragma unroll
-            for (int t = 0; t < PE_STEPS; ++t) save(S_E + t, pe_operand(t, half, px, py, pz));
         }
     }
     stamp();                                                                                // [5] bias gemm done
+    // The 32 positional-encoding operands, evaluated once per point (pe_all, mlp_fp32_dev.h) in front of layer 0: its GEMM, layer 5's and the
+    // training forward's activation store read these registers.  The lane half is made opaque to the compiler, so that nothing of the encoding
+    // is hoisted above the bias GEMM and carried (in the predicated kernel: spilled) across it.  Under the one-launch tile's lookups instead,
+    // between the issue of the taps and their use, the 330 instructions cost the same (profiles/pe_packed_summary.txt).
+    {
+        int half_o = half;
+        asm("" : "+v"(half_o));
+        pe_all(half_o, px, py, pz, pe_e);
+    }
+    if (SAVE) {
+#pragma unroll
+        for (int t = 0; t < PE_STEPS; ++t) save(S_E + t, pe_e[t]);
+    }
     // ---- slab 1: layer 0
     slab_sync();
     // FUSED: the rays' directions, wanted by the views GEMM, fetched here - where h is not live yet - by LDS-DMA into the 2 KB of buf0 that no
@@ -750,3 +761,33 @@ extern "C" int mvsnerf_mlp_fwd_train(const float* packed, int F, const float* nd
     return launch_mlp_pipe<false, true>(packed, F, ndc, ndc_stride, feat, feat_stride, dirs, dirs_stride, P, S, raw, (hipStream_t)stream, saved);
 }
 
+// ------------------------------------------------------------------------------------------ positional-encoding operands (test entry)
+// The tile's 32 B operands of both lane halves, as the two routines of mlp_fp32_dev.h produce them: one wave per 32 points, lane (m, half)
+// writes out[p][t][half] for its point p = 32 * block + m.  VARIANT 0: pe_operand per k-step (the per-lane evaluation mlp_wide.hip runs);
+// VARIANT 1: pe_all, what mlp_fwd_pipe_tile runs.
+template <int VARIANT>
+__global__ __launch_bounds__(64) void pe_operands_kernel(const float* __restrict__ ndc, float* __restrict__ out)
+{
+    const int lane = threadIdx.x, half = lane >> 5;
+    const int64_t p = (int64_t)blockIdx.x * 32 + (lane & 31);
+    const float px = ndc[p * 3 + 0], py = ndc[p * 3 + 1], pz = ndc[p * 3 + 2];
+    float e[PE_STEPS];
+    if constexpr (VARIANT == 0) {
+#pragma unroll
+        for (int t = 0; t < PE_STEPS; ++t) e[t] = pe_operand(t, half, px, py, pz);
+    } else {
+        pe_all(half, px, py, pz, e);
+    }
+#pragma unroll
+    for (int t = 0; t < PE_STEPS; ++t) out[(p * PE_STEPS + t) * 2 + half] = e[t];
+}
+
+extern "C" int mvsnerf_pe_operands_fwd(const float* ndc, int64_t P, int variant, float* out, void* stream)
+{
+    if (!ndc || !out || P < 0 || (P & 31) || P / 32 > 0x7fffffff || (variant != 0 && variant != 1)) return MVSNERF_EINVAL;
+    if (P == 0) return MVSNERF_OK;
+    if (variant == 0) pe_operands_kernel<0><<<(unsigned)(P / 32), 64, 0, (hipStream_t)stream>>>(ndc, out);
+    else pe_operands_kernel<1><<<(unsigned)(P / 32), 64, 0, (hipStream_t)stream>>>(ndc, out);
+    MVS_LAUNCH_CHECK();
+    return MVSNERF_OK;
+}

@@ -96,6 +96,75 @@ __device__ __forceinline__ float pe_operand(int t, int half, float px, float py,
     return pe_sin_or_cos(x, half);
 }
 
+// The same encoding, evaluated once per point instead of once per lane: pe_operand above makes lane (m, half 0) and lane (m, half 1) reduce the
+// same 30 angles and evaluate both polynomials on each, to keep sin in one lane and cos in the other.  Here a lane evaluates 15 of the angles -
+// half 0 the even frequencies f = 2m, half 1 the odd ones f = 2m + 1 - keeps both values and trades one of each pair with its partner lane.
+//
+// pe_sincos2: pe_sin_or_cos's operations in its order on two angles at once.  The multiplies and fmas are written on float2 (v_pk_mul_f32,
+// v_pk_fma_f32: the IEEE operation per component, so the bits are pe_sin_or_cos's); clamp, rintf and the quadrant select have no packed form and
+// stay per component.  sin takes quadrant k, cos quadrant k + 1 of the same (sn, cs); the sign is an xor of the sign bit, which is what the
+// negation of pe_sin_or_cos does to every input.
+typedef float pe_f32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ void pe_sincos2(pe_f32x2 x, pe_f32x2& s, pe_f32x2& c)
+{
+    x[0] = fminf(fmaxf(x[0], -65536.0f), 65536.0f);
+    x[1] = fminf(fmaxf(x[1], -65536.0f), 65536.0f);
+    const pe_f32x2 kx = x * pe_f32x2{0.63661977236758134f, 0.63661977236758134f};
+    const pe_f32x2 k = {rintf(kx[0]), rintf(kx[1])};
+    auto fma2 = [](pe_f32x2 a, pe_f32x2 b, pe_f32x2 d) { return __builtin_elementwise_fma(a, b, d); };
+    auto all = [](float v) { return pe_f32x2{v, v}; };
+    pe_f32x2 r = fma2(k, all(-1.5703125f), x);
+    r = fma2(k, all(-4.837512969970703125e-4f), r);
+    r = fma2(k, all(-7.54978995489188e-8f), r);
+    const pe_f32x2 r2 = r * r;
+    const pe_f32x2 sp = fma2(fma2(all(-1.9515295891e-4f), r2, all(8.3321608736e-3f)), r2, all(-1.6666654611e-1f));
+    const pe_f32x2 sn = fma2(sp * r2, r, r);
+    const pe_f32x2 cp = fma2(fma2(all(2.443315711809948e-5f), r2, all(-1.388731625493765e-3f)), r2, all(4.166664568298827e-2f));
+    const pe_f32x2 cs = fma2(cp * r2, r2, fma2(all(-0.5f), r2, all(1.0f)));
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const unsigned q = (unsigned)(int)k[i];
+        const bool odd = q & 1u;
+        s[i] = __uint_as_float(__float_as_uint(odd ? cs[i] : sn[i]) ^ ((q & 2u) << 30));
+        c[i] = __uint_as_float(__float_as_uint(odd ? sn[i] : cs[i]) ^ (((q + 1u) & 2u) << 30));
+    }
+}
+
+// All 32 positional-encoding B operands of this lane: e[t] has the bits of pe_operand(t, half, px, py, pz).  The angle of (f, c) is coord_c * 2^f
+// as there (the same multiplication; the scale is selected by lane half).  Lane (m, half) evaluates (f = 2m' + half, c) for m' = 0..4, c = 0..2;
+// its sin values are sv, its cos values cv.  Operand t = 2 + 3f + c wants sin in half 0 and cos in half 1: for an even f half 0 has its own sin
+// and half 1 needs half 0's cos, for the odd f above it half 1 has its own cos and half 0 needs half 1's sin.  v_permlane32_swap(sv, cv) exchanges
+// lanes 32-63 of sv with lanes 0-31 of cv, which is exactly that trade: afterwards sv is operand (2m', c) and cv operand (2m' + 1, c) in every
+// lane - one VALU instruction per two operands.
+__device__ __forceinline__ void pe_all(int half, float px, float py, float pz, float (&e)[32])
+{
+    e[0] = half ? py : px;
+    e[1] = half ? 0.0f : pz;
+    const float co[3] = {px, py, pz};
+    float x[16], sv[16], cv[16];
+#pragma unroll
+    for (int m = 0; m < 5; ++m) {
+        const float scale = half ? (float)(2 << (2 * m)) : (float)(1 << (2 * m));
+#pragma unroll
+        for (int c = 0; c < 3; ++c) x[3 * m + c] = co[c] * scale;
+    }
+    x[15] = x[14];                                        // 15 angles, eight pairs
+#pragma unroll
+    for (int i = 0; i < 16; i += 2) {
+        pe_f32x2 s2, c2;
+        pe_sincos2(pe_f32x2{x[i], x[i + 1]}, s2, c2);
+        sv[i] = s2[0]; sv[i + 1] = s2[1]; cv[i] = c2[0]; cv[i + 1] = c2[1];
+    }
+#pragma unroll
+    for (int m = 0; m < 5; ++m)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(sv[3 * m + c]), __float_as_uint(cv[3 * m + c]), false, false);
+            e[2 + 6 * m + c] = __uint_as_float(sw[0]);
+            e[5 + 6 * m + c] = __uint_as_float(sw[1]);
+        }
+}
+
 __device__ __forceinline__ void slab_dma(float* __restrict__ dst, const float* __restrict__ src, int n_floats, int wave, int lane)
 {
     lds_dma<4>(dst, src, n_floats >> 8, wave, lane);     // 1 KB per wave-instruction, scalar base + one lane offset (lds_dma.h)
