@@ -405,6 +405,34 @@ int mvsnerf_live_samples_fwd(const float* density, int D, int H, int W, float th
                              int64_t N, int S, int* count, int* idx, float* ndc_c, float* pts_c, float* dir_c, void* workspace, void* stream);
 int mvsnerf_expand_rows_fwd(const float* src, const int* idx, const int* count, int64_t src_rows, int64_t P, int C, float* dst, void* stream);
 int mvsnerf_compact_rows_fwd(const float* src, const int* idx, const int* count, int64_t P, int64_t dst_rows, int C, float* dst, void* stream);
+/* ---- early ray termination in no-grad renders (no reference counterpart: renderer.py:18-26 composites all S samples; csrc/sparse.hip) ----
+ * A ray batch is marched in segments of stop_every samples; between two segments the transmittance in front of the next one decides which rays go on.
+ * These three entries answer a misaligned pointer with MVSNERF_EINVAL, like a NULL one; every check comes before the first launch.
+ * ray_transmittance: ray_T[n] *= prod_{s0 <= s < s1} ((1 - alpha) + 1e-10f), alpha = 1 - expf(-raw[n][s][3]): the two expressions of compositing
+ *   (csrc/composite_wave.h holds them for both).  raw [N][S][4], 16-byte aligned; ray_T [N], caller-owned, set to 1 by the host before the first
+ *   window.  The order is fixed: T = ray_T[n]; for s = s0 .. s1 - 1 ascending: T = fl(T * factor_s); ray_T[n] = T - so consecutive windows give the bits
+ *   of one left-to-right product, and two runs give the same bytes.  A NaN sigma gives a NaN ray_T.  Four lanes own a ray and read rows s, s+1, s+2, s+3:
+ *   (s1 - s0) * 16 bytes of raw are touched per ray, in whole 64-byte lines when n * S + s0 is a multiple of 4.  One launch, no LDS, no atomics.
+ *   MVSNERF_EINVAL: NULL or misaligned raw / ray_T, N < 0, S < 1, a window with s0 < 0, s1 > S or s0 >= s1; MVSNERF_EUNSUPPORTED: N * S >= 2^31.
+ * live_samples_range: live_samples over the window s0 <= s < s1 of every ray.  A sample is SELECTED iff !(ray_T[n] < eps) when ray_T is given (fp32
+ *   compare; a NaN ray_T never stops its ray) and its cell is live by live_samples' predicate when density is given (both NULL: the whole window).
+ *   count[0] = number selected; idx[j] = n * S + s of the j-th, ASCENDING; ndc_c / pts_c / dir_c as live_samples leaves them.  idx and the compact
+ *   rows hold N * (s1 - s0) entries (the worst case); entries from count on are not written.  The same three launches as live_samples (its scan kernel,
+ *   the RANGE instantiations of its count and write tiles): no atomics, no workgroup waits on another, two runs give the same bytes, count stays on
+ *   the device.  workspace: live_samples_range_workspace_bytes(N, s1 - s0) bytes (0: N < 1, a window < 1 or N * window >= 2^31), 8-byte aligned.
+ *   MVSNERF_EINVAL: NULL count (ndc / idx / ndc_c / workspace with N > 0), pts without pts_c or rays_dir without dir_c, a misaligned pointer, N < 0,
+ *   S < 1, a bad window, a NaN eps, and with density: D, H or W < 1 or a NaN thr; MVSNERF_EUNSUPPORTED: N * S >= 2^31.  N == 0 writes count = 0.
+ * scatter_rows: dst[idx[j]] = src[j] for j < min(count[0], src_rows); every other row of dst [P][C] is left untouched (expand_rows rewrites all P
+ *   rows; this one adds a segment's rows to a raw the host zero-filled once).  idx[j] is range-checked against [0, P) before the store: an entry
+ *   outside writes nothing.  Distinct entries (what live_samples_range leaves) make the result independent of the order of the stores.  C == 4 with
+ *   16-byte aligned src and dst moves one 16-byte load and store per row; src / idx may be NULL with src_rows == 0, which launches nothing.
+ *   MVSNERF_EINVAL: NULL or misaligned count / dst (src / idx with src_rows > 0), src_rows < 0 or > P, P < 0, C < 1; MVSNERF_EUNSUPPORTED: C > 64, P >= 2^31. */
+int mvsnerf_ray_transmittance_fwd(const float* raw, int64_t N, int S, int s0, int s1, float* ray_T, void* stream);
+size_t mvsnerf_live_samples_range_workspace_bytes(int64_t N, int G);
+int mvsnerf_live_samples_range_fwd(const float* density, int D, int H, int W, float thr, const float* ndc, const float* pts, const float* rays_dir,
+                                   int64_t N, int S, int s0, int s1, const float* ray_T, float eps, int* count, int* idx, float* ndc_c,
+                                   float* pts_c, float* dir_c, void* workspace, void* stream);
+int mvsnerf_scatter_rows_fwd(const float* src, const int* idx, const int* count, int64_t src_rows, int64_t P, int C, float* dst, void* stream);
 /* ---- a density volume in the renderer's own frame (no reference counterpart; csrc/occupancy.hip) ----
  * voxel_points: the nodes (k,j,i) of planes [d0, d1) of a [D][H][W] volume, rows in [k][j][i] order: ndc[(d1-d0) H W][3] = (i/(W-1), j/(H-1), k/(D-1)), IEEE
  *   divisions, 0 on an axis of size 1 - the coordinates whose trilinear cell starts exactly on the node, whether the volume is a reference frustum or a

@@ -271,6 +271,11 @@ SIGNATURES = {
     "mvsnerf_live_samples_fwd": (_c_i, [_c_fp, _c_i, _c_i, _c_i, ctypes.c_float, _c_fp, _c_fp, _c_fp, _c_l, _c_i] + [_c_fp] * 7),
     "mvsnerf_expand_rows_fwd": (_c_i, [_c_fp, _c_fp, _c_fp, _c_l, _c_l, _c_i, _c_fp, _c_fp]),
     "mvsnerf_compact_rows_fwd": (_c_i, [_c_fp, _c_fp, _c_fp, _c_l, _c_l, _c_i, _c_fp, _c_fp]),
+    "mvsnerf_ray_transmittance_fwd": (_c_i, [_c_fp, _c_l, _c_i, _c_i, _c_i, _c_fp, _c_fp]),
+    "mvsnerf_live_samples_range_workspace_bytes": (ctypes.c_size_t, [_c_l, _c_i]),
+    "mvsnerf_live_samples_range_fwd": (_c_i, [_c_fp, _c_i, _c_i, _c_i, ctypes.c_float, _c_fp, _c_fp, _c_fp, _c_l, _c_i, _c_i, _c_i, _c_fp, ctypes.c_float]
+                                       + [_c_fp] * 7),
+    "mvsnerf_scatter_rows_fwd": (_c_i, [_c_fp, _c_fp, _c_fp, _c_l, _c_l, _c_i, _c_fp, _c_fp]),
     "mvsnerf_voxel_points_fwd": (_c_i, [_c_i] * 5 + [_c_fp] * 3 + [_c_i] * 4 + [_c_fp] * 3),
     "mvsnerf_max_dilate3d_fwd": (_c_i, [_c_fp] + [_c_i] * 4 + [_c_fp] * 3),
 }

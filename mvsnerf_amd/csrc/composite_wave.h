@@ -17,6 +17,11 @@ __device__ __forceinline__ void mvs_guard_consume(int* guard)
     if (guard[0]) { guard[1] += 1; guard[0] = 0; }
 }
 
+// alpha of a sample (renderer.py:22, dist ignored) and the factor it puts on the transmittance behind it (:24): the two expressions of compositing,
+// here once so that the running transmittance of early ray termination (ray_transmittance_kernel, sparse.hip) cannot drift from them.
+__device__ __forceinline__ float raw2alpha(float sigma) { return 1.0f - expf(-sigma); }
+__device__ __forceinline__ float transmittance_step(float alpha) { return (1.0f - alpha) + 1e-10f; }
+
 // lane l owns samples s0 = l*NR .. s0+NR-1 (values rv[i] = {r,g,b,sigma}; samples >= S are ignored), zr = z_vals of the ray
 template <int NR>
 __device__ __forceinline__ void composite_wave(const f32x4 (&rv)[NR], const float* __restrict__ zr, int64_t ray, int S, int lane, const CompositeOut& o)
@@ -26,7 +31,7 @@ __device__ __forceinline__ void composite_wave(const f32x4 (&rv)[NR], const floa
     float prod = 1.0f;
 #pragma unroll
     for (int i = 0; i < NR; ++i)
-        if (s0 + i < S) prod *= (1.0f - (1.0f - expf(-rv[i][3]))) + 1e-10f;
+        if (s0 + i < S) prod *= transmittance_step(raw2alpha(rv[i][3]));
     // inclusive multiplicative scan over lanes, then shift to exclusive
     float scan = prod;
 #pragma unroll
@@ -42,9 +47,9 @@ __device__ __forceinline__ void composite_wave(const f32x4 (&rv)[NR], const floa
         const int s = s0 + i;
         if (s < S) {
             const f32x4 v = rv[i];
-            const float a = 1.0f - expf(-v[3]);                 // renderer.py:22  (dist ignored)
+            const float a = raw2alpha(v[3]);                    // renderer.py:22  (dist ignored)
             const float w = a * T;                              // :25
-            T *= (1.0f - a) + 1e-10f;                           // :24
+            T *= transmittance_step(a);                         // :24
             sr += w * v[0]; sg += w * v[1]; sb += w * v[2];
             sd += w * zr[s]; sa += w;
             if (o.weights) o.weights[ray * S + s] = w;

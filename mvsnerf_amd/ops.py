@@ -874,18 +874,24 @@ def _sparse_march(vol_cl, imgs, w2cs, intrinsics, rays_pts, rays_ndc, z_vals, ra
     color_vol = vol_cl.shape[-1] != 8
     count, idx, ndc_c, pts_c, dir_c = live_samples(density, rays_ndc, thr, None if color_vol else rays_pts, rays_dir)
     n_live = int(count.item())
-    ndc_l = ndc_c[:n_live]
-    if n_live:
-        ndc_g, dir_l = ndc_l.view(n_live, 1, 3), dir_c[:n_live]
-        if color_vol:
-            feat, dirs = gather_colorvol(vol_cl, ndc_g, dir_l, w2cs[0].contiguous())
-        else:
-            feat, dirs = gather(vol_cl, imgs, w2cs, intrinsics, pts_c[:n_live].view(n_live, 1, 3), ndc_g, dir_l)
-        raw_c = mlp(ndc_l, feat, dirs, n_live)
-    else:
-        raw_c = torch.empty((0, 4), device=rays_ndc.device, dtype=torch.float32)
+    ndc_l, raw_c = _compact_rows_mlp(vol_cl, imgs, w2cs, intrinsics, ndc_c, pts_c, dir_c, n_live, mlp)
     raw = expand_rows(raw_c, idx, count, N * S).view(N, S, 4)
     return (idx, count, ndc_l, raw_c, raw, n_live), composite(raw, z_vals, white_bkgd)
+
+
+def _compact_rows_mlp(vol_cl, imgs, w2cs, intrinsics, ndc_c, pts_c, dir_c, n, mlp):
+    """The gather-and-MLP stage of the compacted marches (_sparse_march, raymarch_early_stop) on the first n compact rows of ops.live_samples /
+    ops.live_samples_range: ops.gather (ops.gather_colorvol for a colour volume) on the rows as (n,1,3) -> mlp(ndc_l, feat, dirs, n).  n == 0 enqueues
+    nothing.  Returns (ndc_l (n,3), raw_c (n,4))."""
+    ndc_l = ndc_c[:n]
+    if not n:
+        return ndc_l, torch.empty((0, 4), device=ndc_c.device, dtype=torch.float32)
+    ndc_g, dir_l = ndc_l.view(n, 1, 3), dir_c[:n]
+    if vol_cl.shape[-1] != 8:
+        feat, dirs = gather_colorvol(vol_cl, ndc_g, dir_l, w2cs[0].contiguous())
+    else:
+        feat, dirs = gather(vol_cl, imgs, w2cs, intrinsics, pts_c[:n].view(n, 1, 3), ndc_g, dir_l)
+    return ndc_l, mlp(ndc_l, feat, dirs, n)
 
 
 def raymarch_sparse(vol_cl, imgs, w2cs, intrinsics, packed, rays_pts, rays_ndc, z_vals, rays_dir, density, thr, white_bkgd=False, want=(), **packed_alt):
@@ -902,6 +908,142 @@ def raymarch_sparse(vol_cl, imgs, w2cs, intrinsics, packed, rays_pts, rays_ndc, 
         vol_cl, imgs, w2cs, intrinsics, rays_pts, rays_ndc, z_vals, rays_dir, density, thr, white_bkgd,
         lambda ndc_l, feat, dirs, n: mlp_forward(packed, F, ndc_l.data_ptr(), 3, feat.data_ptr(), F, dirs.data_ptr(), 3, n, 1, 0, rays_ndc.device, **packed_alt))
     out = {"raw": raw, "rgb_map": rgb, "weights": weights, "depth": depth, "alpha": alpha, "n_live": n_live}
+    out.update({k: v for k, v in (("disp", disp), ("acc", acc)) if k in want})
+    return out
+
+
+# ------------------------------------------------------------------ early ray termination (csrc/sparse.hip)
+def _early_stop_args(eps, stop_every, op):
+    """(eps, stop_every) of an early_stop call as (float, int) after the refusals: eps in [0, 1) (NaN refused), stop_every an integer >= 1."""
+    eps = float(eps)
+    if not (0.0 <= eps < 1.0):                      # NaN fails both compares
+        raise ValueError(f"{op}: early_stop (eps) must be a transmittance in [0, 1), got {eps}")
+    if isinstance(stop_every, bool) or int(stop_every) != stop_every or int(stop_every) < 1:
+        raise ValueError(f"{op}: stop_every must be an integer >= 1, got {stop_every}")
+    return eps, int(stop_every)
+
+
+def _window(S, s0, s1, op):
+    s0, s1 = int(s0), int(s1)
+    if not (0 <= s0 < s1 <= S):
+        raise RuntimeError(f"{op}: the window [{s0}, {s1}) is not inside the {S} samples of a ray")
+    return s0, s1
+
+
+def ray_transmittance(raw, s0, s1, ray_T):
+    """ray_T[n] *= prod_{s0 <= s < s1} ((1 - alpha) + 1e-10), alpha = 1 - exp(-raw[n,s,3]), in place (mvsnerf_ray_transmittance_fwd): raw (N,S,4) and
+    ray_T (N,) contiguous fp32 device tensors, ray_T set to 1 by the caller before the first window.  Ascending s, every product rounded - compositing's
+    running transmittance, whatever the windows are.  Returns ray_T."""
+    _need_no_grad(raw, ray_T, op="ray_transmittance")
+    if raw.dim() != 3 or raw.shape[-1] != 4 or tuple(ray_T.shape) != (raw.shape[0],) or not (raw.is_contiguous() and ray_T.is_contiguous()):
+        raise RuntimeError(f"ray_transmittance: raw must be a contiguous (N,S,4) and ray_T (N,), got {tuple(raw.shape)} and {tuple(ray_T.shape)}")
+    N, S = int(raw.shape[0]), int(raw.shape[1])
+    s0, s1 = _window(S, s0, s1, "ray_transmittance")
+    if N:
+        check(_lib.lib().mvsnerf_ray_transmittance_fwd(dev_f32(raw, "raw"), N, S, s0, s1, dev_f32(ray_T, "ray_T"), stream_ptr()), "ray_transmittance_fwd")
+    return ray_T
+
+
+def live_samples_range(density, rays_ndc, thr, s0, s1, ray_T=None, eps=0.0, rays_pts=None, rays_dir=None):
+    """ops.live_samples over the window s0 <= s < s1 of every ray (mvsnerf_live_samples_range_fwd): a sample is selected iff not (ray_T[n] < eps) when
+    ray_T (N,) is given, and its cell is live in `density` at `thr` when density is given (density None: thr is not read).  Returns (count, idx, ndc_c,
+    pts_c, dir_c) as ops.live_samples, idx holding the flat indices n*S + s, ascending; the buffers have N * (s1 - s0) entries."""
+    _need_no_grad(density, rays_ndc, rays_pts, rays_dir, ray_T, op="live_samples_range")
+    thr = 0.0 if density is None else _thr_f32(thr, "live_samples_range")
+    eps = float(eps)
+    if eps != eps:
+        raise ValueError("live_samples_range: eps is NaN")
+    if density is not None and density.dim() != 3:
+        raise RuntimeError(f"live_samples_range: density must be (D,H,W), got {tuple(density.shape)}")
+    if rays_ndc.dim() != 3 or rays_ndc.shape[-1] != 3:
+        raise RuntimeError(f"live_samples_range: rays_ndc must be (N,S,3), got {tuple(rays_ndc.shape)}")
+    N, S = int(rays_ndc.shape[0]), int(rays_ndc.shape[1])
+    if rays_pts is not None and tuple(rays_pts.shape) != (N, S, 3):
+        raise RuntimeError(f"live_samples_range: rays_pts must be ({N},{S},3), got {tuple(rays_pts.shape)}")
+    if rays_dir is not None and tuple(rays_dir.shape) != (N, 3):
+        raise RuntimeError(f"live_samples_range: rays_dir must be ({N},3), got {tuple(rays_dir.shape)}")
+    if ray_T is not None and tuple(ray_T.shape) != (N,):
+        raise RuntimeError(f"live_samples_range: ray_T must be ({N},), got {tuple(ray_T.shape)}")
+    if S < 1 or N * S >= 2 ** 31:
+        raise RuntimeError(f"live_samples_range: {N} x {S} samples: S >= 1 and fewer than 2^31 samples (idx is int32)")
+    s0, s1 = _window(S, s0, s1, "live_samples_range")
+    lib = _lib.lib()
+    dev = rays_ndc.device
+    D, H, W = (0, 0, 0) if density is None else density.shape
+    P = N * (s1 - s0)
+    c = _Keep()
+    opt = lambda t, name: 0 if t is None else c(t, name)
+    count = torch.empty((1,), device=dev, dtype=torch.int32)
+    idx = torch.empty((P,), device=dev, dtype=torch.int32)
+    rows = [torch.empty((P, 3), device=dev, dtype=torch.float32) if t is not None else None for t in (rays_ndc, rays_pts, rays_dir)]
+    ws = torch.empty((max(int(lib.mvsnerf_live_samples_range_workspace_bytes(N, s1 - s0)), 8) // 8,), device=dev, dtype=torch.int64)
+    check(lib.mvsnerf_live_samples_range_fwd(opt(density, "density"), D, H, W, thr, c(rays_ndc, "rays_ndc"), opt(rays_pts, "rays_pts"),
+                                             opt(rays_dir, "rays_dir"), N, S, s0, s1, opt(ray_T, "ray_T"), eps, count.data_ptr(), idx.data_ptr(),
+                                             *[0 if r is None else r.data_ptr() for r in rows], ws.data_ptr(), stream_ptr()), "live_samples_range_fwd")
+    return (count, idx, *rows)
+
+
+def scatter_rows(src, idx, count, dst):
+    """dst[idx[j]] = src[j] for j < count, every other row of dst (P,C) untouched (mvsnerf_scatter_rows_fwd): src (n,C) fp32, idx / count as
+    ops.live_samples_range returns them (count is read on the device and clamped to n; an idx entry outside [0, P) writes nothing).  Returns dst."""
+    _need_no_grad(src, dst, op="scatter_rows")
+    if src.dim() != 2 or dst.dim() != 2 or src.shape[1] != dst.shape[1] or not dst.is_contiguous():
+        raise RuntimeError(f"scatter_rows: src must be (n,C) and dst a contiguous (P,C), got {tuple(src.shape)} and {tuple(dst.shape)}")
+    n, C, P = int(src.shape[0]), int(src.shape[1]), int(dst.shape[0])
+    if not (idx.dtype == torch.int32 and idx.is_cuda and idx.is_contiguous() and count.dtype == torch.int32 and count.is_cuda and count.numel() == 1):
+        raise RuntimeError("scatter_rows: idx and count are the int32 device tensors of ops.live_samples_range")
+    if n > P or idx.numel() < n:
+        raise RuntimeError(f"scatter_rows: {n} source rows, {idx.numel()} indices, {P} destination rows")
+    if n:
+        c = _Keep()
+        check(_lib.lib().mvsnerf_scatter_rows_fwd(c(src, "src"), idx.data_ptr(), count.data_ptr(), n, P, C, dev_f32(dst, "scatter_rows: dst"), stream_ptr()),
+              "scatter_rows_fwd")
+    return dst
+
+
+def raymarch_early_stop(vol_cl, imgs, w2cs, intrinsics, packed, rays_pts, rays_ndc, z_vals, rays_dir, eps, stop_every=32, density=None, thr=None,
+                        white_bkgd=False, want=(), **packed_alt):
+    """ops.raymarch's outputs with rays stopped once they are opaque: the S samples are marched in segments of stop_every; a ray whose
+    transmittance in front of a segment, T = prod ((1 - alpha) + 1e-10) over the samples before it (fp32, compositing's expression and order), is
+    < eps is stopped there - its remaining samples do not reach the gather or the MLP and have raw = (0,0,0,0).  Every other sample has the bits of
+    the dense sequence.  With density / thr (together or not at all) a sample also has to be live by ops.live_samples' predicate: then "dense" is
+    ops.raymarch_sparse.  Per segment, in stream order: live_samples_range (with ray_T from the second segment on) -> ONE host read of the count (at 0
+    nothing more is enqueued for the segment) -> the gather-and-MLP stage of _sparse_march on the compact rows -> scatter_rows into the zero-filled
+    raw -> ray_transmittance over the segment (not after the last one); then ops.composite.  eps = 0 stops no ray: every output equals the dense call's.
+    The dropped weights of a ray sum to less than eps (1 + S 1e-10): rgb_map and acc move by at most eps, depth by eps max|z|.
+    Returns raymarch_sparse's dict plus n_live (samples that went through the MLP) and n_stopped (rays stopped at some boundary)."""
+    eps, G = _early_stop_args(eps, stop_every, "raymarch_early_stop")
+    if (density is None) != (thr is None):
+        raise ValueError("raymarch_early_stop: density and thr are given together or not at all")
+    _need_no_grad(vol_cl, imgs, rays_pts, rays_ndc, z_vals, rays_dir, density, op="raymarch_early_stop")
+    if thr is not None:
+        thr = _thr_f32(thr, "raymarch_early_stop")
+    C = vol_cl.shape[-1]
+    color_vol = C != 8
+    F = C if color_vol else 8 + 4 * imgs.shape[0]
+    if color_vol and C != 8 + 4 * w2cs.shape[0]:
+        raise RuntimeError(f"raymarch_early_stop: the volume has {C} channels, 8 + 4V is {8 + 4 * w2cs.shape[0]}")
+    N, S = z_vals.shape
+    dev = rays_ndc.device
+    mlp = lambda ndc_l, feat, dirs, n: mlp_forward(packed, F, ndc_l.data_ptr(), 3, feat.data_ptr(), F, dirs.data_ptr(), 3, n, 1, 0, dev, **packed_alt)
+    raw = torch.zeros((N, S, 4), device=dev, dtype=torch.float32)
+    bounds = list(range(0, S, G)) + [S]
+    ray_T = torch.ones((N,), device=dev, dtype=torch.float32) if len(bounds) > 2 else None
+    n_live, n_stopped = 0, 0
+    for k, (s0, s1) in enumerate(zip(bounds[:-1], bounds[1:])):
+        count, idx, ndc_c, pts_c, dir_c = live_samples_range(density, rays_ndc, thr, s0, s1, ray_T if k else None, eps,
+                                                             None if color_vol else rays_pts, rays_dir)
+        if s1 == S and ray_T is not None:           # the last segment: the stopped rays travel with its count, one host read
+            n, n_stopped = torch.stack((count[0], (ray_T < eps).sum(dtype=torch.int32))).tolist()
+        else:
+            n = int(count.item())
+        n_live += n
+        _, raw_c = _compact_rows_mlp(vol_cl, imgs, w2cs, intrinsics, ndc_c, pts_c, dir_c, n, mlp)
+        scatter_rows(raw_c, idx, count, raw.view(N * S, 4))
+        if s1 < S:
+            ray_transmittance(raw, s0, s1, ray_T)
+    rgb, disp, acc, weights, depth, alpha = composite(raw, z_vals, white_bkgd)
+    out = {"raw": raw, "rgb_map": rgb, "weights": weights, "depth": depth, "alpha": alpha, "n_live": n_live, "n_stopped": n_stopped}
     out.update({k: v for k, v in (("disp", disp), ("acc", acc)) if k in want})
     return out
 

@@ -146,21 +146,36 @@ def _density_sources(net, F, vol, pose, V, imgs=None, **camera):
     return dict(vol_cl=ops.channels_last_volume(vol), packed=net.packed(F), w2cs=pose["w2cs"][:V].contiguous(), **src, **net.packed_alt(F))
 
 
-def _render_sparse_batches(system, n_rows, B, make_batch, march_kw):
+def _early_stop(early_stop, stop_every, who):
+    """early_stop= / stop_every= of a render call after ops._early_stop_args' refusals: None (no early stop), or (eps, stop_every)."""
+    return None if early_stop is None else ops._early_stop_args(early_stop, stop_every, f"{who}(early_stop=)")
+
+
+def _render_sparse_batches(system, n_rows, B, make_batch, march_kw, early_stop=None):
     """A frame of n_rows rays with empty space skipped, per sub-batch of B rays: make_batch(idx) -> (pts, ndc, z, dirs) of rays [idx * B, (idx + 1) * B)
     -> ops.raymarch_sparse(**march_kw: vol_cl, imgs, w2cs, intrinsics, packed, density, thr, white_bkgd and the kernel choice) - one host read of
     the live count per sub-batch.  The sub-batches are sharded over the ranks (distributed.render_frame); system.last_live_fraction is this rank's
-    live samples over its samples.  Returns (rgb (n_rows,3), depth (n_rows,))."""
-    live = [0, 0]                   # live samples, samples
+    live samples over its samples.  Returns (rgb (n_rows,3), depth (n_rows,)).
+    early_stop: (eps, stop_every) of _early_stop - the sub-batch call is ops.raymarch_early_stop (march_kw with or without density /
+    thr), one host read per segment of stop_every samples; last_live_fraction then counts the samples that reached the MLP, and
+    system.last_stopped_fraction is this rank's stopped rays over its rays."""
+    live = [0, 0, 0, 0]             # live samples, samples, stopped rays, rays
 
     def render_batch(idx):
         pts, ndc, z, dirs = make_batch(idx)
-        o = ops.raymarch_sparse(rays_pts=pts, rays_ndc=ndc, z_vals=z, rays_dir=dirs, **march_kw)
+        if early_stop is None:
+            o = ops.raymarch_sparse(rays_pts=pts, rays_ndc=ndc, z_vals=z, rays_dir=dirs, **march_kw)
+        else:
+            o = ops.raymarch_early_stop(rays_pts=pts, rays_ndc=ndc, z_vals=z, rays_dir=dirs, eps=early_stop[0], stop_every=early_stop[1], **march_kw)
+            live[2] += o["n_stopped"]
+            live[3] += z.shape[0]
         live[0] += o["n_live"]
         live[1] += z.numel()
         return o["rgb_map"], o["depth"]
     out = D.render_frame(render_batch, 1, n_rows, B)
     system.last_live_fraction = live[0] / live[1] if live[1] else 0.0
+    if early_stop is not None:
+        system.last_stopped_fraction = live[2] / live[3] if live[3] else 0.0
     return out
 
 
@@ -314,7 +329,8 @@ class MVSSystem(_ModuleShim):
                                                                   near_far=near_fars[0], ref_hw=(H, W), pad=args.pad))
 
     @torch.no_grad()
-    def render_view(self, batch, chunk=None, whole_frame_off=False, target=None, batch_rays=16384, volume=None, skip_empty=None, density=None, dilate=0):
+    def render_view(self, batch, chunk=None, whole_frame_off=False, target=None, batch_rays=16384, volume=None, skip_empty=None, density=None, dilate=0,
+                    early_stop=None, stop_every=32):
         """The rendering part of validation_step (:172-254): encode once, then the chunk loop over the target view's
         pixels - tile-parallel over ranks (contiguous chunk ranges + one all_gather).  Returns (rgb (H,W,3), depth (H,W)).
         whole_frame_off=True keeps the per-chunk Python loop (build_rays_test + rendering per chunk) instead of the single
@@ -332,8 +348,15 @@ class MVSSystem(_ModuleShim):
         sharded over the ranks, one host read of the live count per sub-batch; `self.last_live_fraction` is this rank's live samples over its samples.
         netwidth 256, net_type v2 and colour volumes take the same path.  density: (D,h,w) of the volume in use - default
         scene_density(batch, volume, dilate), built on every call: a camera path should build it once (render_path_skip_empty does) and pass it.  dilate is
-        read only when the density is built here."""
-        if skip_empty is not None:          # refusals first: nothing below needs the library before them
+        read only when the density is built here.
+        early_stop: None (default) changes nothing.  A float eps in [0, 1) stops a ray at the first multiple of stop_every samples in front of which its
+        transmittance is < eps (ops.raymarch_early_stop per sub-batch, one host read per segment; rgb moves by at most eps, depth by
+        eps max|z|).  Alone it needs no density volume; with skip_empty a sample reaches the MLP iff its ray is alive and its cell is live.
+        `self.last_stopped_fraction` is this rank's stopped rays over its rays, last_live_fraction the samples that reached the MLP."""
+        stop = _early_stop(early_stop, stop_every, "render_view")          # refusals first: nothing below needs the library before them
+        if stop is not None and whole_frame_off:
+            raise ValueError("render_view: early_stop runs its own per-sub-batch loop; it cannot be combined with whole_frame_off=True")
+        if skip_empty is not None:
             if whole_frame_off:
                 raise ValueError("render_view: skip_empty runs its own per-sub-batch loop; it cannot be combined with whole_frame_off=True")
             skip_empty = _threshold(skip_empty, "render_view(skip_empty=)")
@@ -366,13 +389,14 @@ class MVSSystem(_ModuleShim):
 
         kw = self.render_kwargs_train
         net = kw["network_fn"]
-        if skip_empty is not None:
-            src = _sparse_sources(self, volume_feature, pose_ref, V, imgs[0, :-1], "skip_empty / scene_density")
-            if density is None:
-                density = self.scene_density(batch, volume=volume_feature, dilate=dilate)
-            if tuple(density.shape) != tuple(volume_feature.shape[-3:]):
-                raise RuntimeError(f"render_view: density {tuple(density.shape)} is not the (D,h,w) of the volume {tuple(volume_feature.shape)}")
-            density = density.to(imgs.device, torch.float32).contiguous()
+        if skip_empty is not None or stop is not None:
+            src = _sparse_sources(self, volume_feature, pose_ref, V, imgs[0, :-1], "skip_empty / early_stop / scene_density")
+            if skip_empty is not None:
+                if density is None:
+                    density = self.scene_density(batch, volume=volume_feature, dilate=dilate)
+                if tuple(density.shape) != tuple(volume_feature.shape[-3:]):
+                    raise RuntimeError(f"render_view: density {tuple(density.shape)} is not the (D,h,w) of the volume {tuple(volume_feature.shape)}")
+                src.update(density=density.to(imgs.device, torch.float32).contiguous(), thr=skip_empty)
             k_render = intrinsic if intrinsic.dim() == 2 else intrinsic.mean(0)
             k_ndc = k_render if k_ref is None else k_ref
             nf_t, nf_r = nf_tgt.reshape(-1)[:2].contiguous(), near_fars[0].reshape(-1)[:2].contiguous()
@@ -383,8 +407,7 @@ class MVSSystem(_ModuleShim):
                 pts, dirs, ndc, z, _ = ops.raygen(H, W, k_render, tgt_to_world, k_ndc, world_to_ref, nf_t, nf_r, args.N_samples, pad=args.pad,
                                                   first_pixel=first, n_rays=min(B, H * W - first), ref_hw=ref_hw)
                 return pts, ndc, z, dirs
-            rgb, depth = _render_sparse_batches(self, H * W, B, make_batch,
-                                                dict(src, vol_cl=ops.channels_last_volume(volume_feature), density=density, thr=skip_empty))
+            rgb, depth = _render_sparse_batches(self, H * W, B, make_batch, dict(src, vol_cl=ops.channels_last_volume(volume_feature)), early_stop=stop)
             return rgb.reshape(H, W, 3), depth.reshape(H, W)
         fused = (isinstance(net, MVSNeRF) and getattr(kw.get("network_query_fn"), "_mvsnerf_fused", False)
                  and not getattr(args, "use_color_volume", False) and args.feat_dim == 8 + 4 * V and not whole_frame_off
@@ -852,7 +875,7 @@ class MVSSystemFinetune(_ModuleShim):
 
     # -- rendering the fine-tuned scene (train_mvs_nerf_finetuning_pl.py:192-252) ---------------------
     @torch.no_grad()
-    def render_rays(self, rays, chunk=None, batch_rays=16384, u=None, whole_frame_off=False, skip_empty=None):
+    def render_rays(self, rays, chunk=None, batch_rays=16384, u=None, whole_frame_off=False, skip_empty=None, early_stop=None, stop_every=32):
         """The rendering part of the fine-tuning script's validation_step (:204-237) for the dataset's rays (N,8) = [o | d | near | far]: per
         chunk ray_marcher -> get_ndc_coordinate -> [ray_marcher_fine, when a density volume exists and args.N_importance > 0] -> rendering, from
         the learnt `self.volume` (8 channels + the source images, or the (8 + 4V)-channel colour volume of --use_color_volume).  Returns
@@ -865,8 +888,13 @@ class MVSSystemFinetune(_ModuleShim):
         `self.density_volume` (update_density_volume()) holds no value above it are not sent through the MLP - their raw is (0,0,0,0), the
         others have the bits of the dense sequence (ops.raymarch_sparse).  The frame then runs per sub-batch of batch_rays rays (ray_marcher ->
         ops.ray_points -> [ray_marcher_fine] -> ops.raymarch_sparse: _render_sparse_batches), the sub-batches sharded over the ranks, one host read of the live count per
-        sub-batch; `self.last_live_fraction` is this rank's live samples over its samples."""
-        if skip_empty is not None:          # refusals first: nothing below needs the library before them
+        sub-batch; `self.last_live_fraction` is this rank's live samples over its samples.
+        early_stop / stop_every: as MVSSystem.render_view (DESIGN.md 4h) - alone it needs no density volume, with skip_empty it uses that one;
+        with N_importance > 0 the merged depths are simply a larger S.  `self.last_stopped_fraction` is this rank's stopped rays over its rays."""
+        stop = _early_stop(early_stop, stop_every, "render_rays")          # refusals first: nothing below needs the library before them
+        if stop is not None and whole_frame_off:
+            raise ValueError("render_rays: early_stop runs its own per-sub-batch loop; it cannot be combined with whole_frame_off=True")
+        if skip_empty is not None:
             if whole_frame_off:
                 raise ValueError("render_rays: skip_empty runs its own per-sub-batch loop; it cannot be combined with whole_frame_off=True")
             skip_empty = _threshold(skip_empty, "render_rays(skip_empty=)")
@@ -910,15 +938,16 @@ class MVSSystemFinetune(_ModuleShim):
                 return rgb, depth
             return D.render_frame(render_chunk, 1, N, chunk)
 
-        if skip_empty is not None:
+        if skip_empty is not None or stop is not None:
             src = _sparse_sources(self, vol, self.pose_source, V, self.imgs[0], who)
+            if skip_empty is not None:
+                src.update(density=self.density_volume, thr=skip_empty)
             B = max(int(batch_rays), 1)
 
             def make_batch(idx):
                 pts, ndc, z, _, rays_d = march(idx, B)
                 return pts, ndc, z.contiguous(), rays_d.contiguous()
-            return _render_sparse_batches(self, N, B, make_batch,
-                                          dict(src, vol_cl=ops.channels_last_volume(vol), density=self.density_volume, thr=skip_empty))
+            return _render_sparse_batches(self, N, B, make_batch, dict(src, vol_cl=ops.channels_last_volume(vol)), early_stop=stop)
         net, color_vol = _sparse_config(self, vol, V, who)
         vol_cl = ops.channels_last_volume(vol)
         t = torch.linspace(0, 1, args.N_samples, device=dev)
@@ -1211,16 +1240,19 @@ class MVSSystemFusion(_ModuleShim):
         return ops.node_density(dilate=dilate, **_density_sources(self.network_fn, F, self.volume.feat_volume.detach(), self.pose_source_ref, (F - 8) // 4))
 
     @torch.no_grad()
-    def render_rays(self, rays, chunk=None, batch_rays=65536, skip_empty=None):
+    def render_rays(self, rays, chunk=None, batch_rays=65536, skip_empty=None, early_stop=None, stop_every=32):
         """The rendering part of validation_step (:307-324) for rays (N,8): per chunk ops.ray_march_bbox -> rendering, the chunks of up to batch_rays
         rays issued as one renderer.rendering_batched call; chunk ranges are sharded over the ranks as in MVSSystemFinetune.render_rays.
         Returns (rgb (N,3), depth (N,)).
         skip_empty: None (default) is the dense render above, untouched.  A float is a density threshold: per sub-batch of batch_rays
         rays ops.ray_march_bbox -> ops.raymarch_sparse (_render_sparse_batches) against `self.density_volume` - the fused density of the splat, or the renderer-consistent one
         after update_density_volume(); the sub-batches are sharded over the ranks and `self.last_live_fraction` is this rank's live samples over its
-        samples."""
+        samples.
+        early_stop / stop_every: as MVSSystem.render_view; alone it reads no density volume.  `self.last_stopped_fraction` is this
+        rank's stopped rays over its rays."""
         from .renderer import rendering_batched
-        if skip_empty is not None:          # refusals first: nothing below needs the library before them
+        stop = _early_stop(early_stop, stop_every, "render_rays")          # refusals first: nothing below needs the library before them
+        if skip_empty is not None:
             skip_empty = _threshold(skip_empty, "render_rays(skip_empty=)")
         self._need_volume()
         args = self.args
@@ -1230,10 +1262,11 @@ class MVSSystemFusion(_ModuleShim):
         N = rays.shape[0]
         if N == 0:
             return torch.empty((0, 3), device=dev), torch.empty((0,), device=dev)
-        if skip_empty is not None:
+        if skip_empty is not None or stop is not None:
             vol = self.volume.feat_volume
-            src = _sparse_sources(self, vol, self.pose_source_ref, (args.feat_dim - 8) // 4, None, "render_rays(skip_empty=)")
-            density = self.density_volume.reshape(vol.shape[-3:]).to(dev, torch.float32).contiguous()      # (1,1,D,H,W) as finish() leaves it
+            src = _sparse_sources(self, vol, self.pose_source_ref, (args.feat_dim - 8) // 4, None, "render_rays(skip_empty= / early_stop=)")
+            if skip_empty is not None:                   # (1,1,D,H,W) as finish() leaves it
+                src.update(density=self.density_volume.reshape(vol.shape[-3:]).to(dev, torch.float32).contiguous(), thr=skip_empty)
             lindisp = getattr(args, "use_disp", False)
             B = max(int(batch_rays), 1)
             t = torch.linspace(0, 1, args.N_samples, device=dev)
@@ -1242,7 +1275,7 @@ class MVSSystemFusion(_ModuleShim):
                 r = rays[idx * B:(idx + 1) * B]
                 pts, ndc, z = ops.ray_march_bbox(r, self.bbox_3d, args.N_samples, lindisp=lindisp, t=t)
                 return pts, ndc, z, r[:, 3:6].contiguous()
-            return _render_sparse_batches(self, N, B, make_batch, dict(src, vol_cl=ops.channels_last_volume(vol), density=density, thr=skip_empty))
+            return _render_sparse_batches(self, N, B, make_batch, dict(src, vol_cl=ops.channels_last_volume(vol)), early_stop=stop)
         n_chunks = (N + chunk - 1) // chunk
         world, rank = D.world_rank()
         lo, hi = D.shard_range(n_chunks, world, rank)
