@@ -453,6 +453,32 @@ int mvsnerf_scatter_rows_fwd(const float* src, const int* idx, const int* count,
 int mvsnerf_voxel_points_fwd(int D, int H, int W, int d0, int d1, const float* K_ref, const float* c2w_ref, const float* near_far,
                              int W_img, int H_img, int pad, int lindisp, float* ndc, float* pts, void* stream);
 int mvsnerf_max_dilate3d_fwd(const float* in, int D, int H, int W, int r, float* out, float* workspace, void* stream);
+/* ---- counted launches: the gather and MLP stage of the compacted marches on a row count that stays on the device ----
+ * The rows form of their namesakes (S = 1: every row is its own ray and has its own direction row; dense rows - ndc / pts / dirs / rays_dir / dirs_out
+ * [cap][3], feat [cap][F or feat_stride], raw [cap][4 or 1]) with (cap, count) in place of (N, S): cap is the capacity of the buffers in rows, a host
+ * integer; count the int32 word mvsnerf_live_samples_fwd / _range_fwd leave on the device.  A launch works on rows [0, n), n = min(max(count[0], 0), cap),
+ * read by every workgroup with one scalar load before any other global load; it produces the bits of its namesake at N = n, S = 1 on those rows and
+ * touches no row >= n of its outputs.  Nothing is read on the host, so a sequence of these can be enqueued ahead or captured into a graph.  The grid
+ * is sized by cap: the fp32 128-wide kernel walks the ceil(n / 128) tiles with min(ceil(cap / 128), 512) workgroups (the form of the predicated kernel
+ * behind a guard); every other kernel launches a workgroup per tile of cap, and one whose tile starts at or behind row n returns at once.
+ * mlp_fwd_split_counted takes n_split = MVSNERF_SPLIT_FP16 only and mlp_fwd_guarded_counted is the guarded sequence (counted fp16x3 -> counted fp32
+ * predicated on the guard -> consume; all enqueued whatever the count); the bf16 kernels have no counted form.
+ * MVSNERF_EINVAL: NULL count or a NULL buffer its namesake refuses, cap < 0, the namesake's other refusals; MVSNERF_EALIGN: count off 4 bytes, the buffers
+ * the namesake wants on 16 bytes; MVSNERF_EUNSUPPORTED: cap >= 2^31, an F / width / C / n_split outside the kernel's; cap == 0 enqueues nothing. */
+int mvsnerf_mlp_fwd_counted(const float* packed, int F, const float* ndc, const float* feat, const float* dirs, int64_t cap, const int* count,
+                            int alpha_only, float* raw, void* stream);
+int mvsnerf_mlp_fwd_guarded_counted(const void* packed_fp16, const float* packed_f32, int F, const float* ndc, const float* feat, const float* dirs,
+                                    int64_t cap, const int* count, int alpha_only, float* raw, int* guard, void* stream);
+int mvsnerf_mlp_fwd_split_counted(const void* packed_split, const float* packed_f32, int F, int n_split, const float* ndc, const float* feat,
+                                  const float* dirs, int64_t cap, const int* count, int alpha_only, float* raw, void* stream);
+int mvsnerf_mlp_fwd_wide_counted(const float* packed, int F, int width, const float* ndc, const float* feat, const float* dirs, int64_t cap,
+                                 const int* count, int alpha_only, float* raw, void* stream);
+int mvsnerf_gather_fwd_counted(const float* vol, int D, int H, int W, const float* imgs_nhwc4, int V, int IH, int IW, const float* w2c, const float* K,
+                               const float* pts, const float* ndc, int64_t cap, const int* count, const float* rays_dir, float* feat, int feat_stride,
+                               float* dirs_out, int vol_layout, void* stream);
+int mvsnerf_gather_colorvol_fwd_counted(const float* vol, int D, int H, int W, int C, const float* ndc, int64_t cap, const int* count,
+                                        const float* rays_dir, const float* w2c_ref, float* feat, int feat_stride, float* dirs_out, int vol_layout,
+                                        int force_offsets64, void* stream);
 
 #ifdef __cplusplus
 }

@@ -278,6 +278,12 @@ SIGNATURES = {
     "mvsnerf_scatter_rows_fwd": (_c_i, [_c_fp, _c_fp, _c_fp, _c_l, _c_l, _c_i, _c_fp, _c_fp]),
     "mvsnerf_voxel_points_fwd": (_c_i, [_c_i] * 5 + [_c_fp] * 3 + [_c_i] * 4 + [_c_fp] * 3),
     "mvsnerf_max_dilate3d_fwd": (_c_i, [_c_fp] + [_c_i] * 4 + [_c_fp] * 3),
+    "mvsnerf_mlp_fwd_counted": (_c_i, [_c_fp, _c_i, _c_fp, _c_fp, _c_fp, _c_l, _c_fp, _c_i, _c_fp, _c_fp]),
+    "mvsnerf_mlp_fwd_guarded_counted": (_c_i, [_c_fp, _c_fp, _c_i, _c_fp, _c_fp, _c_fp, _c_l, _c_fp, _c_i, _c_fp, _c_fp, _c_fp]),
+    "mvsnerf_mlp_fwd_split_counted": (_c_i, [_c_fp, _c_fp, _c_i, _c_i, _c_fp, _c_fp, _c_fp, _c_l, _c_fp, _c_i, _c_fp, _c_fp]),
+    "mvsnerf_mlp_fwd_wide_counted": (_c_i, [_c_fp, _c_i, _c_i, _c_fp, _c_fp, _c_fp, _c_l, _c_fp, _c_i, _c_fp, _c_fp]),
+    "mvsnerf_gather_fwd_counted": (_c_i, [_c_fp] + [_c_i] * 3 + [_c_fp] + [_c_i] * 3 + [_c_fp] * 4 + [_c_l, _c_fp, _c_fp, _c_fp, _c_i, _c_fp, _c_i, _c_fp]),
+    "mvsnerf_gather_colorvol_fwd_counted": (_c_i, [_c_fp] + [_c_i] * 4 + [_c_fp, _c_l, _c_fp, _c_fp, _c_fp, _c_fp, _c_i, _c_fp, _c_i, _c_i, _c_fp]),
 }
 
 _lib = None

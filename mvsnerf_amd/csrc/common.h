@@ -28,6 +28,23 @@ static inline int mvs_raise_lds_cap(const void* fn, int bytes, unsigned long lon
     return 0;
 }
 
+// Counted launches: the number of rows a kernel works on, from the int32 word ops.live_samples leaves on the device -
+// n = min(max(*count, 0), cap).  The address is a kernel argument, so the load is a scalar one and n lives in an SGPR (readfirstlane says so
+// to the compiler); a workgroup reads it before any other global load and leaves when n gives it no row.
+__device__ __forceinline__ int mvs_counted_rows(const int* __restrict__ count, int cap)
+{
+    const int n = __builtin_amdgcn_readfirstlane(*count);
+    return n < 0 ? 0 : n > cap ? cap : n;
+}
+// The argument codes every counted entry shares: a NULL or misaligned count, a capacity outside [0, 2^31)
+static inline int mvs_counted_args(const int* count, int64_t cap)
+{
+    if (!count || cap < 0) return MVSNERF_EINVAL;
+    if (reinterpret_cast<uintptr_t>(count) & 3u) return MVSNERF_EALIGN;
+    if (cap >= ((int64_t)1 << 31)) return MVSNERF_EUNSUPPORTED;
+    return MVSNERF_OK;
+}
+
 // smallest multiple of 4 that is >= n and whose quarter is odd: an LDS row stride (in floats) that walks all 16 bank groups of 16 bytes
 __host__ __device__ inline int mvs_odd_quad_stride(int n) { const int q = (n + 3) >> 2; return (q | 1) << 2; }
 

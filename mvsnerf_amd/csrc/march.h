@@ -27,6 +27,12 @@ int mvs_mlp_fwd_if(const float* packed, int F, const float* ndc, int ndc_stride,
 // mlp_f16x3.hip: the two-piece fp16 MLP on P = N * S points; reports a non-finite weight or value through guard[0] when guard != NULL
 int mvs_mlp_f16x3_fwd(const void* packed_h, const float* packed_f32, int F, const float* ndc, int ndc_stride, const float* feat, int feat_stride,
                       const float* dirs, int dirs_stride, int64_t P, int S, int alpha_only, float* raw, hipStream_t st, int* guard = nullptr);
+// The counted forms of the two: rows [0, min(max(*count, 0), cap)) of dense (cap, 3 | F | 3) row buffers, S = 1, the count read on
+// the device.  mvs_mlp_fwd_counted checks its arguments (run_if may be NULL); mvs_mlp_f16x3_fwd_counted's callers do, and pass cap >= 1.
+int mvs_mlp_fwd_counted(const float* packed, int F, const float* ndc, const float* feat, const float* dirs, int64_t cap, const int* count,
+                        int alpha_only, float* raw, const int* run_if, void* stream);
+int mvs_mlp_f16x3_fwd_counted(const void* packed_h, const float* packed_f32, int F, const float* ndc, const float* feat, const float* dirs,
+                              int cap, const int* count, int alpha_only, float* raw, hipStream_t st, int* guard = nullptr);
 // encoder.hip: ends a guarded sequence whose last kernel does not: counts a tripped guard, re-arms it
 int mvs_guard_consume(int* guard, hipStream_t st);
 // mlp.hip: the one-launch fp32 ray march (raymarch_fused_kernel) and whether it applies to a batch: fp32 MLP, no guard, channel-last images,

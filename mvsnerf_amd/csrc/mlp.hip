@@ -637,6 +637,56 @@ __global__ __launch_bounds__(256, 2) void mlp_fwd_pipe_if_kernel(
     }
 }
 
+// Counted launch: the rows form (S = 1: every compact row of ops.live_samples has its own direction row, dense 3 / F / 3 strides)
+// on the first n = min(max(*count, 0), cap) rows, n read on the device.  The same tile walk: the grid is sized by the capacity, a workgroup
+// walks the ceil(n / 128) tiles the count leaves and one without a tile returns before any other global load (n = 0: all of them).  Each tile is
+// mlp_fwd_pipe_tile with P = n - the plain kernel's bits at N = n, and no row >= n is written.  run_if (may be NULL): the guard word of a
+// counted guarded sequence, as in mlp_fwd_pipe_if_kernel.
+template <bool ALPHA_ONLY>
+__global__ __launch_bounds__(256, 2) void mlp_fwd_pipe_counted_kernel(
+    const float* __restrict__ packed, int F, const float* __restrict__ ndc, const float* __restrict__ feat, const float* __restrict__ dirs,
+    int cap, const int* __restrict__ count, float* __restrict__ raw, const int* __restrict__ run_if)
+{
+    if (run_if && *run_if == 0) return;
+    const int n = mvs_counted_rows(count, cap);
+    const unsigned n_tiles = ((unsigned)n + 127u) / 128u;
+    for (unsigned tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        mlp_fwd_pipe_tile<ALPHA_ONLY, false>(tile, packed, F, ndc, 3, feat, F, dirs, 3, n, 1, raw, nullptr, nullptr);
+        __syncthreads();                                       // as above: the next tile's first slabs overwrite what this one's last GEMMs read
+    }
+}
+
+template <bool AO>
+static int launch_mlp_pipe_counted(const float* packed, int F, const float* ndc, const float* feat, const float* dirs, int cap, const int* count,
+                                   float* raw, const int* run_if, hipStream_t st)
+{
+    const size_t lds_bytes = PIPE_LDS_FLOATS * sizeof(float);
+    static unsigned long long cap_set = 0;
+    if (int rc_ = mvs_raise_lds_cap(reinterpret_cast<const void*>(mlp_fwd_pipe_counted_kernel<AO>), (int)lds_bytes, &cap_set)) return rc_;
+    const unsigned n_tiles = mvs_cdiv(cap, 128);
+    mlp_fwd_pipe_counted_kernel<AO><<<n_tiles < 512u ? n_tiles : 512u, 256, lds_bytes, st>>>(packed, F, ndc, feat, dirs, cap, count, raw, run_if);
+    MVS_LAUNCH_CHECK();
+    return MVSNERF_OK;
+}
+
+int mvs_mlp_fwd_counted(const float* packed, int F, const float* ndc, const float* feat, const float* dirs, int64_t cap, const int* count,
+                        int alpha_only, float* raw, const int* run_if, void* stream)
+{
+    if (!packed || !ndc || !feat || !raw || (!alpha_only && !dirs)) return MVSNERF_EINVAL;
+    if (int rc = mvs_counted_args(count, cap)) return rc;
+    if (F < 2 || F > MAX_F || (F & 1)) return MVSNERF_EUNSUPPORTED;
+    if (!mvs_aligned16(packed) || !mvs_aligned16(raw)) return MVSNERF_EALIGN;
+    if (cap == 0) return MVSNERF_OK;
+    if (alpha_only) return launch_mlp_pipe_counted<true>(packed, F, ndc, feat, dirs, (int)cap, count, raw, run_if, (hipStream_t)stream);
+    return launch_mlp_pipe_counted<false>(packed, F, ndc, feat, dirs, (int)cap, count, raw, run_if, (hipStream_t)stream);
+}
+
+extern "C" int mvsnerf_mlp_fwd_counted(const float* packed, int F, const float* ndc, const float* feat, const float* dirs, int64_t cap,
+                                       const int* count, int alpha_only, float* raw, void* stream)
+{
+    return mvs_mlp_fwd_counted(packed, F, ndc, feat, dirs, cap, count, alpha_only, raw, nullptr, stream);
+}
+
 template <bool AO, bool SAVE>
 static int launch_mlp_pipe(const float* packed, int F, const float* ndc, int ndc_stride, const float* feat, int feat_stride,
                            const float* dirs, int dirs_stride, int64_t P, int S, float* raw, hipStream_t st, float* saved = nullptr, long long* census = nullptr,

@@ -1099,3 +1099,15 @@ extern "C" int mvsnerf_mlp_fwd_split(const void* packed_split, const float* pack
     MVS_LAUNCH_CHECK();
     return MVSNERF_OK;
 }
+
+// The split kernel on a device-side row count: the fp16 split only - the bf16 splits have no counted form.
+extern "C" int mvsnerf_mlp_fwd_split_counted(const void* packed_split, const float* packed_f32, int F, int n_split, const float* ndc,
+                                             const float* feat, const float* dirs, int64_t cap, const int* count, int alpha_only, float* raw, void* stream)
+{
+    if (!packed_split || !packed_f32 || !ndc || !feat || !raw || (!alpha_only && !dirs)) return MVSNERF_EINVAL;
+    if (int rc = mvs_counted_args(count, cap)) return rc;
+    if (F < 2 || F > MAX_F || (F & 1) || n_split != MVSNERF_SPLIT_FP16) return MVSNERF_EUNSUPPORTED;
+    if (!mvs_aligned16(packed_split) || !mvs_aligned16(raw)) return MVSNERF_EALIGN;
+    if (cap == 0) return MVSNERF_OK;
+    return mvs_mlp_f16x3_fwd_counted(packed_split, packed_f32, F, ndc, feat, dirs, (int)cap, count, alpha_only, raw, (hipStream_t)stream);
+}

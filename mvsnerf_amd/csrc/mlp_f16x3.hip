@@ -287,9 +287,10 @@ constexpr int WIN_TARGET = 5;                            // ... outside, it is s
 constexpr int SC_LIM = 120;                              // |log2| of the cumulative scale (the multiplicative modulation of six layers takes features of 3e5 to 1e36)
 __device__ __forceinline__ float pow2f(int e) { return __builtin_amdgcn_ldexpf(1.0f, min(max(e, -126), 126)); }
 
+// One tile = 256 points = one workgroup's work; `tile` is the workgroup index in both kernels below.
 template <bool ALPHA_ONLY>
-__global__ __launch_bounds__(H3_THREADS) void mlp_fwd_f16x3_kernel(
-    const _Float16* __restrict__ wq, const float* __restrict__ packed_f32, int F, const float* __restrict__ ndc, int ndc_stride,
+__device__ __forceinline__ void mlp_fwd_f16x3_tile(
+    const unsigned tile, const _Float16* __restrict__ wq, const float* __restrict__ packed_f32, int F, const float* __restrict__ ndc, int ndc_stride,
     const float* __restrict__ feat, int feat_stride, const float* __restrict__ dirs, int dirs_stride,
     int64_t P, int S, float* __restrict__ raw, int* __restrict__ guard)
 {
@@ -302,14 +303,14 @@ __global__ __launch_bounds__(H3_THREADS) void mlp_fwd_f16x3_kernel(
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int half = lane >> 5;
-    const int64_t p_raw = ((int64_t)blockIdx.x * H3_WAVES + wave) * 32 + (lane & 31);
+    const int64_t p_raw = ((int64_t)tile * H3_WAVES + wave) * 32 + (lane & 31);
     const bool live = p_raw < P;
     const int64_t p = live ? p_raw : P - 1;
     constexpr size_t ACT_PLANE = (size_t)B_ACT_STEPS * 4 * 512, PE_PLANE = (size_t)B_PE_STEPS * 4 * 512;     // fp16 elements of one plane
     constexpr size_t VIEW_PLANE = (size_t)B_VIEW_STEPS * 2 * 512;
     const size_t feat_plane = b_seg(L.fsteps, 4);
 #ifdef H3_CENSUS      // DEV probe: shader-clock stamps of this wave's phases, 32 per tile, behind the results (scratch/r6/h3_census.py allocates them)
-    unsigned* cen = reinterpret_cast<unsigned*>(raw + P * (ALPHA_ONLY ? 1 : 4)) + ((int64_t)blockIdx.x * H3_WAVES + wave) * 32;
+    unsigned* cen = reinterpret_cast<unsigned*>(raw + P * (ALPHA_ONLY ? 1 : 4)) + ((int64_t)tile * H3_WAVES + wave) * 32;
     int cen_i = 0;
 #define H3_STAMP() do { const unsigned long long t__ = __builtin_amdgcn_s_memtime(); if (lane == 0 && cen_i < 32) cen[cen_i] = (unsigned)t__; ++cen_i; } while (0)
 #else
@@ -336,7 +337,7 @@ __global__ __launch_bounds__(H3_THREADS) void mlp_fwd_f16x3_kernel(
     }
     float fv[24];                                 // F/2 <= 20 feature operands of this lane half
     // (buf1 is idle until layer 1's slab is asked for behind the first barrier: 4 KB of it per wave stage the features - mlp_b16_dev.h)
-    if (!stage_features(fv, feat, feat_stride, F, ((int64_t)blockIdx.x * H3_WAVES + wave) * 32, P, buf1 + wave * 4096, lane)) {
+    if (!stage_features(fv, feat, feat_stride, F, ((int64_t)tile * H3_WAVES + wave) * 32, P, buf1 + wave * 4096, lane)) {
         const float* fp = feat + p * feat_stride + half * (F / 2);
         // (the compiler turns this into one scalar branch + one load per element; issuing all 24 unconditionally - padding slots re-reading element 0 - measured
         // SLOWER, 34.4 -> 41.9 us in the bf16 kernel: a 64-lane dword load at an 80-byte stride is ~20 cache lines per instruction, the address unit is what waits)
@@ -380,7 +381,7 @@ __global__ __launch_bounds__(H3_THREADS) void mlp_fwd_f16x3_kernel(
     auto report = [&]() {
         if (guard) {
             if (bad) guard[0] = 1;
-            if (blockIdx.x == 0 && tid == 0 && (float)wq[L.total] != 0.0f) guard[0] = 1;      // a weight was clamped at pack time
+            if (tile == 0 && tid == 0 && (float)wq[L.total] != 0.0f) guard[0] = 1;      // a weight was clamped at pack time
         }
     };
     // accumulators start as the layer's bias vector (fragment order, LDS) times the point's scale
@@ -563,7 +564,7 @@ __global__ __launch_bounds__(H3_THREADS) void mlp_fwd_f16x3_kernel(
     auto point_again = [&]() {
         int t2 = threadIdx.x;
         asm volatile("" : "+v"(t2));
-        return ((int64_t)blockIdx.x * H3_WAVES + (t2 >> 6)) * 32 + (t2 & 31);
+        return ((int64_t)tile * H3_WAVES + (t2 >> 6)) * 32 + (t2 & 31);
     };
     if (ALPHA_ONLY) {
         const int64_t q_raw = point_again();
@@ -624,6 +625,37 @@ __global__ __launch_bounds__(H3_THREADS) void mlp_fwd_f16x3_kernel(
     }
 }
 
+template <bool ALPHA_ONLY>
+__global__ __launch_bounds__(H3_THREADS) void mlp_fwd_f16x3_kernel(
+    const _Float16* __restrict__ wq, const float* __restrict__ packed_f32, int F, const float* __restrict__ ndc, int ndc_stride,
+    const float* __restrict__ feat, int feat_stride, const float* __restrict__ dirs, int dirs_stride,
+    int64_t P, int S, float* __restrict__ raw, int* __restrict__ guard)
+{
+    mlp_fwd_f16x3_tile<ALPHA_ONLY>(blockIdx.x, wq, packed_f32, F, ndc, ndc_stride, feat, feat_stride, dirs, dirs_stride, P, S, raw, guard);
+}
+
+// Counted launch: the rows form (S = 1, dense strides) on the first n = min(max(*count, 0), cap) rows, n read on the device.
+// A grid for the capacity; a workgroup whose tile starts at or behind row n returns before any other global load, the others run the tile with
+// P = n: the plain kernel's bits at N = n, no row >= n written.  (Chosen by measurement against a tile walk; the walk is the DEV
+// probe -DMVS_COUNTED_WALK, never defined in the product build.)
+template <bool ALPHA_ONLY>
+__global__ __launch_bounds__(H3_THREADS) void mlp_fwd_f16x3_counted_kernel(
+    const _Float16* __restrict__ wq, const float* __restrict__ packed_f32, int F, const float* __restrict__ ndc,
+    const float* __restrict__ feat, const float* __restrict__ dirs, int cap, const int* __restrict__ count, float* __restrict__ raw, int* __restrict__ guard)
+{
+    const int n = mvs_counted_rows(count, cap);
+#if defined(MVS_COUNTED_WALK)
+    const unsigned n_tiles = ((unsigned)n + 32 * H3_WAVES - 1) / (32 * H3_WAVES);
+    for (unsigned tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        mlp_fwd_f16x3_tile<ALPHA_ONLY>(tile, wq, packed_f32, F, ndc, 3, feat, F, dirs, 3, n, 1, raw, guard);
+        slab_sync();
+    }
+#else
+    if (blockIdx.x * (unsigned)(32 * H3_WAVES) >= (unsigned)n) return;
+    mlp_fwd_f16x3_tile<ALPHA_ONLY>(blockIdx.x, wq, packed_f32, F, ndc, 3, feat, F, dirs, 3, n, 1, raw, guard);
+#endif
+}
+
 }  // namespace
 
 // internal entries behind mvsnerf_mlp_{packed_split_elems, pack_split, fwd_split}(n_split = MVSNERF_SPLIT_FP16) in mlp_bf16.hip
@@ -656,6 +688,24 @@ int mvs_mlp_f16x3_fwd(const void* packed_h, const float* packed_f32, int F, cons
         mlp_fwd_f16x3_kernel<true><<<grid, H3_THREADS, H3_LDS_BYTES, st>>>(wq, packed_f32, F, ndc, ndc_stride, feat, feat_stride, dirs, dirs_stride, P, S, raw, guard);
     else
         mlp_fwd_f16x3_kernel<false><<<grid, H3_THREADS, H3_LDS_BYTES, st>>>(wq, packed_f32, F, ndc, ndc_stride, feat, feat_stride, dirs, dirs_stride, P, S, raw, guard);
+    MVS_LAUNCH_CHECK();
+    return MVSNERF_OK;
+}
+
+// The counted form of mvs_mlp_f16x3_fwd (arguments checked by the callers): cap >= 1 rows of capacity, the row count read on the device
+int mvs_mlp_f16x3_fwd_counted(const void* packed_h, const float* packed_f32, int F, const float* ndc, const float* feat, const float* dirs,
+                              int cap, const int* count, int alpha_only, float* raw, hipStream_t st, int* guard)
+{
+    static unsigned long long cap_a = 0, cap_b = 0;         // per-device bit masks (common.h)
+    if (int rc_ = mvs_raise_lds_cap(reinterpret_cast<const void*>(mlp_fwd_f16x3_counted_kernel<false>), H3_LDS_BYTES, &cap_a)) return rc_;
+    if (int rc_ = mvs_raise_lds_cap(reinterpret_cast<const void*>(mlp_fwd_f16x3_counted_kernel<true>), H3_LDS_BYTES, &cap_b)) return rc_;
+    const _Float16* wq = reinterpret_cast<const _Float16*>(packed_h);
+    unsigned grid = mvs_cdiv(cap, 32 * H3_WAVES);
+#if defined(MVS_COUNTED_WALK)
+    if (grid > 256u) grid = 256u;
+#endif
+    if (alpha_only) mlp_fwd_f16x3_counted_kernel<true><<<grid, H3_THREADS, H3_LDS_BYTES, st>>>(wq, packed_f32, F, ndc, feat, dirs, cap, count, raw, guard);
+    else mlp_fwd_f16x3_counted_kernel<false><<<grid, H3_THREADS, H3_LDS_BYTES, st>>>(wq, packed_f32, F, ndc, feat, dirs, cap, count, raw, guard);
     MVS_LAUNCH_CHECK();
     return MVSNERF_OK;
 }

@@ -137,7 +137,7 @@ template <bool ALPHA_ONLY, bool ADD>
 __device__ __forceinline__ void mlp_fwd_wide_tile(
     const float* __restrict__ packed, int F, const float* __restrict__ ndc, int ndc_stride,
     const float* __restrict__ feat, int feat_stride, const float* __restrict__ dirs, int dirs_stride,
-    int64_t P, int S, float* __restrict__ raw, const int wave)
+    int64_t P, int S, float* __restrict__ raw, const int wave, const unsigned tile)
 {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* buf0 = lds;
@@ -148,7 +148,6 @@ __device__ __forceinline__ void mlp_fwd_wide_tile(
     constexpr bool add = ADD;
     using Next = SlabUnder<SL>;
     const Layout L = layout(F);
-    const unsigned tile = blockIdx.x;
     // The lane number, from the hardware anew (v_mbcnt; volatile, so no copy of it is kept): every phase below - start, a layer, the heads - asks
     // again and derives its LDS addresses, its lane half and its point's index from the answer.  What the thread index would otherwise keep alive
     // through all GEMMs (itself, the half, two LDS base addresses, a 64-bit point index) is five registers more than the 384 above leave.
@@ -327,8 +326,52 @@ __global__ __launch_bounds__(256, 1) void mlp_fwd_wide_kernel(
     int64_t P, int S, float* __restrict__ raw)
 {
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    if (packed[layout(F).vec + V_ADD] != 0.0f) mlp_fwd_wide_tile<ALPHA_ONLY, true>(packed, F, ndc, ndc_stride, feat, feat_stride, dirs, dirs_stride, P, S, raw, wave);
-    else mlp_fwd_wide_tile<ALPHA_ONLY, false>(packed, F, ndc, ndc_stride, feat, feat_stride, dirs, dirs_stride, P, S, raw, wave);
+    if (packed[layout(F).vec + V_ADD] != 0.0f) mlp_fwd_wide_tile<ALPHA_ONLY, true>(packed, F, ndc, ndc_stride, feat, feat_stride, dirs, dirs_stride, P, S, raw, wave, blockIdx.x);
+    else mlp_fwd_wide_tile<ALPHA_ONLY, false>(packed, F, ndc, ndc_stride, feat, feat_stride, dirs, dirs_stride, P, S, raw, wave, blockIdx.x);
+}
+
+// Counted launch: the rows form (S = 1, dense strides) on the first n = min(max(*count, 0), cap) rows, n read on the device.  A
+// grid for the capacity; a workgroup whose tile starts at or behind row n returns before any other global load, the others run the tile with
+// P = n: the plain kernel's bits at N = n, no row >= n written.  (The tile walk is the DEV probe -DMVS_COUNTED_WALK, never defined in the product
+// build: DESIGN.md 4i.)
+template <bool ALPHA_ONLY>
+__global__ __launch_bounds__(256, 1) void mlp_fwd_wide_counted_kernel(
+    const float* __restrict__ packed, int F, const float* __restrict__ ndc, const float* __restrict__ feat, const float* __restrict__ dirs,
+    int cap, const int* __restrict__ count, float* __restrict__ raw)
+{
+    const int n = mvs_counted_rows(count, cap);
+#if defined(MVS_COUNTED_WALK)
+    const unsigned n_tiles = ((unsigned)n + 127u) / 128u;
+    if (blockIdx.x >= n_tiles) return;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const bool add = packed[layout(F).vec + V_ADD] != 0.0f;
+    for (unsigned tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        if (add) mlp_fwd_wide_tile<ALPHA_ONLY, true>(packed, F, ndc, 3, feat, F, dirs, 3, n, 1, raw, wave, tile);
+        else mlp_fwd_wide_tile<ALPHA_ONLY, false>(packed, F, ndc, 3, feat, F, dirs, 3, n, 1, raw, wave, tile);
+        __syncthreads();
+    }
+#else
+    if (blockIdx.x * 128u >= (unsigned)n) return;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (packed[layout(F).vec + V_ADD] != 0.0f) mlp_fwd_wide_tile<ALPHA_ONLY, true>(packed, F, ndc, 3, feat, F, dirs, 3, n, 1, raw, wave, blockIdx.x);
+    else mlp_fwd_wide_tile<ALPHA_ONLY, false>(packed, F, ndc, 3, feat, F, dirs, 3, n, 1, raw, wave, blockIdx.x);
+#endif
+}
+
+template <bool AO>
+static int launch_mlp_wide_counted(const float* packed, int F, const float* ndc, const float* feat, const float* dirs, int cap, const int* count,
+                                   float* raw, hipStream_t st)
+{
+    const size_t lds_bytes = WIDE_LDS_FLOATS * sizeof(float);
+    static unsigned long long lds_cap_set = 0;          // per-device bit mask (common.h)
+    if (int rc_ = mvs_raise_lds_cap(reinterpret_cast<const void*>(mlp_fwd_wide_counted_kernel<AO>), (int)lds_bytes, &lds_cap_set)) return rc_;
+    unsigned grid = mvs_cdiv(cap, 128);
+#if defined(MVS_COUNTED_WALK)
+    if (grid > 256u) grid = 256u;
+#endif
+    mlp_fwd_wide_counted_kernel<AO><<<grid, 256, lds_bytes, st>>>(packed, F, ndc, feat, dirs, cap, count, raw);
+    MVS_LAUNCH_CHECK();
+    return MVSNERF_OK;
 }
 
 template <bool AO>
@@ -356,4 +399,17 @@ extern "C" int mvsnerf_mlp_fwd_wide(const float* packed, int F, int width, const
     hipStream_t st = (hipStream_t)stream;
     if (alpha_only) return launch_mlp_wide<true>(packed, F, ndc, ndc_stride, feat, feat_stride, dirs, dirs_stride, P, S, raw, st);
     return launch_mlp_wide<false>(packed, F, ndc, ndc_stride, feat, feat_stride, dirs, dirs_stride, P, S, raw, st);
+}
+
+extern "C" int mvsnerf_mlp_fwd_wide_counted(const float* packed, int F, int width, const float* ndc, const float* feat, const float* dirs,
+                                            int64_t cap, const int* count, int alpha_only, float* raw, void* stream)
+{
+    if (!packed || !ndc || !feat || !raw || (!alpha_only && !dirs)) return MVSNERF_EINVAL;
+    if (int rc = mvs_counted_args(count, cap)) return rc;
+    if (!wide_shape_ok(F, width)) return MVSNERF_EUNSUPPORTED;
+    if (!mvs_aligned16(packed) || !mvs_aligned16(raw)) return MVSNERF_EALIGN;
+    if (cap == 0) return MVSNERF_OK;
+    hipStream_t st = (hipStream_t)stream;
+    if (alpha_only) return launch_mlp_wide_counted<true>(packed, F, ndc, feat, dirs, (int)cap, count, raw, st);
+    return launch_mlp_wide_counted<false>(packed, F, ndc, feat, dirs, (int)cap, count, raw, st);
 }

@@ -28,6 +28,21 @@ extern "C" int mvsnerf_mlp_fwd_guarded(const void* packed_fp16, const float* pac
     return mvs_guard_consume(guard, (hipStream_t)stream);
 }
 
+// The guarded sequence on a device-side row count: counted fp16x3 kernel -> counted fp32 kernel predicated on the guard -> consume.
+// All three are enqueued whatever the count is; at a count of 0 the guard is neither tripped nor counted.
+extern "C" int mvsnerf_mlp_fwd_guarded_counted(const void* packed_fp16, const float* packed_f32, int F, const float* ndc, const float* feat,
+                                               const float* dirs, int64_t cap, const int* count, int alpha_only, float* raw, int* guard, void* stream)
+{
+    if (!packed_fp16 || !packed_f32 || !ndc || !feat || !raw || !guard || (!alpha_only && !dirs)) return MVSNERF_EINVAL;
+    if (int rc = mvs_counted_args(count, cap)) return rc;
+    if (F < 2 || F > 40 || (F & 1)) return MVSNERF_EUNSUPPORTED;
+    if (!mvs_aligned16(packed_fp16) || !mvs_aligned16(packed_f32) || !mvs_aligned16(raw)) return MVSNERF_EALIGN;
+    if (cap == 0) return MVSNERF_OK;
+    if (int rc = mvs_mlp_f16x3_fwd_counted(packed_fp16, packed_f32, F, ndc, feat, dirs, (int)cap, count, alpha_only, raw, (hipStream_t)stream, guard)) return rc;
+    if (int rc = mvs_mlp_fwd_counted(packed_f32, F, ndc, feat, dirs, cap, count, alpha_only, raw, guard, stream)) return rc;
+    return mvs_guard_consume(guard, (hipStream_t)stream);
+}
+
 // A guard needs the fp16 split planes (the guarded sequence); checked before anything of the batch is launched.
 static bool mlp_choice_ok(const MarchBatch& b) { return !b.guard || (b.packed_split && b.n_split == MVSNERF_SPLIT_FP16); }
 

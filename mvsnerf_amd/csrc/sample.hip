@@ -271,7 +271,7 @@ struct GatherArgs {
 };
 
 template <bool SMALL, bool ZFAST>      // ZFAST: the volume is depth-fastest (MVSNERF_VOL_HWDC): lane = (row y, channel half), see sample_dev.h
-__global__ __launch_bounds__(256) void gather_fused_kernel(GatherArgs a)
+__device__ __forceinline__ void gather_fused_block(const GatherArgs& a)
 {
 #pragma clang fp contract(off)
     const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -334,6 +334,25 @@ __global__ __launch_bounds__(256) void gather_fused_kernel(GatherArgs a)
     if (q == 3 && a.dirs_out && p_raw < a.N) dir_feature_of(a.rays_dir + p_raw * 3, a.w2c, 1, a.dirs_out + p_raw * 3);   // reference view = view 0
 }
 
+template <bool SMALL, bool ZFAST>
+__global__ __launch_bounds__(256) void gather_fused_kernel(GatherArgs a)
+{
+    gather_fused_block<SMALL, ZFAST>(a);
+}
+
+// Counted launch: a.P = a.N = the capacity in rows (S = 1: every row is its own ray); the block works on the first
+// n = min(max(*count, 0), cap) of them - a grid for the capacity, a block of 64 rows that starts at or behind row n returns before any other
+// global load, the others run the block above with P = N = n (the plain kernel's bits at N = n, no row >= n of feat or dirs_out written).
+template <bool SMALL, bool ZFAST>
+__global__ __launch_bounds__(256) void gather_fused_counted_kernel(GatherArgs a, const int* __restrict__ count)
+{
+    const int n = mvs_counted_rows(count, (int)a.P);
+    if (blockIdx.x * 64u >= (unsigned)n) return;
+    a.P = n;
+    a.N = n;
+    gather_fused_block<SMALL, ZFAST>(a);
+}
+
 extern "C" int mvsnerf_gather_fwd(const float* vol, int D, int H, int W, const float* imgs_nhwc4, int V, int IH, int IW,
                                   const float* w2c, const float* K, const float* pts, const float* ndc, int64_t N, int S,
                                   const float* rays_dir, float* feat, int feat_stride, float* dirs_out, int vol_layout, void* stream)
@@ -356,6 +375,34 @@ extern "C" int mvsnerf_gather_fwd(const float* vol, int D, int H, int W, const f
     } else {
         if (small) gather_fused_kernel<true, false><<<grid, 256, 0, st>>>(a);
         else gather_fused_kernel<false, false><<<grid, 256, 0, st>>>(a);
+    }
+    MVS_LAUNCH_CHECK();
+    return MVSNERF_OK;
+}
+
+// mvsnerf_gather_fwd on the first min(max(*count, 0), cap) of cap rows (S = 1: pts / ndc / rays_dir / dirs_out are [cap][3], feat [cap][feat_stride]),
+// the count read on the device
+extern "C" int mvsnerf_gather_fwd_counted(const float* vol, int D, int H, int W, const float* imgs_nhwc4, int V, int IH, int IW,
+                                          const float* w2c, const float* K, const float* pts, const float* ndc, int64_t cap, const int* count,
+                                          const float* rays_dir, float* feat, int feat_stride, float* dirs_out, int vol_layout, void* stream)
+{
+    if (vol_layout != MVSNERF_VOL_DHWC && vol_layout != MVSNERF_VOL_HWDC) return MVSNERF_EINVAL;
+    if (!vol || !imgs_nhwc4 || !w2c || !K || !pts || !ndc || !feat || D < 1 || H < 1 || W < 1 || V < 1 || IH < 2 || IW < 2) return MVSNERF_EINVAL;
+    if (dirs_out && !rays_dir) return MVSNERF_EINVAL;
+    if (feat_stride < 8 + 4 * V) return MVSNERF_EINVAL;
+    if (int rc = mvs_counted_args(count, cap)) return rc;
+    if ((feat_stride & 3) || !mvs_aligned16(feat) || !mvs_aligned16(vol) || !mvs_aligned16(imgs_nhwc4)) return MVSNERF_EALIGN;
+    if (cap == 0) return MVSNERF_OK;
+    const GatherArgs a{vol, D, H, W, imgs_nhwc4, V, IH, IW, w2c, K, pts, ndc, cap, cap, rays_dir, feat, feat_stride, dirs_out};
+    const bool small = gather_fits_32bit(D, H, W, V, IH, IW, cap, feat_stride);
+    const unsigned grid = mvs_cdiv(cap, 64);
+    hipStream_t st = (hipStream_t)stream;
+    if (vol_layout == MVSNERF_VOL_HWDC) {
+        if (small) gather_fused_counted_kernel<true, true><<<grid, 256, 0, st>>>(a, count);
+        else gather_fused_counted_kernel<false, true><<<grid, 256, 0, st>>>(a, count);
+    } else {
+        if (small) gather_fused_counted_kernel<true, false><<<grid, 256, 0, st>>>(a, count);
+        else gather_fused_counted_kernel<false, false><<<grid, 256, 0, st>>>(a, count);
     }
     MVS_LAUNCH_CHECK();
     return MVSNERF_OK;
@@ -384,7 +431,7 @@ struct WideGatherArgs {
 };
 
 template <bool SMALL, bool ZFAST>      // SMALL: voxel, sample and feature-row offsets fit 32 bits (checked by the launcher); ZFAST: MVSNERF_VOL_HWDC
-__global__ __launch_bounds__(256) void volume_sample_wide_kernel(WideGatherArgs a)
+__device__ __forceinline__ void volume_sample_wide_block(const WideGatherArgs& a)
 {
 #pragma clang fp contract(off)
     const int Q = a.C >> 2;
@@ -427,6 +474,24 @@ __global__ __launch_bounds__(256) void volume_sample_wide_kernel(WideGatherArgs 
     if (cq == Q - 1 && p_raw < a.N) dir_feature_of(a.rays_dir + p_raw * 3, a.w2c, 1, a.dirs_out + p_raw * 3);
 }
 
+template <bool SMALL, bool ZFAST>
+__global__ __launch_bounds__(256) void volume_sample_wide_kernel(WideGatherArgs a)
+{
+    volume_sample_wide_block<SMALL, ZFAST>(a);
+}
+
+// Counted launch, as gather_fused_counted_kernel: a.P = the capacity in rows, a.N = the capacity or 0 (no dirs_out); a block of
+// a.spb rows that starts at or behind row n = min(max(*count, 0), cap) returns before any other global load
+template <bool SMALL, bool ZFAST>
+__global__ __launch_bounds__(256) void volume_sample_wide_counted_kernel(WideGatherArgs a, const int* __restrict__ count)
+{
+    const int n = mvs_counted_rows(count, (int)a.P);
+    if (blockIdx.x * (unsigned)a.spb >= (unsigned)n) return;
+    a.P = n;
+    a.N = a.N ? n : 0;
+    volume_sample_wide_block<SMALL, ZFAST>(a);
+}
+
 extern "C" int mvsnerf_gather_colorvol_fwd(const float* vol, int D, int H, int W, int C, const float* ndc, int64_t N, int S,
                                            const float* rays_dir, const float* w2c_ref, float* feat, int feat_stride, float* dirs_out,
                                            int vol_layout, int force_offsets64, void* stream)
@@ -450,6 +515,35 @@ extern "C" int mvsnerf_gather_colorvol_fwd(const float* vol, int D, int H, int W
     } else {
         if (small) volume_sample_wide_kernel<true, false><<<grid, 256, 0, st>>>(a);
         else volume_sample_wide_kernel<false, false><<<grid, 256, 0, st>>>(a);
+    }
+    MVS_LAUNCH_CHECK();
+    return MVSNERF_OK;
+}
+
+// mvsnerf_gather_colorvol_fwd on the first min(max(*count, 0), cap) of cap rows (S = 1: ndc / rays_dir / dirs_out are [cap][3], feat
+// [cap][feat_stride]), the count read on the device
+extern "C" int mvsnerf_gather_colorvol_fwd_counted(const float* vol, int D, int H, int W, int C, const float* ndc, int64_t cap, const int* count,
+                                                   const float* rays_dir, const float* w2c_ref, float* feat, int feat_stride, float* dirs_out,
+                                                   int vol_layout, int force_offsets64, void* stream)
+{
+    if (vol_layout != MVSNERF_VOL_DHWC && vol_layout != MVSNERF_VOL_HWDC) return MVSNERF_EINVAL;
+    if (!vol || !ndc || !feat || D < 1 || H < 1 || W < 1 || C < 1 || feat_stride < C) return MVSNERF_EINVAL;
+    if (dirs_out && !rays_dir) return MVSNERF_EINVAL;
+    if (int rc = mvs_counted_args(count, cap)) return rc;
+    if ((C & 3) || C <= 8 || C > 40) return MVSNERF_EUNSUPPORTED;
+    if ((feat_stride & 3) || !mvs_aligned16(feat) || !mvs_aligned16(vol)) return MVSNERF_EALIGN;
+    if (cap == 0) return MVSNERF_OK;
+    const int Q = C >> 2, spb = 256 / Q;
+    const WideGatherArgs a{vol, D, H, W, C, ndc, cap, dirs_out ? cap : 0, rays_dir, w2c_ref, feat, feat_stride, dirs_out, spb, (65536 + Q - 1) / Q};
+    const bool small = !force_offsets64 && (int64_t)D * H * W * C < ((int64_t)1 << 31) && cap * (int64_t)feat_stride < ((int64_t)1 << 31);
+    const unsigned grid = (unsigned)((cap + spb - 1) / spb);
+    hipStream_t st = (hipStream_t)stream;
+    if (vol_layout == MVSNERF_VOL_HWDC) {
+        if (small) volume_sample_wide_counted_kernel<true, true><<<grid, 256, 0, st>>>(a, count);
+        else volume_sample_wide_counted_kernel<false, true><<<grid, 256, 0, st>>>(a, count);
+    } else {
+        if (small) volume_sample_wide_counted_kernel<true, false><<<grid, 256, 0, st>>>(a, count);
+        else volume_sample_wide_counted_kernel<false, false><<<grid, 256, 0, st>>>(a, count);
     }
     MVS_LAUNCH_CHECK();
     return MVSNERF_OK;

@@ -115,44 +115,75 @@ def channels_last_images(imgs):
     return dst
 
 
-def gather(vol_cl, imgs, w2cs, intrinsics, rays_pts, rays_ndc, rays_dir=None):
-    """Fused gen_pts_feats (+ gen_dir_feature when rays_dir is given): -> (input_feat (N,S,8+4V), dirs (N,3) | None)."""
+def _count_ptr(count, S, op):
+    """count= of a counted launch after its refusals, made before the library is touched: the one-element int32 device tensor of
+    ops.live_samples / live_samples_range, on rows with S == 1.  Returns its address."""
+    if not (torch.is_tensor(count) and count.is_cuda and count.dtype == torch.int32 and count.numel() == 1):
+        raise RuntimeError(f"{op}: count must be the one-element int32 device tensor of ops.live_samples")
+    if S != 1:
+        raise RuntimeError(f"{op}: count= takes the rows form only (S == 1: every row is its own ray), got S = {S}")
+    return count.data_ptr()
+
+
+def _gather_out(out, N, S, F, with_dirs, dev, op):
+    """(feat (N,S,F), dirs (N,3) | None) of a gather: fresh, or the caller's pair `out` (what a counted launch leaves untouched stays visible)."""
+    if out is None:
+        return (torch.empty((N, S, F), device=dev, dtype=torch.float32), torch.empty((N, 3), device=dev, dtype=torch.float32) if with_dirs else None)
+    feat, dirs = out
+    if tuple(feat.shape) != (N, S, F) or (with_dirs and (dirs is None or tuple(dirs.shape) != (N, 3))):
+        raise RuntimeError(f"{op}: out must be (feat ({N},{S},{F}), dirs ({N},3))")
+    dev_f32(feat, f"{op}: out[0]")
+    if with_dirs:
+        dev_f32(dirs, f"{op}: out[1]")
+    return feat, dirs if with_dirs else None
+
+
+def gather(vol_cl, imgs, w2cs, intrinsics, rays_pts, rays_ndc, rays_dir=None, count=None, out=None):
+    """Fused gen_pts_feats (+ gen_dir_feature when rays_dir is given): -> (input_feat (N,S,8+4V), dirs (N,3) | None).
+    count: the (1,) int32 device tensor of ops.live_samples - the counted launch of DESIGN.md 4i on rows (S == 1): N is then the capacity, rows
+    [0, min(max(count, 0), N)) get the bits of the call on that many rows and no other row is written.  out: a caller-owned (feat, dirs) pair."""
     _need_no_grad(vol_cl, imgs, rays_pts, rays_ndc, op="gather")
     N, S = rays_ndc.shape[:2]
+    cptr = None if count is None else _count_ptr(count, S, "gather")
     V = imgs.shape[0]
     F = 8 + 4 * V
     D, H, W, C = vol_cl.shape
     if C != 8:
         raise RuntimeError("gather: the neural volume must have 8 channels")
-    feat = torch.empty((N, S, F), device=rays_ndc.device, dtype=torch.float32)
-    dirs = None if rays_dir is None else torch.empty((N, 3), device=rays_ndc.device, dtype=torch.float32)
+    feat, dirs = _gather_out(out, N, S, F, rays_dir is not None, rays_ndc.device, "gather")
     icl = channels_last_images(imgs)
     vp, vl = vol_ptr_layout(vol_cl)
-    check(_lib.lib().mvsnerf_gather_fwd(vp, D, H, W, icl.data_ptr(), V, imgs.shape[2], imgs.shape[3],
-                                        dev_f32(w2cs, "w2cs"), dev_f32(intrinsics, "intrinsics"), dev_f32(rays_pts, "rays_pts"),
-                                        dev_f32(rays_ndc, "rays_ndc"), N, S, 0 if rays_dir is None else dev_f32(rays_dir, "rays_dir"),
-                                        feat.data_ptr(), F, 0 if dirs is None else dirs.data_ptr(), vl, stream_ptr()), "gather_fwd")
+    head = (vp, D, H, W, icl.data_ptr(), V, imgs.shape[2], imgs.shape[3], dev_f32(w2cs, "w2cs"), dev_f32(intrinsics, "intrinsics"),
+            dev_f32(rays_pts, "rays_pts"), dev_f32(rays_ndc, "rays_ndc"))
+    tail = (0 if rays_dir is None else dev_f32(rays_dir, "rays_dir"), feat.data_ptr(), F, 0 if dirs is None else dirs.data_ptr(), vl, stream_ptr())
+    if cptr is None:
+        check(_lib.lib().mvsnerf_gather_fwd(*head, N, S, *tail), "gather_fwd")
+    else:
+        check(_lib.lib().mvsnerf_gather_fwd_counted(*head, N, cptr, *tail), "gather_fwd_counted")
     return feat, dirs
 
 
-def gather_colorvol(vol_cl, rays_ndc, rays_dir=None, w2c_ref=None, force_offsets64=False):
+def gather_colorvol(vol_cl, rays_ndc, rays_dir=None, w2c_ref=None, force_offsets64=False, count=None, out=None):
     """gen_pts_feats of --use_color_volume (+ gen_dir_feature when rays_dir is given) in one launch: vol_cl (D,H,W,C) with C % 4 == 0,
     8 < C <= 40; rays_ndc (N,S,3) -> (input_feat (N,S,C), dirs (N,3) | None).  The bits of volume_sample / dir_feature(normalize=True).
-    force_offsets64: run the kernel's 64-bit-offset form whatever the sizes (tests)."""
+    force_offsets64: run the kernel's 64-bit-offset form whatever the sizes (tests).  count / out: as ops.gather."""
     _need_no_grad(vol_cl, rays_ndc, rays_dir, op="gather_colorvol")
     if rays_ndc.dim() != 3 or rays_ndc.shape[-1] != 3:
         raise RuntimeError(f"gather_colorvol: rays_ndc must be (N,S,3), got {tuple(rays_ndc.shape)}")
     N, S = rays_ndc.shape[:2]
+    cptr = None if count is None else _count_ptr(count, S, "gather_colorvol")
     D, H, W, C = vol_cl.shape
-    feat = torch.empty((N, S, C), device=rays_ndc.device, dtype=torch.float32)
-    dirs = None if rays_dir is None else torch.empty((N, 3), device=rays_ndc.device, dtype=torch.float32)
     if rays_dir is not None and tuple(rays_dir.shape) != (N, 3):
         raise RuntimeError(f"gather_colorvol: rays_dir must be ({N},3), got {tuple(rays_dir.shape)}")
+    feat, dirs = _gather_out(out, N, S, C, rays_dir is not None, rays_ndc.device, "gather_colorvol")
     vp, vl = vol_ptr_layout(vol_cl)
-    check(_lib.lib().mvsnerf_gather_colorvol_fwd(vp, D, H, W, C, dev_f32(rays_ndc, "rays_ndc"), N, S,
-                                                 0 if rays_dir is None else dev_f32(rays_dir, "rays_dir"),
-                                                 0 if w2c_ref is None else dev_f32(w2c_ref, "w2c_ref"), feat.data_ptr(), C,
-                                                 0 if dirs is None else dirs.data_ptr(), vl, int(bool(force_offsets64)), stream_ptr()), "gather_colorvol_fwd")
+    head = (vp, D, H, W, C, dev_f32(rays_ndc, "rays_ndc"))
+    tail = (0 if rays_dir is None else dev_f32(rays_dir, "rays_dir"), 0 if w2c_ref is None else dev_f32(w2c_ref, "w2c_ref"), feat.data_ptr(), C,
+            0 if dirs is None else dirs.data_ptr(), vl, int(bool(force_offsets64)), stream_ptr())
+    if cptr is None:
+        check(_lib.lib().mvsnerf_gather_colorvol_fwd(*head, N, S, *tail), "gather_colorvol_fwd")
+    else:
+        check(_lib.lib().mvsnerf_gather_colorvol_fwd_counted(*head, N, cptr, *tail), "gather_colorvol_fwd_counted")
     return feat, dirs
 
 
@@ -531,17 +562,44 @@ def mlp_pack_bf16(weights, F):
 
 
 def mlp_forward(packed, F, ndc_ptr, ndc_stride, feat_ptr, feat_stride, dirs_ptr, dirs_stride, N, S, alpha_only, device, *,
-                packed_bf16=None, packed_split=None, guard=None):
+                packed_bf16=None, packed_split=None, guard=None, count=None, out=None):
     """Network query (run_network_mvs, renderer.py:42-63) -> raw (N*S, 1 if alpha_only else 4).  The keywords choose the kernel as the ray march
     does (Renderer_ours.packed_alt returns them): guard + packed_split = (fp16x3 planes, 18) -> the guarded sequence, packed_split = (planes,
-    n_split) -> the split kernel, packed_bf16 -> bf16, none -> fp32.  A WidePacked (netwidth 256) runs the wide fp32 kernel and takes no keyword."""
+    n_split) -> the split kernel, packed_bf16 -> bf16, none -> fp32.  A WidePacked (netwidth 256) runs the wide fp32 kernel and takes no keyword.
+    count: the (1,) int32 device tensor of ops.live_samples - the counted launch of DESIGN.md 4i on dense rows (S == 1, strides 3 / F / 3): N is
+    then the capacity, rows [0, min(max(count, 0), N)) of raw get the bits of the call with that N and no other row is written; the bf16 family has
+    no counted kernel.  out: a caller-owned contiguous fp32 (N*S, 1 | 4) tensor to write into."""
+    cptr = None
+    if count is not None:           # the refusals of a counted launch, before the library is touched
+        cptr = _count_ptr(count, S, "mlp_forward")
+        _device_count_mode(packed_bf16, packed_split, "mlp_forward(count=)")
+        if (ndc_stride, feat_stride, dirs_stride) != (3, F, 3):
+            raise RuntimeError(f"mlp_forward: count= takes dense rows (strides 3 / {F} / 3), got {ndc_stride} / {feat_stride} / {dirs_stride}")
     wide = isinstance(packed, WidePacked)
     if wide:
         if packed_bf16 is not None or packed_split is not None or guard is not None:
             raise ValueError("mlp_forward: netwidth 256 runs on the fp32 wide kernel only; packed_bf16 / packed_split / guard select 128-wide kernels")
         if packed.F != F:
             raise RuntimeError(f"mlp_forward: the buffer was packed for feat_dim {packed.F}, the call says {F}")
-    l, raw = _lib.lib(), torch.empty((N * S, 1 if alpha_only else 4), device=device, dtype=torch.float32)
+    l = _lib.lib()
+    raw = torch.empty((N * S, 1 if alpha_only else 4), device=device, dtype=torch.float32) if out is None else out
+    if out is not None:
+        if tuple(raw.shape) != (N * S, 1 if alpha_only else 4):
+            raise RuntimeError(f"mlp_forward: out must be ({N * S},{1 if alpha_only else 4}), got {tuple(raw.shape)}")
+        dev_f32(raw, "mlp_forward: out")
+    if cptr is not None:
+        io = (ndc_ptr, feat_ptr, dirs_ptr, N, cptr, int(alpha_only), raw.data_ptr())
+        if wide:
+            check(l.mvsnerf_mlp_fwd_wide_counted(dev_f32(packed.buffer, "packed"), F, packed.width, *io, stream_ptr()), "mlp_fwd_wide_counted")
+        elif guard is not None:
+            if packed_split is None:
+                raise ValueError("mlp_forward: a guard needs the fp16x3 split planes (the guarded sequence)")
+            check(l.mvsnerf_mlp_fwd_guarded_counted(packed_split[0].data_ptr(), packed.data_ptr(), F, *io, guard.data_ptr(), stream_ptr()), "mlp_fwd_guarded_counted")
+        elif packed_split is not None:
+            check(l.mvsnerf_mlp_fwd_split_counted(packed_split[0].data_ptr(), packed.data_ptr(), F, packed_split[1], *io, stream_ptr()), "mlp_fwd_split_counted")
+        else:
+            check(l.mvsnerf_mlp_fwd_counted(packed.data_ptr(), F, *io, stream_ptr()), "mlp_fwd_counted")
+        return raw
     io = (ndc_ptr, ndc_stride, feat_ptr, feat_stride, dirs_ptr, dirs_stride, N, S, int(alpha_only), raw.data_ptr())
     if wide:
         check(l.mvsnerf_mlp_fwd_wide(dev_f32(packed.buffer, "packed"), F, packed.width, *io, stream_ptr()), "mlp_fwd_wide")
@@ -556,6 +614,17 @@ def mlp_forward(packed, F, ndc_ptr, ndc_stride, feat_ptr, feat_stride, dirs_ptr,
     else:
         check(l.mvsnerf_mlp_fwd(packed.data_ptr(), F, *io, stream_ptr()), "mlp_fwd")
     return raw
+
+
+def _device_count_mode(packed_bf16, packed_split, op):
+    """The bf16 family has no counted forward kernel: a kernel choice (MVSNeRF.packed_alt's keywords) that names one is refused
+    by its mode's name."""
+    mode = "bf16" if packed_bf16 is not None else None
+    if packed_split is not None and packed_split[1] != N_SPLIT["fp16x3"]:
+        mode = {v: k for k, v in N_SPLIT.items()}.get(packed_split[1], f"n_split {packed_split[1]}")
+    if mode is not None:
+        raise NotImplementedError(f"{op}: the {mode!r} MLP kernels take their row count from the host only; device counts run under "
+                                  "'auto', 'fp32' and 'fp16x3' (and netwidth 256)")
 
 
 def _mlp_fields(packed_bf16, packed_split, guard):
@@ -894,16 +963,49 @@ def _compact_rows_mlp(vol_cl, imgs, w2cs, intrinsics, ndc_c, pts_c, dir_c, n, ml
     return ndc_l, mlp(ndc_l, feat, dirs, n)
 
 
-def raymarch_sparse(vol_cl, imgs, w2cs, intrinsics, packed, rays_pts, rays_ndc, z_vals, rays_dir, density, thr, white_bkgd=False, want=(), **packed_alt):
+def _compact_rows_mlp_counted(vol_cl, imgs, w2cs, intrinsics, ndc_c, pts_c, dir_c, count, mlp):
+    """_compact_rows_mlp without the host: the counted gather and the counted MLP stage on the worst-case buffers of ops.live_samples /
+    ops.live_samples_range, both enqueued whatever `count` holds: mlp(ndc_c (cap,3), feat (cap,1,F), dirs (cap,3), cap) -> raw_c (cap,4), of which
+    rows [0, count) are written.  A capacity of 0 rows enqueues nothing."""
+    cap = ndc_c.shape[0]
+    if not cap:
+        return torch.empty((0, 4), device=ndc_c.device, dtype=torch.float32)
+    ndc_g = ndc_c.view(cap, 1, 3)
+    if vol_cl.shape[-1] != 8:
+        feat, dirs = gather_colorvol(vol_cl, ndc_g, dir_c, w2cs[0].contiguous(), count=count)
+    else:
+        feat, dirs = gather(vol_cl, imgs, w2cs, intrinsics, pts_c.view(cap, 1, 3), ndc_g, dir_c, count=count)
+    return mlp(ndc_c, feat, dirs, cap)
+
+
+def raymarch_sparse(vol_cl, imgs, w2cs, intrinsics, packed, rays_pts, rays_ndc, z_vals, rays_dir, density, thr, white_bkgd=False, want=(),
+                    device_count=False, **packed_alt):
     """ops.raymarch's outputs with the radiance MLP run on the live samples only (ops.live_samples of `density` at `thr`): the sequence of
     _sparse_march with ops.mlp_forward as its MLP stage.  packed: mlp_pack's buffer or a WidePacked; **packed_alt: the kernel choice of
-    ops.mlp_forward (MVSNeRF.packed_alt).  Returns raw, rgb_map, weights, depth, alpha, disp / acc when in `want`, and n_live (int)."""
+    ops.mlp_forward (MVSNeRF.packed_alt).  Returns raw, rgb_map, weights, depth, alpha, disp / acc when in `want`, and n_live (int).
+    device_count=True: the same sequence without the host read - the gather and the MLP are counted launches on the worst-case (N*S)-row
+    buffers, enqueued whatever the count is; the outputs have the same bits, n_live is an int32 device scalar, and the call can be enqueued ahead or
+    captured into a graph.  Not under the bf16-family modes (NotImplementedError)."""
+    if device_count:
+        _device_count_mode(packed_alt.get("packed_bf16"), packed_alt.get("packed_split"), "raymarch_sparse(device_count=True)")
     _need_no_grad(vol_cl, imgs, rays_pts, rays_ndc, z_vals, rays_dir, density, op="raymarch_sparse")
     thr = _thr_f32(thr, "raymarch_sparse")
     C = vol_cl.shape[-1]
     F = C if C != 8 else 8 + 4 * imgs.shape[0]
     if C != 8 and C != 8 + 4 * w2cs.shape[0]:
         raise RuntimeError(f"raymarch_sparse: the volume has {C} channels, 8 + 4V is {8 + 4 * w2cs.shape[0]}")
+    if device_count:
+        N, S = z_vals.shape
+        dev = rays_ndc.device
+        count, idx, ndc_c, pts_c, dir_c = live_samples(density, rays_ndc, thr, None if C != 8 else rays_pts, rays_dir)
+        raw_c = _compact_rows_mlp_counted(
+            vol_cl, imgs, w2cs, intrinsics, ndc_c, pts_c, dir_c, count,
+            lambda ndc_l, feat, dirs, cap: mlp_forward(packed, F, ndc_l.data_ptr(), 3, feat.data_ptr(), F, dirs.data_ptr(), 3, cap, 1, 0, dev, count=count, **packed_alt))
+        raw = expand_rows(raw_c, idx, count, N * S).view(N, S, 4)
+        rgb, disp, acc, weights, depth, alpha = composite(raw, z_vals, white_bkgd)
+        out = {"raw": raw, "rgb_map": rgb, "weights": weights, "depth": depth, "alpha": alpha, "n_live": count.reshape(())}
+        out.update({k: v for k, v in (("disp", disp), ("acc", acc)) if k in want})
+        return out
     (_, _, _, _, raw, n_live), (rgb, disp, acc, weights, depth, alpha) = _sparse_march(
         vol_cl, imgs, w2cs, intrinsics, rays_pts, rays_ndc, z_vals, rays_dir, density, thr, white_bkgd,
         lambda ndc_l, feat, dirs, n: mlp_forward(packed, F, ndc_l.data_ptr(), 3, feat.data_ptr(), F, dirs.data_ptr(), 3, n, 1, 0, rays_ndc.device, **packed_alt))
@@ -1011,7 +1113,14 @@ def raymarch_early_stop(vol_cl, imgs, w2cs, intrinsics, packed, rays_pts, rays_n
     nothing more is enqueued for the segment) -> the gather-and-MLP stage of _sparse_march on the compact rows -> scatter_rows into the zero-filled
     raw -> ray_transmittance over the segment (not after the last one); then ops.composite.  eps = 0 stops no ray: every output equals the dense call's.
     The dropped weights of a ray sum to less than eps (1 + S 1e-10): rgb_map and acc move by at most eps, depth by eps max|z|.
-    Returns raymarch_sparse's dict plus n_live (samples that went through the MLP) and n_stopped (rays stopped at some boundary)."""
+    Returns raymarch_sparse's dict plus n_live (samples that went through the MLP) and n_stopped (rays stopped at some boundary).
+    device_count (keyword, default False; it travels among **packed_alt because this function's named parameters are pinned): True is
+    the march without a host read - every segment is enqueued with counted gather and MLP launches on its worst-case buffers, the per-segment counts
+    are summed on the device and n_live / n_stopped are int32 device scalars; the other outputs have the same bits.  Not under the bf16-family modes
+    (NotImplementedError)."""
+    device_count = bool(packed_alt.pop("device_count", False))
+    if device_count:
+        _device_count_mode(packed_alt.get("packed_bf16"), packed_alt.get("packed_split"), "raymarch_early_stop(device_count=True)")
     eps, G = _early_stop_args(eps, stop_every, "raymarch_early_stop")
     if (density is None) != (thr is None):
         raise ValueError("raymarch_early_stop: density and thr are given together or not at all")
@@ -1029,6 +1138,23 @@ def raymarch_early_stop(vol_cl, imgs, w2cs, intrinsics, packed, rays_pts, rays_n
     raw = torch.zeros((N, S, 4), device=dev, dtype=torch.float32)
     bounds = list(range(0, S, G)) + [S]
     ray_T = torch.ones((N,), device=dev, dtype=torch.float32) if len(bounds) > 2 else None
+    if device_count:
+        n_live = torch.zeros((), device=dev, dtype=torch.int32)
+        for k, (s0, s1) in enumerate(zip(bounds[:-1], bounds[1:])):
+            count, idx, ndc_c, pts_c, dir_c = live_samples_range(density, rays_ndc, thr, s0, s1, ray_T if k else None, eps,
+                                                                 None if color_vol else rays_pts, rays_dir)
+            n_live = n_live + count[0]
+            raw_c = _compact_rows_mlp_counted(
+                vol_cl, imgs, w2cs, intrinsics, ndc_c, pts_c, dir_c, count,
+                lambda ndc_l, feat, dirs, cap: mlp_forward(packed, F, ndc_l.data_ptr(), 3, feat.data_ptr(), F, dirs.data_ptr(), 3, cap, 1, 0, dev, count=count, **packed_alt))
+            scatter_rows(raw_c, idx, count, raw.view(N * S, 4))
+            if s1 < S:
+                ray_transmittance(raw, s0, s1, ray_T)
+        n_stopped = torch.zeros((), device=dev, dtype=torch.int32) if ray_T is None else (ray_T < eps).sum(dtype=torch.int32)
+        rgb, disp, acc, weights, depth, alpha = composite(raw, z_vals, white_bkgd)
+        out = {"raw": raw, "rgb_map": rgb, "weights": weights, "depth": depth, "alpha": alpha, "n_live": n_live, "n_stopped": n_stopped}
+        out.update({k: v for k, v in (("disp", disp), ("acc", acc)) if k in want})
+        return out
     n_live, n_stopped = 0, 0
     for k, (s0, s1) in enumerate(zip(bounds[:-1], bounds[1:])):
         count, idx, ndc_c, pts_c, dir_c = live_samples_range(density, rays_ndc, thr, s0, s1, ray_T if k else None, eps,

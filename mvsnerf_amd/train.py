@@ -151,28 +151,47 @@ def _early_stop(early_stop, stop_every, who):
     return None if early_stop is None else ops._early_stop_args(early_stop, stop_every, f"{who}(early_stop=)")
 
 
-def _render_sparse_batches(system, n_rows, B, make_batch, march_kw, early_stop=None):
+def _device_count(device_count, skip_empty, stop, who):
+    """device_count= of a render call as a bool after its refusals, which need no library: it belongs to the sparse paths, and the
+    bf16-family MLP modes have no counted kernels."""
+    if not device_count:
+        return False
+    if skip_empty is None and stop is None:
+        raise ValueError(f"{who}: device_count=True is a switch of the skip_empty / early_stop paths; pass one of them with it")
+    mode = ops.inference_mlp_mode()
+    if mode in ("bf16", "bf16x3", "bf16x6"):
+        raise NotImplementedError(f"{who}(device_count=True): the {mode!r} MLP kernels take their row count from the host only; device counts run "
+                                  "under 'auto', 'fp32' and 'fp16x3'")
+    return True
+
+
+def _render_sparse_batches(system, n_rows, B, make_batch, march_kw, early_stop=None, device_count=False):
     """A frame of n_rows rays with empty space skipped, per sub-batch of B rays: make_batch(idx) -> (pts, ndc, z, dirs) of rays [idx * B, (idx + 1) * B)
     -> ops.raymarch_sparse(**march_kw: vol_cl, imgs, w2cs, intrinsics, packed, density, thr, white_bkgd and the kernel choice) - one host read of
     the live count per sub-batch.  The sub-batches are sharded over the ranks (distributed.render_frame); system.last_live_fraction is this rank's
     live samples over its samples.  Returns (rgb (n_rows,3), depth (n_rows,)).
     early_stop: (eps, stop_every) of _early_stop - the sub-batch call is ops.raymarch_early_stop (march_kw with or without density /
     thr), one host read per segment of stop_every samples; last_live_fraction then counts the samples that reached the MLP, and
-    system.last_stopped_fraction is this rank's stopped rays over its rays."""
+    system.last_stopped_fraction is this rank's stopped rays over its rays.
+    device_count: the sub-batch calls run with device_count=True - no host read per sub-batch or segment; the counts are summed on
+    the device and read ONCE, after the frame's last sub-batch has been enqueued, for the two fractions."""
     live = [0, 0, 0, 0]             # live samples, samples, stopped rays, rays
+    kw = dict(march_kw, device_count=True) if device_count else march_kw
 
     def render_batch(idx):
         pts, ndc, z, dirs = make_batch(idx)
         if early_stop is None:
-            o = ops.raymarch_sparse(rays_pts=pts, rays_ndc=ndc, z_vals=z, rays_dir=dirs, **march_kw)
+            o = ops.raymarch_sparse(rays_pts=pts, rays_ndc=ndc, z_vals=z, rays_dir=dirs, **kw)
         else:
-            o = ops.raymarch_early_stop(rays_pts=pts, rays_ndc=ndc, z_vals=z, rays_dir=dirs, eps=early_stop[0], stop_every=early_stop[1], **march_kw)
-            live[2] += o["n_stopped"]
+            o = ops.raymarch_early_stop(rays_pts=pts, rays_ndc=ndc, z_vals=z, rays_dir=dirs, eps=early_stop[0], stop_every=early_stop[1], **kw)
+            live[2] = live[2] + (o["n_stopped"].long() if device_count else o["n_stopped"])
             live[3] += z.shape[0]
-        live[0] += o["n_live"]
+        live[0] = live[0] + (o["n_live"].long() if device_count else o["n_live"])       # (int64 device sums: a frame can hold more than 2^31 samples)
         live[1] += z.numel()
         return o["rgb_map"], o["depth"]
     out = D.render_frame(render_batch, 1, n_rows, B)
+    if torch.is_tensor(live[0]):                                 # device_count: the frame's one host read, behind its last sub-batch
+        live[0], live[2] = torch.stack([live[0], live[2] if torch.is_tensor(live[2]) else torch.zeros_like(live[0])]).tolist()
     system.last_live_fraction = live[0] / live[1] if live[1] else 0.0
     if early_stop is not None:
         system.last_stopped_fraction = live[2] / live[3] if live[3] else 0.0
@@ -330,7 +349,7 @@ class MVSSystem(_ModuleShim):
 
     @torch.no_grad()
     def render_view(self, batch, chunk=None, whole_frame_off=False, target=None, batch_rays=16384, volume=None, skip_empty=None, density=None, dilate=0,
-                    early_stop=None, stop_every=32):
+                    device_count=False, early_stop=None, stop_every=32):
         """The rendering part of validation_step (:172-254): encode once, then the chunk loop over the target view's
         pixels - tile-parallel over ranks (contiguous chunk ranges + one all_gather).  Returns (rgb (H,W,3), depth (H,W)).
         whole_frame_off=True keeps the per-chunk Python loop (build_rays_test + rendering per chunk) instead of the single
@@ -352,8 +371,11 @@ class MVSSystem(_ModuleShim):
         early_stop: None (default) changes nothing.  A float eps in [0, 1) stops a ray at the first multiple of stop_every samples in front of which its
         transmittance is < eps (ops.raymarch_early_stop per sub-batch, one host read per segment; rgb moves by at most eps, depth by
         eps max|z|).  Alone it needs no density volume; with skip_empty a sample reaches the MLP iff its ray is alive and its cell is live.
-        `self.last_stopped_fraction` is this rank's stopped rays over its rays, last_live_fraction the samples that reached the MLP."""
+        `self.last_stopped_fraction` is this rank's stopped rays over its rays, last_live_fraction the samples that reached the MLP.
+        device_count: False (default) changes nothing.  True (with skip_empty or early_stop only, not under the bf16-family modes) runs
+        the sub-batches without a host read - the same pixels; the two fractions come from one host read behind the frame's last sub-batch."""
         stop = _early_stop(early_stop, stop_every, "render_view")          # refusals first: nothing below needs the library before them
+        device_count = _device_count(device_count, skip_empty, stop, "render_view")
         if stop is not None and whole_frame_off:
             raise ValueError("render_view: early_stop runs its own per-sub-batch loop; it cannot be combined with whole_frame_off=True")
         if skip_empty is not None:
@@ -407,7 +429,8 @@ class MVSSystem(_ModuleShim):
                 pts, dirs, ndc, z, _ = ops.raygen(H, W, k_render, tgt_to_world, k_ndc, world_to_ref, nf_t, nf_r, args.N_samples, pad=args.pad,
                                                   first_pixel=first, n_rays=min(B, H * W - first), ref_hw=ref_hw)
                 return pts, ndc, z, dirs
-            rgb, depth = _render_sparse_batches(self, H * W, B, make_batch, dict(src, vol_cl=ops.channels_last_volume(volume_feature)), early_stop=stop)
+            rgb, depth = _render_sparse_batches(self, H * W, B, make_batch, dict(src, vol_cl=ops.channels_last_volume(volume_feature)), early_stop=stop,
+                                                device_count=device_count)
             return rgb.reshape(H, W, 3), depth.reshape(H, W)
         fused = (isinstance(net, MVSNeRF) and getattr(kw.get("network_query_fn"), "_mvsnerf_fused", False)
                  and not getattr(args, "use_color_volume", False) and args.feat_dim == 8 + 4 * V and not whole_frame_off
@@ -453,20 +476,22 @@ class MVSSystem(_ModuleShim):
         return self._render_path(batch, c2ws_render, hw, intrinsic, near_far, depth_panel, crop, minmax, cmap, volume, None, 0)
 
     @torch.no_grad()
-    def render_path_skip_empty(self, batch, c2ws_render, skip_empty, dilate=0, **render_path_kw):
+    def render_path_skip_empty(self, batch, c2ws_render, skip_empty, dilate=0, device_count=False, **render_path_kw):
         """render_path with render_view's skip_empty (a density threshold): the scene is encoded once, its density volume is built ONCE per
         path next to the encode (scene_density(batch, volume, dilate)), and both are handed to every render_view call.  render_path_kw: render_path's
-        keywords (hw, intrinsic, near_far, depth_panel, crop, minmax, cmap, volume).  `self.last_live_fraction` is the last frame's."""
+        keywords (hw, intrinsic, near_far, depth_panel, crop, minmax, cmap, volume).  `self.last_live_fraction` is the last frame's.
+        device_count: render_view's - one host read per frame, for the fraction, instead of one per sub-batch."""
         skip_empty = _threshold(skip_empty, "render_path_skip_empty(skip_empty=)")       # before the encode; render_view parses it again per frame
+        device_count = _device_count(device_count, skip_empty, None, "render_path_skip_empty")
         names = ("hw", "intrinsic", "near_far", "depth_panel", "crop", "minmax", "cmap", "volume")
         unknown = sorted(set(render_path_kw) - set(names))
         if unknown:
             raise TypeError(f"render_path_skip_empty: unexpected keyword(s) {unknown}; render_path's are {list(names)}")
         kw = dict(hw=None, intrinsic=None, near_far=None, depth_panel=True, crop=False, minmax=None, cmap=None, volume=None)
         kw.update(render_path_kw)
-        return self._render_path(batch, c2ws_render, *(kw[n] for n in names), skip_empty, dilate)
+        return self._render_path(batch, c2ws_render, *(kw[n] for n in names), skip_empty, dilate, device_count)
 
-    def _render_path(self, batch, c2ws_render, hw, intrinsic, near_far, depth_panel, crop, minmax, cmap, volume, skip_empty, dilate):
+    def _render_path(self, batch, c2ws_render, hw, intrinsic, near_far, depth_panel, crop, minmax, cmap, volume, skip_empty, dilate, device_count=False):
         batch = batch_to_device({k: v for k, v in batch.items() if k != "scan"}, self.device)
         _, pose_ref = self.decode_batch(batch)
         dev = self.device
@@ -478,7 +503,8 @@ class MVSSystem(_ModuleShim):
             c2ws = torch.cat([c2ws, torch.tensor([0.0, 0.0, 0.0, 1.0], device=dev).expand(c2ws.shape[0], 1, 4)], 1)
         crop, mm, lut, frames = _frame_setup(c2ws.shape[0], H, W, depth_panel, crop, minmax, cmap, pose_ref["near_fars"][0], dev)
         vol = self.encode_scene(batch) if volume is None else volume
-        sparse = {} if skip_empty is None else dict(skip_empty=skip_empty, density=self.scene_density(batch, volume=vol, dilate=dilate))
+        sparse = {} if skip_empty is None else dict(skip_empty=skip_empty, density=self.scene_density(batch, volume=vol, dilate=dilate),
+                                                    device_count=device_count)
         for k in range(c2ws.shape[0]):
             rgb, depth = self.render_view(batch, volume=vol, target=dict(hw=(H, W), intrinsic=intrinsic, c2w=c2ws[k], near_far=near_far), **sparse)
             ops.frame_u8(rgb, depth if depth_panel else None, minmax=mm, lut=lut, crop=crop, out=frames[k])
@@ -875,7 +901,8 @@ class MVSSystemFinetune(_ModuleShim):
 
     # -- rendering the fine-tuned scene (train_mvs_nerf_finetuning_pl.py:192-252) ---------------------
     @torch.no_grad()
-    def render_rays(self, rays, chunk=None, batch_rays=16384, u=None, whole_frame_off=False, skip_empty=None, early_stop=None, stop_every=32):
+    def render_rays(self, rays, chunk=None, batch_rays=16384, u=None, whole_frame_off=False, skip_empty=None, device_count=False, early_stop=None,
+                    stop_every=32):
         """The rendering part of the fine-tuning script's validation_step (:204-237) for the dataset's rays (N,8) = [o | d | near | far]: per
         chunk ray_marcher -> get_ndc_coordinate -> [ray_marcher_fine, when a density volume exists and args.N_importance > 0] -> rendering, from
         the learnt `self.volume` (8 channels + the source images, or the (8 + 4V)-channel colour volume of --use_color_volume).  Returns
@@ -890,8 +917,10 @@ class MVSSystemFinetune(_ModuleShim):
         ops.ray_points -> [ray_marcher_fine] -> ops.raymarch_sparse: _render_sparse_batches), the sub-batches sharded over the ranks, one host read of the live count per
         sub-batch; `self.last_live_fraction` is this rank's live samples over its samples.
         early_stop / stop_every: as MVSSystem.render_view (DESIGN.md 4h) - alone it needs no density volume, with skip_empty it uses that one;
-        with N_importance > 0 the merged depths are simply a larger S.  `self.last_stopped_fraction` is this rank's stopped rays over its rays."""
+        with N_importance > 0 the merged depths are simply a larger S.  `self.last_stopped_fraction` is this rank's stopped rays over its rays.
+        device_count: as MVSSystem.render_view - the sparse sub-batches without a host read, the same values."""
         stop = _early_stop(early_stop, stop_every, "render_rays")          # refusals first: nothing below needs the library before them
+        device_count = _device_count(device_count, skip_empty, stop, "render_rays")
         if stop is not None and whole_frame_off:
             raise ValueError("render_rays: early_stop runs its own per-sub-batch loop; it cannot be combined with whole_frame_off=True")
         if skip_empty is not None:
@@ -947,7 +976,7 @@ class MVSSystemFinetune(_ModuleShim):
             def make_batch(idx):
                 pts, ndc, z, _, rays_d = march(idx, B)
                 return pts, ndc, z.contiguous(), rays_d.contiguous()
-            return _render_sparse_batches(self, N, B, make_batch, dict(src, vol_cl=ops.channels_last_volume(vol)), early_stop=stop)
+            return _render_sparse_batches(self, N, B, make_batch, dict(src, vol_cl=ops.channels_last_volume(vol)), early_stop=stop, device_count=device_count)
         net, color_vol = _sparse_config(self, vol, V, who)
         vol_cl = ops.channels_last_volume(vol)
         t = torch.linspace(0, 1, args.N_samples, device=dev)
@@ -963,11 +992,14 @@ class MVSSystemFinetune(_ModuleShim):
         return D.render_frame_pixels(render_range, 1, N, chunk, device=dev)
 
     @torch.no_grad()
-    def render_path(self, c2ws_render, hw, focal, depth_panel=True, crop=False, minmax=None, cmap=None, **render_rays_kw):
+    def render_path(self, c2ws_render, hw, focal, depth_panel=True, crop=False, minmax=None, cmap=None, device_count=False, **render_rays_kw):
         """The video loop of renderer_video.ipynb for the fine-tuned scene: per pose of c2ws_render (K,4,4) the notebook's rays (get_ray_directions(H, W,
         focal) / get_rays, the source near / far) -> render_rays -> ops.frame_u8 into frame k.  Returns uint8 (K, H', W' * panels, 3) on the device;
-        depth_panel / crop / minmax / cmap as MVSSystem.render_path (minmax defaults to the source near / far); other keywords go to render_rays."""
-        return _render_path_rays(self, c2ws_render, hw, focal, self.near_far_source, depth_panel, crop, minmax, cmap, self.imgs.device, **render_rays_kw)
+        depth_panel / crop / minmax / cmap as MVSSystem.render_path (minmax defaults to the source near / far); device_count and the other keywords go to
+        render_rays (device_count=True with skip_empty / early_stop: one host read per frame)."""
+        _device_count(device_count, render_rays_kw.get("skip_empty"), render_rays_kw.get("early_stop"), "render_path")
+        return _render_path_rays(self, c2ws_render, hw, focal, self.near_far_source, depth_panel, crop, minmax, cmap, self.imgs.device,
+                                 device_count=device_count, **render_rays_kw)
 
     @torch.no_grad()
     def validation_step(self, batch, batch_nb):
@@ -1240,7 +1272,7 @@ class MVSSystemFusion(_ModuleShim):
         return ops.node_density(dilate=dilate, **_density_sources(self.network_fn, F, self.volume.feat_volume.detach(), self.pose_source_ref, (F - 8) // 4))
 
     @torch.no_grad()
-    def render_rays(self, rays, chunk=None, batch_rays=65536, skip_empty=None, early_stop=None, stop_every=32):
+    def render_rays(self, rays, chunk=None, batch_rays=65536, skip_empty=None, device_count=False, early_stop=None, stop_every=32):
         """The rendering part of validation_step (:307-324) for rays (N,8): per chunk ops.ray_march_bbox -> rendering, the chunks of up to batch_rays
         rays issued as one renderer.rendering_batched call; chunk ranges are sharded over the ranks as in MVSSystemFinetune.render_rays.
         Returns (rgb (N,3), depth (N,)).
@@ -1249,9 +1281,11 @@ class MVSSystemFusion(_ModuleShim):
         after update_density_volume(); the sub-batches are sharded over the ranks and `self.last_live_fraction` is this rank's live samples over its
         samples.
         early_stop / stop_every: as MVSSystem.render_view; alone it reads no density volume.  `self.last_stopped_fraction` is this
-        rank's stopped rays over its rays."""
+        rank's stopped rays over its rays.
+        device_count: as MVSSystem.render_view - the sparse sub-batches without a host read, the same values."""
         from .renderer import rendering_batched
         stop = _early_stop(early_stop, stop_every, "render_rays")          # refusals first: nothing below needs the library before them
+        device_count = _device_count(device_count, skip_empty, stop, "render_rays")
         if skip_empty is not None:
             skip_empty = _threshold(skip_empty, "render_rays(skip_empty=)")
         self._need_volume()
@@ -1275,7 +1309,7 @@ class MVSSystemFusion(_ModuleShim):
                 r = rays[idx * B:(idx + 1) * B]
                 pts, ndc, z = ops.ray_march_bbox(r, self.bbox_3d, args.N_samples, lindisp=lindisp, t=t)
                 return pts, ndc, z, r[:, 3:6].contiguous()
-            return _render_sparse_batches(self, N, B, make_batch, dict(src, vol_cl=ops.channels_last_volume(vol)), early_stop=stop)
+            return _render_sparse_batches(self, N, B, make_batch, dict(src, vol_cl=ops.channels_last_volume(vol)), early_stop=stop, device_count=device_count)
         n_chunks = (N + chunk - 1) // chunk
         world, rank = D.world_rank()
         lo, hi = D.shard_range(n_chunks, world, rank)
@@ -1293,12 +1327,13 @@ class MVSSystemFusion(_ModuleShim):
         return D._assemble_frame(torch.cat(rows, 0) if rows else None, 1, N, chunk, n_chunks, world, None, dev)
 
     @torch.no_grad()
-    def render_path(self, c2ws_render, hw, focal, depth_panel=True, crop=False, minmax=None, cmap=None, **render_rays_kw):
+    def render_path(self, c2ws_render, hw, focal, depth_panel=True, crop=False, minmax=None, cmap=None, device_count=False, **render_rays_kw):
         """MVSSystemFinetune.render_path for the fused scene: the rays of each pose carry the first camera's source near / far (render_rays clips them to
         the box), which is also the default depth range of the colour map."""
+        _device_count(device_count, render_rays_kw.get("skip_empty"), render_rays_kw.get("early_stop"), "render_path")
         self._need_volume()
         return _render_path_rays(self, c2ws_render, hw, focal, torch.as_tensor(self.views[0][2]), depth_panel, crop, minmax, cmap, self.bbox_3d.device,
-                                 **render_rays_kw)
+                                 device_count=device_count, **render_rays_kw)
 
     @torch.no_grad()
     def validation_step(self, batch, batch_nb):
