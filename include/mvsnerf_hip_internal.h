@@ -479,6 +479,35 @@ int mvsnerf_gather_fwd_counted(const float* vol, int D, int H, int W, const floa
 int mvsnerf_gather_colorvol_fwd_counted(const float* vol, int D, int H, int W, int C, const float* ndc, int64_t cap, const int* count,
                                         const float* rays_dir, const float* w2c_ref, float* feat, int feat_stride, float* dirs_out, int vol_layout,
                                         int force_offsets64, void* stream);
+/* ---- the training rays of a scene as a device-resident bank (data/dtu_ft.py:143-188 and data/blender.py:49-85, read_meta's all-rays buffer;
+ *      csrc/scene_rays.hip) ----
+ * Bank: images_rgba [M][H][W][4] uint8 (three-channel input is stored with alpha 255; a ray's colour is one 32-bit load), c2w [M][3][4], K [M][3][3],
+ *   near_far [M][2] fp32, depth_bank [M][H][W] fp32 or NULL.  idx [B] int64: flat indices into M*H*W, view-major then row-major - the order of
+ *   torch.cat(all_rays, 0): m = idx / (H W), y = (idx % (H W)) / W, x = idx % W.  An index outside [0, M H W) gives an all-zero row in every output and
+ *   nothing is read for it; no index makes a kernel read outside the bank.
+ * scene_rays_gather: rays [B][8] = [o | d | near | far] and rgb [B][3] - all_rays[idx], all_rgbs[idx] - plus depth [B] = depth_bank[idx] and
+ *   mask [B] (bytes 0 / 1, alpha > 0; data/blender.py:69) when those pointers are non-NULL (depth needs a depth_bank).
+ * scene_rays_march: the same rows and the front end of a fine-tuning step (train_mvs_nerf_finetuning_pl.py:147-156) in ONE launch: z [B][S] of
+ *   ray_marcher (data/ray_utils.py:152-197) from t [S] = the caller's linspace(0, 1, S), jitter [B][S] = the caller's torch.rand draw (read when
+ *   perturb > 0; NULL otherwise) and lindisp, pts [B][S][3] = o + d z, and, when ndc is non-NULL, ndc [B][S][3] = get_ndc_coordinate (utils.py:112-146)
+ *   in the reference camera (w2c_ref [4][4], K_ref [3][3], near_far_ref [2], W_ref, H_ref, pad), what mvsnerf_ray_points_fwd computes from the same rays.
+ * Arithmetic, fp32 with every operation rounded on its own unless stated (no contraction, IEEE divisions):
+ *   direction ((x - cx) / fx, (y - cy) / fy, 1) (data/ray_utils.py:27); rays_d[k] = (dx R[k][0] + dy R[k][1]) + R[k][2]; rays_o = c2w[:, 3]; near, far copied;
+ *   colour c / 255 (torch's ToTensor on the CPU), then rgb a + (1 - a) with a = alpha / 255 (data/blender.py:70; alpha 255 leaves rgb as it is);
+ *   z = near (1 - t) + far t (lindisp: 1 / ((1 / near)(1 - t) + (1 / far) t)); perturb > 0: lower + (upper - lower) * (perturb * jitter) between the
+ *   mid points 0.5 (z[s-1] + z[s]) (csrc/ray_dev.h, shared with mvsnerf_raygen_fwd and mvsnerf_ray_points_fwd); pts = fma(d, z, o) and the NDC coordinates
+ *   exactly as mvsnerf_ray_points_fwd forms them (one device function).
+ * One thread per ray (gather) / per sample (march); no LDS, no atomics; two runs give the same bytes.
+ * MVSNERF_EINVAL: a NULL required pointer (idx with B > 0; jitter with perturb > 0; depth without depth_bank; a reference-camera pointer, W_ref or
+ *   H_ref < 2, or pad < 0 with ndc), a pointer misaligned for its element type (idx 8 bytes, images and every float array 4), M, H, W or S < 1, B < 0,
+ *   a negative or NaN perturb; MVSNERF_EUNSUPPORTED: M H W > INT64_MAX / 8, B (B S for the march) > 2^38.  All before the launch; B == 0 launches nothing. */
+int mvsnerf_scene_rays_gather_fwd(const unsigned char* images_rgba, const float* c2w, const float* K, const float* near_far, const float* depth_bank,
+                                  int M, int H, int W, const int64_t* idx, int64_t B, float* rays, float* rgb, float* depth, unsigned char* mask,
+                                  void* stream);
+int mvsnerf_scene_rays_march_fwd(const unsigned char* images_rgba, const float* c2w, const float* K, const float* near_far, int M, int H, int W,
+                                 const int64_t* idx, int64_t B, const float* t, int S, const float* jitter, float perturb, int lindisp,
+                                 const float* w2c_ref, const float* K_ref, const float* near_far_ref, int W_ref, int H_ref, int pad,
+                                 float* rays, float* rgb, float* z, float* pts, float* ndc, void* stream);
 
 #ifdef __cplusplus
 }

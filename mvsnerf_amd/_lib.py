@@ -284,6 +284,9 @@ SIGNATURES = {
     "mvsnerf_mlp_fwd_wide_counted": (_c_i, [_c_fp, _c_i, _c_i, _c_fp, _c_fp, _c_fp, _c_l, _c_fp, _c_i, _c_fp, _c_fp]),
     "mvsnerf_gather_fwd_counted": (_c_i, [_c_fp] + [_c_i] * 3 + [_c_fp] + [_c_i] * 3 + [_c_fp] * 4 + [_c_l, _c_fp, _c_fp, _c_fp, _c_i, _c_fp, _c_i, _c_fp]),
     "mvsnerf_gather_colorvol_fwd_counted": (_c_i, [_c_fp] + [_c_i] * 4 + [_c_fp, _c_l, _c_fp, _c_fp, _c_fp, _c_fp, _c_i, _c_fp, _c_i, _c_i, _c_fp]),
+    "mvsnerf_scene_rays_gather_fwd": (_c_i, [_c_fp] * 5 + [_c_i] * 3 + [_c_fp, _c_l] + [_c_fp] * 5),
+    "mvsnerf_scene_rays_march_fwd": (_c_i, [_c_fp] * 4 + [_c_i] * 3 + [_c_fp, _c_l, _c_fp, _c_i, _c_fp, ctypes.c_float, _c_i] + [_c_fp] * 3 + [_c_i] * 3
+                                     + [_c_fp] * 6),
 }
 
 _lib = None

@@ -217,21 +217,8 @@ __global__ __launch_bounds__(256) void ray_points_kernel(const float* __restrict
     const float px = ray_point(o[0], d[0], z), py = ray_point(o[1], d[1], z), pz = ray_point(o[2], d[2], z);      // o + d*z (ray_dev.h)
     pts[t * 3 + 0] = px; pts[t * 3 + 1] = py; pts[t * 3 + 2] = pz;
     if (!ndc) return;
-    const float near_ref = nf_ref[0], far_ref = nf_ref[1];
-    const float cx = fmaf(pz, w2c[2], fmaf(py, w2c[1], px * w2c[0])) + w2c[3];
-    const float cy = fmaf(pz, w2c[6], fmaf(py, w2c[5], px * w2c[4])) + w2c[7];
-    const float cz = fmaf(pz, w2c[10], fmaf(py, w2c[9], px * w2c[8])) + w2c[11];
-    const float qx = fmaf(cz, Kr[2], fmaf(cy, Kr[1], cx * Kr[0]));
-    const float qy = fmaf(cz, Kr[5], fmaf(cy, Kr[4], cx * Kr[3]));
-    const float qz = fmaf(cz, Kr[8], fmaf(cy, Kr[7], cx * Kr[6]));
-    float nx = (qx / qz + 0.0f) / (float)(W_ref - 1);
-    float ny = (qy / qz + 0.0f) / (float)(H_ref - 1);
-    const float nz = lindisp ? (1.0f / qz - 1.0f / near_ref) / (1.0f / far_ref - 1.0f / near_ref) : (qz - near_ref) / (far_ref - near_ref);
-    if (pad > 0) {
-        const float Wf = (float)W_ref / 4.0f, Hf = (float)H_ref / 4.0f;               // (inv_scale+1)/4
-        ny = ny * Hf / (Hf + (float)(pad * 2)) + (float)pad / (Hf + (float)(pad * 2));
-        nx = nx * Wf / (Wf + (float)(pad * 2)) + (float)pad / (Wf + (float)(pad * 2));
-    }
+    float nx, ny, nz;
+    ray_ndc(px, py, pz, w2c, Kr, nf_ref[0], nf_ref[1], W_ref, H_ref, pad, lindisp, nx, ny, nz);      // get_ndc_coordinate (ray_dev.h)
     ndc[t * 3 + 0] = nx; ndc[t * 3 + 1] = ny; ndc[t * 3 + 2] = nz;
 }
 

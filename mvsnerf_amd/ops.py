@@ -350,6 +350,78 @@ def ray_march_bbox(rays, bbox_3d, N_samples, lindisp=False, perturb=0.0, jitter=
     return pts, ndc, z
 
 
+def _scene_bank(images, c2ws, intrinsics, near_far, depths, idx, op):
+    """The bank and index pointers of the scene_rays entries (mvsnerf_amd.rays.SceneRays holds the tensors in this form): images (M,H,W,4) uint8,
+    c2ws (M,3,4), intrinsics (M,3,3), near_far (M,2) fp32, depths (M,H,W) fp32 | None, idx (B,) int64; all contiguous on the current device."""
+    if images.dim() != 4 or images.shape[-1] != 4 or images.dtype != torch.uint8 or not images.is_cuda or not images.is_contiguous():
+        raise RuntimeError(f"{op}: images must be a contiguous (M,H,W,4) uint8 tensor on the GPU, got {tuple(images.shape)} {images.dtype} {images.device}")
+    M, H, W = (int(v) for v in images.shape[:3])
+    if tuple(c2ws.shape) != (M, 3, 4) or tuple(intrinsics.shape) != (M, 3, 3) or tuple(near_far.shape) != (M, 2):
+        raise RuntimeError(f"{op}: c2ws ({M},3,4), intrinsics ({M},3,3) and near_far ({M},2) expected, got {tuple(c2ws.shape)}, "
+                           f"{tuple(intrinsics.shape)}, {tuple(near_far.shape)}")
+    if depths is not None and tuple(depths.shape) != (M, H, W):
+        raise RuntimeError(f"{op}: depths must be ({M},{H},{W}), got {tuple(depths.shape)}")
+    if idx.dim() != 1 or idx.dtype != torch.int64 or idx.device != images.device or not idx.is_contiguous():
+        raise RuntimeError(f"{op}: idx must be a contiguous (B,) int64 tensor on {images.device}, got {tuple(idx.shape)} {idx.dtype} {idx.device}")
+    if images.device.index != torch.cuda.current_device():
+        raise RuntimeError(f"{op}: the bank is on {images.device} but the current device is cuda:{torch.cuda.current_device()}")
+    return M, H, W
+
+
+def scene_rays_gather(images, c2ws, intrinsics, near_far, depths, idx, want_depth=False, want_mask=False):
+    """all_rays[idx], all_rgbs[idx] of the all-rays buffer the reference's datasets build (data/dtu_ft.py:143-188, data/blender.py:49-85), formed from the
+    8-bit images and the cameras in one launch: -> (rays (B,8), rgbs (B,3), depth (B,) | None, mask (B,) bool | None).  idx: flat int64 indices into M*H*W,
+    view-major then row-major; an index outside the bank gives zero rows."""
+    _need_no_grad(c2ws, intrinsics, near_far, op="scene_rays_gather")
+    M, H, W = _scene_bank(images, c2ws, intrinsics, near_far, depths, idx, "scene_rays_gather")
+    if want_depth and depths is None:
+        raise RuntimeError("scene_rays_gather: want_depth needs a bank with depths")
+    B, dev = int(idx.shape[0]), images.device
+    c = _Keep()
+    rays, rgb = torch.empty((B, 8), device=dev, dtype=torch.float32), torch.empty((B, 3), device=dev, dtype=torch.float32)
+    depth = torch.empty((B,), device=dev, dtype=torch.float32) if want_depth else None
+    mask = torch.empty((B,), device=dev, dtype=torch.uint8) if want_mask else None
+    if B == 0:                                       # (an empty tensor has no address to hand over)
+        return rays, rgb, depth, None if mask is None else mask.view(torch.bool)
+    check(_lib.lib().mvsnerf_scene_rays_gather_fwd(images.data_ptr(), c(c2ws, "c2ws"), c(intrinsics, "intrinsics"), c(near_far, "near_far"),
+                                                   0 if depths is None else c(depths, "depths"), M, H, W, idx.data_ptr(), B, rays.data_ptr(), rgb.data_ptr(),
+                                                   0 if depth is None else depth.data_ptr(), 0 if mask is None else mask.data_ptr(), stream_ptr()),
+          "scene_rays_gather_fwd")
+    return rays, rgb, depth, None if mask is None else mask.view(torch.bool)
+
+
+def scene_rays_march(images, c2ws, intrinsics, near_far, idx, N_samples, t=None, jitter=None, perturb=0.0, lindisp=False, ref=None):
+    """The front end of a fine-tuning step in one launch: the rows of scene_rays_gather, ray_marcher's depths (data/ray_utils.py:152-197), o + d*z and,
+    with ref = (w2c_ref, K_ref, near_far_ref, (H_ref, W_ref), pad), get_ndc_coordinate -> (rays (B,8), rgbs (B,3), z (B,S), pts (B,S,3), ndc (B,S,3) | None).
+    jitter: the (B,S) uniform draw of :190, required when perturb > 0; t: linspace(0, 1, N_samples) when the caller keeps one."""
+    _need_no_grad(c2ws, intrinsics, near_far, op="scene_rays_march")
+    M, H, W = _scene_bank(images, c2ws, intrinsics, near_far, None, idx, "scene_rays_march")
+    B, S, dev = int(idx.shape[0]), int(N_samples), images.device
+    if perturb > 0 and (jitter is None or tuple(jitter.shape) != (B, S)):
+        raise RuntimeError(f"scene_rays_march: perturb > 0 needs the ({B}, {S}) uniform draw as jitter=")
+    if t is None:
+        t = torch.linspace(0, 1, S, device=dev)
+    if t.numel() != S:
+        raise RuntimeError(f"scene_rays_march: t must hold {S} values")
+    c = _Keep()
+    f32 = dict(device=dev, dtype=torch.float32)
+    rays, rgb, z = torch.empty((B, 8), **f32), torch.empty((B, 3), **f32), torch.empty((B, S), **f32)
+    pts = torch.empty((B, S, 3), **f32)
+    ndc = None if ref is None else torch.empty((B, S, 3), **f32)
+    if B == 0:                                       # (an empty tensor has no address to hand over)
+        return rays, rgb, z, pts, ndc
+    if ref is None:
+        cam = (0, 0, 0, 0, 0, 0)
+    else:
+        w2c_ref, K_ref, nf_ref, ref_hw, pad = ref
+        cam = (c(w2c_ref, "w2c_ref"), c(K_ref, "K_ref"), c(nf_ref.reshape(-1)[:2], "near_far_ref"), int(ref_hw[1]), int(ref_hw[0]), int(pad))
+    check(_lib.lib().mvsnerf_scene_rays_march_fwd(images.data_ptr(), c(c2ws, "c2ws"), c(intrinsics, "intrinsics"), c(near_far, "near_far"), M, H, W,
+                                                  idx.data_ptr(), B, c(t, "t"), S, c(jitter, "jitter") if perturb > 0 else 0, float(perturb),
+                                                  int(bool(lindisp)), *cam, rays.data_ptr(), rgb.data_ptr(), z.data_ptr(), pts.data_ptr(),
+                                                  0 if ndc is None else ndc.data_ptr(), stream_ptr()), "scene_rays_march_fwd")
+    return rays, rgb, z, pts, ndc
+
+
 def sample_pdf(bins, weights, u):
     """data/ray_utils.py:96-139 with the uniform draws supplied: bins (N,nb), weights (N,nb-1), u (N,NI) -> (N,NI)."""
     _need_no_grad(bins, weights, u, op="sample_pdf")

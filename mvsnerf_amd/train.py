@@ -737,6 +737,42 @@ def _sparse_training_render(system, sparse, volume, imgs, w2cs, intrinsics, pts,
     return o["rgb_map"]
 
 
+def _fit_loop(system, steps, optimizer):
+    """The optimisation loop of the per-scene systems, over an iterable of callables that each run one training step and return {'loss'}:
+    step -> backward -> gradient exchange -> Adam; with args.dp_volume_grad == "samples" the volume is re-broadcast from rank 0 every
+    args.dp_volume_resync steps (default 200) so that last-bit differences of the atomics-ordered scatters cannot add up.  Returns the losses."""
+    if optimizer is None:
+        optimizer = system.configure_optimizers()[0][0]
+    if system._allreduce is None:
+        system._allreduce = D.FlatGradAllReduce(system.grad_vars)
+    resync = int(getattr(system.args, "dp_volume_resync", 200))
+    losses = []
+    for step in steps:
+        optimizer.zero_grad(set_to_none=True)
+        out = step()
+        out["loss"].backward()
+        system._allreduce()
+        optimizer.step()
+        system.global_step += 1
+        if getattr(system.args, "dp_volume_grad", "allreduce") == "samples" and resync > 0 and system.global_step % resync == 0 and D._collective_needed():
+            D.broadcast(ops.channels_last_volume(system.volume.feat_volume.data), src=0)     # the (D,H,W,C) view of the same memory
+        losses.append(out["loss"].detach())
+    return [float(l) for l in losses]                                   # one host synchronisation, after the last step is enqueued
+
+
+def _scene_index_batches(scene, n_steps, batch_size, seed):
+    """The index batches of n_steps steps over a rays.SceneRays bank: scene.epoch(batch_size) after scene.epoch, every epoch's permutation drawn
+    from ONE generator on the bank's device seeded with `seed` (the global generators are not touched)."""
+    g = torch.Generator(device=scene.device).manual_seed(int(seed))
+    n_steps, done = int(n_steps), 0
+    while done < n_steps:
+        for idx in scene.epoch(int(batch_size), generator=g):
+            if done == n_steps:
+                return
+            done += 1
+            yield idx
+
+
 class MVSSystemFinetune(_ModuleShim):
     """reference train_mvs_nerf_finetuning_pl.py:32-189: the scene is encoded ONCE (`init_volume`), the 8-channel
     volume becomes a learnable `RefVolume` (checkpoint key `volume.feat_volume`) and only the ray march runs per step;
@@ -866,23 +902,39 @@ class MVSSystemFinetune(_ModuleShim):
         that are live against self.train_density, the renderer-consistent density of the scene dilated by args.skip_empty_dilate voxels (default 1) and
         rebuilt every args.skip_empty_refresh steps (default 200); ops.raymarch_sparse_train, DESIGN.md 4g.  self.last_live_fraction is the step's."""
         args = self.args
-        sparse = _skip_empty_train(args)
-        if sparse is not None:
-            _refresh_train_density(self, sparse, self._render_space_density)
+        self._step_prologue()
         rays, target = batch["rays"].squeeze(0).to(self.imgs.device), batch["rgbs"].squeeze(0).to(self.imgs.device)
-        if getattr(args, "use_density_volume", False) and 0 == self.global_step % 200:              # :144-145
-            self.update_density_volume()
         lindisp = getattr(args, "use_disp", False)
         pts, rays_o, rays_d, z_vals = ray_marcher(rays, N_samples=args.N_samples, lindisp=lindisp, perturb=args.perturb)
-        H, W = self.imgs.shape[-2:]
+        pts, ndc = self._to_ndc(rays_o, rays_d, z_vals)
+        return self._step_body(rays, target, rays_o, rays_d, z_vals, pts, ndc)
 
-        def to_ndc(z):     # o + d*z and get_ndc_coordinate (:150-156) in one kernel
-            return ops.ray_points(rays_o, rays_d, z, self.pose_source["w2cs"][0], self.pose_source["intrinsics"][0], self.near_far_source,
-                                  ref_hw=(H, W), pad=args.pad, lindisp=lindisp)
-        pts, ndc = to_ndc(z_vals)
+    def _step_prologue(self):
+        """What a step does before it forms its rays: the training density of args.skip_empty_train and the density volume of :144-145."""
+        sparse = _skip_empty_train(self.args)
+        if sparse is not None:
+            _refresh_train_density(self, sparse, self._render_space_density)
+        if getattr(self.args, "use_density_volume", False) and 0 == self.global_step % 200:         # :144-145
+            self.update_density_volume()
+
+    def _ref_camera(self):
+        """The reference camera of get_ndc_coordinate (:150-156) in the form ops.scene_rays_march takes: (w2c, K, near_far, (H, W), pad)."""
+        H, W = self.imgs.shape[-2:]
+        return self.pose_source["w2cs"][0], self.pose_source["intrinsics"][0], self.near_far_source, (H, W), self.args.pad
+
+    def _to_ndc(self, rays_o, rays_d, z):
+        """o + d*z and get_ndc_coordinate (:150-156) in one kernel."""
+        w2c, K, nf, hw, pad = self._ref_camera()
+        return ops.ray_points(rays_o, rays_d, z, w2c, K, nf, ref_hw=hw, pad=pad, lindisp=getattr(self.args, "use_disp", False))
+
+    def _step_body(self, rays, target, rays_o, rays_d, z_vals, pts, ndc):
+        """A step behind ray_marcher / get_ndc_coordinate (:158-189), shared by training_step (rays from the batch) and fit_scene (rays, depths, points
+        and NDC coordinates from one ops.scene_rays_march launch): importance sampling, the render, the loss."""
+        args = self.args
+        sparse = _skip_empty_train(args)
         if self.density_volume is not None and getattr(args, "N_importance", 0) > 0:                # :158-163
             pts, rays_o, rays_d, z_vals = ray_marcher_fine(rays, self.density_volume, z_vals, ndc, N_importance=args.N_importance)
-            pts, ndc = to_ndc(z_vals)
+            pts, ndc = self._to_ndc(rays_o, rays_d, z_vals)
         with ops.mlp_precision("bf16" if getattr(args, "use_amp", False) else ops.MLP_PRECISION):
             if sparse is not None:
                 V = self.imgs.shape[1]
@@ -1044,23 +1096,26 @@ class MVSSystemFinetune(_ModuleShim):
     def fit_steps(self, batches, optimizer=None):
         """training_step -> backward -> gradient exchange -> Adam; with args.dp_volume_grad == "samples" the volume is re-broadcast from
         rank 0 every args.dp_volume_resync steps (default 200) so that last-bit differences of the atomics-ordered scatters cannot add up."""
-        if optimizer is None:
-            optimizer = self.configure_optimizers()[0][0]
-        if self._allreduce is None:
-            self._allreduce = D.FlatGradAllReduce(self.grad_vars)
-        resync = int(getattr(self.args, "dp_volume_resync", 200))
-        losses = []
-        for i, batch in enumerate(batches):
-            optimizer.zero_grad(set_to_none=True)
-            out = self.training_step(batch, i)
-            out["loss"].backward()
-            self._allreduce()
-            optimizer.step()
-            self.global_step += 1
-            if self.args.dp_volume_grad == "samples" and resync > 0 and self.global_step % resync == 0 and D._collective_needed():
-                D.broadcast(ops.channels_last_volume(self.volume.feat_volume.data), src=0)     # the (D,H,W,C) view of the same memory
-            losses.append(out["loss"].detach())
-        return [float(l) for l in losses]                                   # one host synchronisation, after the last step is enqueued
+        return _fit_loop(self, ((lambda batch=batch, i=i: self.training_step(batch, i)) for i, batch in enumerate(batches)), optimizer)
+
+    def fit_scene(self, scene, n_steps, batch_size=None, seed=0, optimizer=None):
+        """fit_steps fed by a rays.SceneRays bank instead of batches: n_steps steps over the index batches of scene.epoch(batch_size) (default
+        args.batch_size; a new epoch starts when one is exhausted) shuffled by a generator seeded with `seed`.  Each step is ONE
+        ops.scene_rays_march launch - rays, target colours, stratified depths, points and their NDC coordinates in the reference camera - and then
+        the body of training_step; with args.perturb > 0 a step draws torch.rand((B, S)) from the global device generator, the one draw
+        ray_marcher makes.  The step of training_step on {'rays', 'rgbs'} = scene.gather(idx) computes the same bits.  Returns the
+        losses; one host synchronisation, after the last step is enqueued."""
+        args = self.args
+        S, lindisp, ref = int(args.N_samples), getattr(args, "use_disp", False), self._ref_camera()
+
+        def step(idx):
+            self._step_prologue()
+            jitter = torch.rand((idx.shape[0], S), device=idx.device) if args.perturb > 0 else None
+            m = scene.march(idx, S, perturb=args.perturb, jitter=jitter, lindisp=lindisp, ref=ref)
+            rays = m["rays"]
+            return self._step_body(rays, m["rgbs"], rays[:, 0:3], rays[:, 3:6], m["z_vals"], m["pts"], m["ndc"])
+        batches = _scene_index_batches(scene, n_steps, batch_size or args.batch_size, seed)
+        return _fit_loop(self, ((lambda idx=idx: step(idx)) for idx in batches), optimizer)
 
     def configure_optimizers(self):
         self.optimizer = _adam(self.grad_vars, self.args.lrate)
@@ -1250,6 +1305,17 @@ class MVSSystemFusion(_ModuleShim):
             self.log("train/img_mse_loss", img_loss)
             self.log("train/PSNR", mse2psnr2(img_loss), prog_bar=True)
         return {"loss": img_loss}
+
+    def fit_scene(self, scene, n_steps, batch_size=None, seed=0, optimizer=None):
+        """MVSSystemFinetune.fit_scene for the fused scene: every step gathers its rays and colours from the rays.SceneRays bank (ops.scene_rays_gather,
+        one launch) and runs training_step on them - the march against the box stays ops.ray_march_bbox.  Returns the losses."""
+        self._need_volume()
+        batches = _scene_index_batches(scene, n_steps, batch_size or self.args.batch_size, seed)
+
+        def step(i, idx):
+            rays, rgbs = scene.gather(idx)
+            return self.training_step({"rays": rays[None], "rgbs": rgbs[None]}, i)
+        return _fit_loop(self, ((lambda i=i, idx=idx: step(i, idx)) for i, idx in enumerate(batches)), optimizer)
 
     # -- rendering the fused scene -----------------------------------------------------------------
     @torch.no_grad()
