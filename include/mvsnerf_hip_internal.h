@@ -508,6 +508,33 @@ int mvsnerf_scene_rays_march_fwd(const unsigned char* images_rgba, const float* 
                                  const int64_t* idx, int64_t B, const float* t, int S, const float* jitter, float perturb, int lindisp,
                                  const float* w2c_ref, const float* K_ref, const float* near_far_ref, int W_ref, int H_ref, int pad,
                                  float* rays, float* rgb, float* z, float* pts, float* ndc, void* stream);
+/* source_images: the source views of read_source_views (data/dtu_ft.py:72-119) from the bank: out [V][3][H][W] fp32 for ids [V] int64 (device).  Per
+ *   channel c / 255 and a / 255 (IEEE divisions), rgb a + (1 - a) in three roundings (the colour of the training rays above, one device function), then
+ *   T.Normalize's sub_(mean).div_(std): (x - mean[k]) / std[k], an IEEE subtraction and division.  mean, std: HOST float[3], read before the launch.  An id
+ *   outside [0, M) gives zeros and reads nothing.  MVSNERF_EINVAL: a NULL pointer, V, M, H or W < 1; MVSNERF_EALIGN: images_rgba or out not 4-byte,
+ *   ids not 8-byte aligned; MVSNERF_EUNSUPPORTED: H W > 2^31 - 1 or 3 V H W > 2^38. */
+int mvsnerf_source_images_fwd(const unsigned char* images_rgba, const int64_t* ids, int V, int M, int H, int W, const float* mean, const float* std,
+                              float* out, void* stream);
+/* ---- Pillow's 8-bit resampler on the bank's images: Image.resize(size, LANCZOS | BILINEAR) of the reference's per-scene datasets (data/dtu_ft.py:108,
+ *      data/blender.py:66, data/llff.py:241; data/dtu.py:160), byte for byte, without box= and reducing_gap= (csrc/resample.hip) ----
+ * src [M][Hin][Win][4], dst [M][Hout][Wout][4] uint8.  The horizontal pass runs first, over all input rows and only if Win != Wout, into workspace when a
+ *   vertical pass (only if Hin != Hout) follows; equal sizes give a copy.  (Pillow 12's Image.resize runs the vertical pass first for an image more than
+ *   100 times as tall as wide whose height shrinks; this entry does not.)
+ * Tables per axis, int32, built by the caller (mvsnerf_amd/ops.py _resample_tables; tests/resample_refs.py tables): win [n_out][2] = (xmin, n) and
+ *   kk [n_out][ks], Pillow's precompute_coeffs and normalize_coeffs_8bpc (PRECISION_BITS 22).  A pass computes per channel
+ *   clamp((2^21 + sum_{x < n} src[xmin + x] kk[x]) >> 22, 0, 255) in int32.  The tables of an axis whose size does not change are not read (NULL, 0).
+ *   Every thread checks its own window before any load: xmin >= 0, 0 <= n <= ks, xmin + n <= n_in; a bad window gives an all-zero pixel and reads nothing
+ *   (when a vertical pass follows, it resamples the zero pixels a bad horizontal window left in the workspace: zeros again, alpha 255 in alpha_mode 0).
+ * alpha_mode 0 (an RGB image): three channels are resampled and dst's alpha byte is written as 255 (also by the copy).
+ * alpha_mode 1 (an image with alpha): Pillow resamples premultiplied bytes (RGBA -> RGBa -> RGBA): the first pass loads c' = ((t >> 8) + t) >> 8 with
+ *   t = c a + 128, all four channels are resampled, and the last pass stores c' when the resampled a is 0 or 255, else min(255 c' / a, 255).  The copy copies.
+ * workspace_bytes: M Hin Wout 4 when both passes run, else 0 (also for sizes the entry refuses).
+ * MVSNERF_EINVAL: NULL src or dst, a size < 1, an alpha_mode other than 0 / 1, a NULL table or ks < 1 for an axis that changes, a NULL workspace when both
+ *   passes run; MVSNERF_EALIGN: src, dst, workspace or a table not 4-byte aligned; MVSNERF_EUNSUPPORTED: Hin Win, Hin Wout or Hout Wout > 2^31 - 1, any of
+ *   them times M > 2^38 (a pass is one 256-thread workgroup per 256 pixels), ks > 65535.  All before the first launch. */
+size_t mvsnerf_resample_u8_workspace_bytes(int M, int Hin, int Win, int Hout, int Wout);
+int mvsnerf_resample_u8_fwd(const unsigned char* src, int M, int Hin, int Win, unsigned char* dst, int Hout, int Wout, const int* xwin, const int* xkk,
+                            int xks, const int* ywin, const int* ykk, int yks, int alpha_mode, void* workspace, void* stream);
 
 #ifdef __cplusplus
 }

@@ -287,6 +287,9 @@ SIGNATURES = {
     "mvsnerf_scene_rays_gather_fwd": (_c_i, [_c_fp] * 5 + [_c_i] * 3 + [_c_fp, _c_l] + [_c_fp] * 5),
     "mvsnerf_scene_rays_march_fwd": (_c_i, [_c_fp] * 4 + [_c_i] * 3 + [_c_fp, _c_l, _c_fp, _c_i, _c_fp, ctypes.c_float, _c_i] + [_c_fp] * 3 + [_c_i] * 3
                                      + [_c_fp] * 6),
+    "mvsnerf_source_images_fwd": (_c_i, [_c_fp, _c_fp] + [_c_i] * 4 + [ctypes.POINTER(ctypes.c_float)] * 2 + [_c_fp, _c_fp]),
+    "mvsnerf_resample_u8_workspace_bytes": (ctypes.c_size_t, [_c_i] * 5),
+    "mvsnerf_resample_u8_fwd": (_c_i, [_c_fp] + [_c_i] * 3 + [_c_fp, _c_i, _c_i, _c_fp, _c_fp, _c_i, _c_fp, _c_fp, _c_i, _c_i, _c_fp, _c_fp]),
 }
 
 _lib = None

@@ -4,6 +4,7 @@
 //   scene_rays_gather   idx[B] -> rays[B][8], rgb[B][3] (+ depth[B], mask[B]): all_rays[idx], all_rgbs[idx]
 //   scene_rays_march    idx[B] -> the same rows and the front end of a fine-tuning step: ray_marcher's depths (data/ray_utils.py:152-197), o + d*z and
 //                       get_ndc_coordinate (utils.py:112-146) in one launch
+//   source_images       ids[V] -> imgs[V][3][H][W]: the normalised source views of read_source_views
 // Bank: images [M][H][W][4] uint8 RGBA (a ray's colour is one 32-bit load), c2w [M][3][4], K [M][3][3], near_far [M][2], depth [M][H][W] or NULL.
 // Every operation is rounded on its own, as eager torch on the CPU rounds it (tests/scene_rays_refs.py is the elementwise restatement); an index outside
 // [0, M*H*W) reads nothing and gives an all-zero row in every output.  Both kernels are bandwidth-bound: no LDS, no atomics.
@@ -132,6 +133,33 @@ __global__ __launch_bounds__(256) void scene_rays_march_kernel(SceneBank b, cons
     ndc[t * 3 + 0] = nx; ndc[t * 3 + 1] = ny; ndc[t * 3 + 2] = nz;
 }
 
+// The source views of read_source_views (data/dtu_ft.py:72-119, data/blender.py:91-146) from the bank: ToTensor, the blend onto white, then
+// T.Normalize's sub_(mean).div_(std), each an fp32 operation rounded on its own.  One thread per element of out [V][3][H][W], t = (v * 3 + k) * HW + px:
+// a wave stores 256 contiguous bytes and the three threads of a pixel read its four bytes again (cached).  One channel per thread also leaves the compiler
+// no pair of channels to pack into a v_pk_*_f32 (check_isa.sh refuses the form it chose for three per thread).  An id outside [0, M) reads nothing and
+// gives zeros.
+struct Norm3 { float mean[3], std[3]; };
+
+__global__ __launch_bounds__(256) void source_images_kernel(SceneBank b, const int64_t* __restrict__ ids, int64_t total, int64_t HW, Norm3 nrm,
+                                                            float* __restrict__ out)
+{
+#pragma clang fp contract(off)
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= total) return;
+    const int64_t plane = t / HW, px = t - plane * HW, v = plane / 3;
+    const int k = (int)(plane - v * 3);
+    const int64_t id = ids[v];
+    float x = 0.0f;
+    if ((uint64_t)id < (uint64_t)b.M) {
+        float c[3];
+        scene_ray_colour(b, id * HW + px, c);                                           // the colour of the training rays: one device function
+        const float ck = k == 0 ? c[0] : (k == 1 ? c[1] : c[2]);
+        const float mean = k == 0 ? nrm.mean[0] : (k == 1 ? nrm.mean[1] : nrm.mean[2]), std = k == 0 ? nrm.std[0] : (k == 1 ? nrm.std[1] : nrm.std[2]);
+        x = (ck - mean) / std;
+    }
+    out[t] = x;
+}
+
 static inline bool aligned_to(const void* p, unsigned a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 // The bank and the index batch: NULL or misaligned pointers and sizes < 1 are MVSNERF_EINVAL, a bank beyond INT64_MAX / 8 rays MVSNERF_EUNSUPPORTED
@@ -179,6 +207,20 @@ extern "C" int mvsnerf_scene_rays_march_fwd(const unsigned char* images_rgba, co
     scene_rays_march_kernel<<<mvs_cdiv(B * S, 256), 256, 0, (hipStream_t)stream>>>(b, idx, B, t, S, jitter, perturb > 0.0f ? perturb : 0.0f, lindisp,
                                                                                   ndc ? w2c_ref : nullptr, K_ref, near_far_ref, W_ref, H_ref, pad, rays, rgb, z,
                                                                                   pts, ndc);
+    MVS_LAUNCH_CHECK();
+    return MVSNERF_OK;
+}
+
+extern "C" int mvsnerf_source_images_fwd(const unsigned char* images_rgba, const int64_t* ids, int V, int M, int H, int W, const float* mean, const float* std,
+                                         float* out, void* stream)
+{
+    if (!images_rgba || !ids || !mean || !std || !out || V < 1 || M < 1 || H < 1 || W < 1) return MVSNERF_EINVAL;
+    if (!aligned_to(images_rgba, 4) || !aligned_to(ids, 8) || !aligned_to(out, 4)) return MVSNERF_EALIGN;
+    const int64_t HW = (int64_t)H * W;
+    if (HW > 0x7fffffff || HW > ((int64_t)1 << 38) / 3 / V) return MVSNERF_EUNSUPPORTED;    // 3 V H W / 256 workgroups must fit the grid
+    const Norm3 nrm{{mean[0], mean[1], mean[2]}, {std[0], std[1], std[2]}};             // host arrays, read here
+    const SceneBank b{images_rgba, nullptr, nullptr, nullptr, nullptr, M, H, W, M * HW};
+    source_images_kernel<<<mvs_cdiv(3 * V * HW, 256), 256, 0, (hipStream_t)stream>>>(b, ids, 3 * V * HW, HW, nrm, out);
     MVS_LAUNCH_CHECK();
     return MVSNERF_OK;
 }

@@ -422,6 +422,117 @@ def scene_rays_march(images, c2ws, intrinsics, near_far, idx, N_samples, t=None,
     return rays, rgb, z, pts, ndc
 
 
+def source_images(images, ids, mean, std):
+    """The `imgs` of read_source_views (data/dtu_ft.py:72-119) from the bank in one launch: images (M,H,W,4) uint8, ids (V,) int64 on the bank's device ->
+    (V,3,H,W) fp32 = T.Normalize(mean, std)(ToTensor, blended onto white); an id outside [0, M) gives zeros."""
+    if images.dim() != 4 or images.shape[-1] != 4 or images.dtype != torch.uint8 or not images.is_cuda or not images.is_contiguous():
+        raise RuntimeError(f"source_images: images must be a contiguous (M,H,W,4) uint8 tensor on the GPU, got {tuple(images.shape)} {images.dtype} {images.device}")
+    if ids.dim() != 1 or ids.dtype != torch.int64 or ids.device != images.device or not ids.is_contiguous() or ids.shape[0] < 1:
+        raise RuntimeError(f"source_images: ids must be a contiguous (V,) int64 tensor on {images.device}, V >= 1, got {tuple(ids.shape)} {ids.dtype} {ids.device}")
+    if images.device.index != torch.cuda.current_device():
+        raise RuntimeError(f"source_images: the bank is on {images.device} but the current device is cuda:{torch.cuda.current_device()}")
+    M, H, W = (int(v) for v in images.shape[:3])
+    V = int(ids.shape[0])
+    f3 = ctypes.c_float * 3
+    out = torch.empty((V, 3, H, W), device=images.device, dtype=torch.float32)
+    check(_lib.lib().mvsnerf_source_images_fwd(images.data_ptr(), ids.data_ptr(), V, M, H, W, f3(*[float(v) for v in mean]), f3(*[float(v) for v in std]),
+                                               out.data_ptr(), stream_ptr()), "source_images_fwd")
+    return out
+
+
+RESAMPLE_SUPPORT = {"lanczos": 3.0, "bilinear": 1.0}
+_resample_cache = {}
+
+
+def _resample_filter(name, x):
+    import math
+    if name == "lanczos":                              # Pillow's lanczos_filter: a truncated sinc, sinc(x) sinc(x / 3) on [-3, 3)
+        if -3.0 <= x < 3.0:
+            a, b = x * math.pi, x / 3 * math.pi
+            return (1.0 if a == 0.0 else math.sin(a) / a) * (1.0 if b == 0.0 else math.sin(b) / b)
+        return 0.0
+    x = abs(x)                                         # bilinear_filter
+    return 1.0 - x if x < 1.0 else 0.0
+
+
+def _resample_tables(n_in, n_out, resample):
+    """Pillow's precompute_coeffs + normalize_coeffs_8bpc (src/libImaging/Resample.c) for one axis, in float64 on the host:
+    -> (win (n_out,2) int32 = (xmin, n), kk (n_out,ksize) int32, ksize) as numpy arrays; cached per (n_in, n_out, resample)."""
+    key = (int(n_in), int(n_out), resample)
+    if key in _resample_cache:
+        return _resample_cache[key]
+    import math
+    import numpy as np
+    n_in, n_out = key[:2]
+    scale = n_in / n_out
+    fs = max(scale, 1.0)
+    support = RESAMPLE_SUPPORT[resample] * fs
+    ksize = int(math.ceil(support)) * 2 + 1
+    ss = 1.0 / fs
+    win, kk = np.zeros((n_out, 2), dtype=np.int32), np.zeros((n_out, ksize), dtype=np.int32)
+    for xx in range(n_out):
+        center = (xx + 0.5) * scale
+        xmin = max(int(center - support + 0.5), 0)
+        n = min(int(center + support + 0.5), n_in) - xmin
+        w = [_resample_filter(resample, (x + xmin - center + 0.5) * ss) for x in range(n)]
+        ww = 0.0
+        for v in w:                                    # left to right, as Pillow sums
+            ww += v
+        if ww != 0.0:
+            w = [v / ww for v in w]
+        win[xx] = xmin, n
+        kk[xx, :n] = [int(v * 4194304.0 - 0.5) if v < 0 else int(v * 4194304.0 + 0.5) for v in w]       # 2^22, truncation towards zero
+    if len(_resample_cache) >= 64:
+        _resample_cache.clear()
+    _resample_cache[key] = (win, kk, ksize)
+    return _resample_cache[key]
+
+
+_resample_dev_cache = {}
+
+
+def _resample_tables_dev(n_in, n_out, resample, device):
+    """The tables of _resample_tables as int32 device tensors, cached per (n_in, n_out, resample, device): the pattern of _mlp_bwd_maps."""
+    key = (int(n_in), int(n_out), resample, str(device))
+    if key not in _resample_dev_cache:
+        win, kk, ksize = _resample_tables(n_in, n_out, resample)
+        if len(_resample_dev_cache) >= 64:
+            _resample_dev_cache.clear()
+        _resample_dev_cache[key] = (torch.from_numpy(win).to(device), torch.from_numpy(kk).to(device), ksize)
+    return _resample_dev_cache[key]
+
+
+def resample_u8(src, size_hw, resample="lanczos", premultiply=False, out=None):
+    """`Image.resize((W', H'), LANCZOS | BILINEAR)` of Pillow on 8-bit images in the bank's layout, byte for byte (csrc/resample.hip):
+    src (M,H,W,4) uint8 on the GPU -> (M,H',W',4).  premultiply=False: an RGB image; three channels are resampled and the alpha byte of the result is 255.
+    premultiply=True: an image with alpha; resampled premultiplied and divided by the new alpha again, as Pillow resizes mode RGBA.  out: a contiguous
+    (M,H',W',4) uint8 tensor to write into (a view's slot of a bank)."""
+    if resample not in RESAMPLE_SUPPORT:
+        raise ValueError(f"resample_u8: resample must be one of {sorted(RESAMPLE_SUPPORT)}, got {resample!r}")
+    if not torch.is_tensor(src) or src.dim() != 4 or src.shape[-1] != 4 or src.dtype != torch.uint8 or not src.is_cuda or not src.is_contiguous():
+        raise RuntimeError(f"resample_u8: src must be a contiguous (M,H,W,4) uint8 tensor on the GPU, got {tuple(getattr(src, 'shape', ()))} "
+                           f"{getattr(src, 'dtype', None)} {getattr(src, 'device', None)}")
+    M, H, W = (int(v) for v in src.shape[:3])
+    Ho, Wo = (int(v) for v in size_hw)
+    if min(M, H, W) < 1 or min(Ho, Wo) < 1:
+        raise ValueError(f"resample_u8: empty images or target, {tuple(src.shape)} -> {(Ho, Wo)}")
+    if src.device.index != torch.cuda.current_device():
+        raise RuntimeError(f"resample_u8: src is on {src.device} but the current device is cuda:{torch.cuda.current_device()}")
+    if out is None:
+        out = torch.empty((M, Ho, Wo, 4), device=src.device, dtype=torch.uint8)
+    elif tuple(out.shape) != (M, Ho, Wo, 4) or out.dtype != torch.uint8 or out.device != src.device or not out.is_contiguous():
+        raise RuntimeError(f"resample_u8: out must be a contiguous ({M},{Ho},{Wo},4) uint8 tensor on {src.device}, got {tuple(out.shape)} {out.dtype} {out.device}")
+    xw, xk, xks = _resample_tables_dev(W, Wo, resample, src.device) if Wo != W else (None, None, 0)
+    yw, yk, yks = _resample_tables_dev(H, Ho, resample, src.device) if Ho != H else (None, None, 0)
+    lib = _lib.lib()
+    nbytes = lib.mvsnerf_resample_u8_workspace_bytes(M, H, W, Ho, Wo)
+    work = torch.empty((nbytes,), device=src.device, dtype=torch.uint8) if nbytes else None
+    p = lambda t: 0 if t is None else t.data_ptr()
+    check(lib.mvsnerf_resample_u8_fwd(src.data_ptr(), M, H, W, out.data_ptr(), Ho, Wo, p(xw), p(xk), xks, p(yw), p(yk), yks, int(bool(premultiply)),
+                                      p(work), stream_ptr()), "resample_u8_fwd")
+    return out
+
+
 def sample_pdf(bins, weights, u):
     """data/ray_utils.py:96-139 with the uniform draws supplied: bins (N,nb), weights (N,nb-1), u (N,NI) -> (N,NI)."""
     _need_no_grad(bins, weights, u, op="sample_pdf")

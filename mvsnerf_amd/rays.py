@@ -32,6 +32,14 @@ class SceneRays:
         M, H, W = (int(v) for v in images.shape[:3])
         if min(M, H, W) < 1:
             raise ValueError(f"SceneRays: an empty bank, images {tuple(images.shape)}")
+        self._init_cameras(M, H, W, c2ws, intrinsics, near_far, depths, device)
+        self.has_alpha = images.shape[-1] == 4
+        if not self.has_alpha:
+            images = torch.cat((images, torch.full((M, H, W, 1), 255, dtype=torch.uint8, device=images.device)), -1)
+        self.images = images.to(self.device).contiguous()
+
+    def _init_cameras(self, M, H, W, c2ws, intrinsics, near_far, depths, device):
+        """Everything of the bank but its images, for M views of H x W pixels."""
         c2w64 = torch.as_tensor(c2ws).to("cpu", torch.float64)
         if c2w64.dim() != 3 or c2w64.shape[0] != M or tuple(c2w64.shape[1:]) not in ((4, 4), (3, 4)):
             raise ValueError(f"SceneRays: c2ws must be ({M},4,4) or ({M},3,4) for {M} images, got {tuple(c2w64.shape)}")
@@ -53,16 +61,52 @@ class SceneRays:
                 raise ValueError(f"SceneRays: depths must be ({M},{H},{W}), got {tuple(depths.shape)}")
         self.device = torch.device(device)
         self.n_views, self.hw, self.n_rays = M, (H, W), M * H * W
-        self.has_alpha = images.shape[-1] == 4
-        if not self.has_alpha:
-            images = torch.cat((images, torch.full((M, H, W, 1), 255, dtype=torch.uint8, device=images.device)), -1)
-        self.images = images.to(self.device).contiguous()
         self._c2w64, self._K64 = c2w64.contiguous(), K64.contiguous()                   # the host's cameras, for source_views
         self.c2ws = c2w64[:, :3, :4].to(torch.float32).to(self.device).contiguous()
         self.intrinsics = K64.to(torch.float32).to(self.device).contiguous()
         self.near_far = nf.to(self.device).contiguous()
         self.depths = None if depths is None else depths.to(self.device, torch.float32).contiguous()
         self._t = {}
+
+    @classmethod
+    def from_images(cls, images, c2ws, intrinsics, near_far, img_wh, resample="lanczos", depths=None, device="cuda"):
+        """The bank from the scene's images at the size they were decoded at: `np.asarray(Image.open(p))` of every view, resized on the device to
+        img_wh = (W, H) exactly as `Image.resize(img_wh, Image.LANCZOS)` of Pillow resizes them (data/dtu_ft.py:163, data/blender.py:66,
+        data/llff.py:344; resample="bilinear": Image.BILINEAR, data/dtu.py:160) - the same bytes as SceneRays(<the Pillow-resized images>, ...).
+            images      (M,Hin,Win,3|4) uint8, or a sequence of (H_i,W_i,3|4) uint8 arrays whose sizes may differ (one channel count for all)
+            intrinsics, depths    those of the RESIZED images, as the reference's datasets hold them after their own scaling
+        One image at a time: upload, resize into that view's slot of the bank (ops.resample_u8); the device holds the bank, one source image
+        (briefly also its three-channel form) and the horizontal pass's output.  RGBA is resampled premultiplied, as Pillow resizes mode RGBA.
+        Refused: an image more than 100 times as tall as wide whose height shrinks (Pillow 12 runs the vertical pass first for those)."""
+        if resample not in ops.RESAMPLE_SUPPORT:
+            raise ValueError(f"SceneRays.from_images: resample must be one of {sorted(ops.RESAMPLE_SUPPORT)}, got {resample!r}")
+        W, H = (int(v) for v in img_wh)
+        if min(W, H) < 1:
+            raise ValueError(f"SceneRays.from_images: img_wh must be (W, H) >= 1, got {tuple(img_wh)}")
+        views = [torch.as_tensor(v) for v in images]                                    # (a 4-D array iterates over its views)
+        if not views:
+            raise ValueError("SceneRays.from_images: no images")
+        for v in views:
+            if v.dtype != torch.uint8:
+                raise TypeError(f"SceneRays.from_images: images must be uint8, as decoded from the scene's 8-bit files, got {v.dtype} "
+                                "(a float image would be quantised silently)")
+            if v.dim() != 3 or v.shape[-1] not in (3, 4) or v.shape[-1] != views[0].shape[-1] or min(v.shape[:2]) < 1:
+                raise ValueError(f"SceneRays.from_images: every image must be (H,W,3) or (H,W,4) with one channel count, got {tuple(v.shape)}")
+            if v.shape[0] > 100 * v.shape[1] and H < v.shape[0]:
+                raise ValueError(f"SceneRays.from_images: a {v.shape[0]} x {v.shape[1]} image (more than 100 times as tall as wide) made lower: "
+                                 "Pillow 12 resizes such an image vertically first, the device resampler does not")
+        self = cls.__new__(cls)
+        M = len(views)
+        self._init_cameras(M, H, W, c2ws, intrinsics, near_far, depths, device)
+        self.has_alpha = views[0].shape[-1] == 4
+        self.images = torch.empty((M, H, W, 4), dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            for m, v in enumerate(views):
+                src = v.to(self.device)
+                if not self.has_alpha:
+                    src = torch.nn.functional.pad(src, (0, 1), value=255)
+                ops.resample_u8(src.contiguous()[None], (H, W), resample=resample, premultiply=self.has_alpha, out=self.images[m:m + 1])
+        return self
 
     def _bank(self):
         return self.images, self.c2ws, self.intrinsics, self.near_far
@@ -108,11 +152,13 @@ class SceneRays:
         for i in range(0, self.n_rays, B):
             yield perm[i:i + B]
 
-    def source_views(self, ids):
+    def source_views(self, ids, on_device=False):
         """read_source_views (data/dtu_ft.py:72-119) for the views `ids`, the first being the reference view: (imgs (1,V,3,H,W) ImageNet-normalised,
         proj_mats (1,V,3,4), near_far (2,), pose_source {'c2ws', 'w2cs' (V,4,4), 'intrinsics' (V,3,3) full resolution}) - what the systems' constructors
         take.  proj = (K/4 [R|t])_v (K/4 [R|t])_ids[0]^-1, rows 0:3, the identity for the first id; float64 on the host, rounded once.  near_far is
-        that of ids[-1] (:88 leaves the last one read).  RGBA images are blended onto white (data/blender.py:135)."""
+        that of ids[-1] (:88 leaves the last one read).  RGBA images are blended onto white (data/blender.py:135).  on_device=True: imgs is formed on
+        the bank's device in one launch (ops.source_images) and stays there, the same bits; the default pulls the views' bytes to the host and forms it
+        there."""
         ids = [int(i) for i in ids]
         if not ids or min(ids) < 0 or max(ids) >= self.n_views:
             raise IndexError(f"SceneRays.source_views: ids {ids} of {self.n_views} views")
@@ -131,10 +177,14 @@ class SceneRays:
             else:
                 projs.append(P @ ref_inv)
         f32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))
-        px = self.images[torch.as_tensor(ids, device=self.device)].cpu().to(torch.float32).div(255)          # ToTensor
-        rgb = px[..., :3] * px[..., 3:] + (1 - px[..., 3:])                              # blend A to RGB
-        rgb = rgb.permute(0, 3, 1, 2).contiguous()
-        mean, std = torch.tensor(IMAGENET_MEAN).view(1, 3, 1, 1), torch.tensor(IMAGENET_STD).view(1, 3, 1, 1)
-        imgs = rgb.sub_(mean).div_(std).unsqueeze(0)                                     # T.Normalize
+        if on_device:
+            with torch.cuda.device(self.device):
+                imgs = ops.source_images(self.images, torch.as_tensor(ids, device=self.device), IMAGENET_MEAN, IMAGENET_STD).unsqueeze(0)
+        else:
+            px = self.images[torch.as_tensor(ids, device=self.device)].cpu().to(torch.float32).div(255)      # ToTensor
+            rgb = px[..., :3] * px[..., 3:] + (1 - px[..., 3:])                          # blend A to RGB
+            rgb = rgb.permute(0, 3, 1, 2).contiguous()
+            mean, std = torch.tensor(IMAGENET_MEAN).view(1, 3, 1, 1), torch.tensor(IMAGENET_STD).view(1, 3, 1, 1)
+            imgs = rgb.sub_(mean).div_(std).unsqueeze(0)                                 # T.Normalize
         pose = {"c2ws": f32(c2w), "w2cs": f32(w2c), "intrinsics": f32(K)}
         return imgs, f32(np.stack(projs)[:, :3]).unsqueeze(0), self.near_far[ids[-1]].cpu().clone(), pose
