@@ -71,8 +71,10 @@ __device__ __forceinline__ float pe_sc(PeArg a, int f, int want_cos)
     return __builtin_amdgcn_sinf(want_cos ? 0.25f - __builtin_fabsf(r) : r);
 }
 
-// the polynomial routine of mlp.hip (rounds 1-5): what the bf16 kernels keep (their parity test pins them to a torch emulation of bf16 rounding within 2e-3,
-// and one rounding boundary crossed by a 1e-7 difference in an input moves an output by more)
+// the polynomial routine of mlp.hip (rounds 1-5).  Only the split kernels keep it: mlp_fwd_split_kernel<NS> (mlp_bf16.hip, n_split 1 / 2 / 3) encodes with pe_op().
+// The plain bf16 kernels - mlp_fwd_bf16_pair_kernel and the training forward mlp_fwd_bf16_kernel - and mlp_f16x3.hip encode with pe_op_hw(), the transcendental
+// unit above (which is why the bf16 parity test, tests/test_gpu_raymarch.py::test_bf16_mlp_mode, bounds a quantile: one rounding boundary crossed by a 1e-7
+// difference in an input moves an output by more than 2e-3)
 __device__ __forceinline__ float pe_sc_poly(float x, int want_cos)
 {
     x = fminf(fmaxf(x, -65536.0f), 65536.0f);
