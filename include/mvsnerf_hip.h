@@ -311,7 +311,7 @@ int mvsnerf_mlp_fwd_bf16(const void* packed_bf16, const float* packed_f32, int F
  *                       bias gradients and reductions fp32; gradients are returned in fp32 (fp32 master weights, fp32 all-reduce).
  *                       `saved` must come from mvsnerf_mlp_fwd_bf16_train (bf16 slots); `gslots` holds bf16 slots as well
  *                       (mvsnerf_mlp_gradslot_floats(N*S) / 2 floats).  As with autocast, what is kept for the backward pass is 16-bit.
- *   F as for the fp32 training entries below: even, 2 <= F <= 40. */
+ *   F as for the fp32 training entries below: even, 2 <= F <= 40 (the backward: 4 <= F <= 40). */
 int mvsnerf_mlp_fwd_bf16_train(const void* packed_bf16, const float* packed_f32, int F, const float* ndc, int ndc_stride,
                                const float* feat, int feat_stride, const float* dirs, int dirs_stride,
                                int64_t N, int S, float* raw, float* saved, void* stream);
@@ -332,8 +332,11 @@ int mvsnerf_mlp_bwd_bf16(const float* packed_fwd, const void* packed_bwd_bf16, i
  *   gslots: scratch of mvsnerf_mlp_gradslot_floats(N*S) floats; workspace: mvsnerf_mlp_bwd_workspace_floats();
  *   maps: device int table built by the host side (fragment row -> nn.Linear row/column, mvsnerf_amd/ops.py:_mlp_bwd_maps): 1312 entries,
  *                     and for F > 32 a 64-entry feature column table behind them (1376 in all; csrc/mlp_bwd.hip describes every table).
- *   F: every even feat_dim the forward takes, 2 <= F <= 40 (V <= 8 source views) - the training forward, both packs and the backward alike;
- *                     other values MVSNERF_EUNSUPPORTED.  The two size queries without an F argument cover F = 40.
+ *   F: every even feat_dim the forward takes, 2 <= F <= 40 (V <= 8 source views), for the training forward and both packs; the backward
+ *                     (mvsnerf_mlp_bwd, mvsnerf_mlp_bwd_bf16) needs 4 <= F: d_feat rows are written four columns at a time (n_feat_out a
+ *                     multiple of 4, 4 <= n_feat_out <= F, else MVSNERF_EINVAL), and F = 8 + 4V >= 12 is all a caller has.  Other values of
+ *                     F - F = 2 at the backward among them -, S < 1 and N < 0 are MVSNERF_EUNSUPPORTED, looked at after the null pointers
+ *                     and before n_feat_out / the alignment of d_feat.  The two size queries without an F argument cover F = 40.
  *   No gradient is produced for ndc / view directions / colour features (the reference's losses never need them:
  *   rays and source images carry no parameters). */
 size_t mvsnerf_mlp_saved_floats(int64_t n_points);

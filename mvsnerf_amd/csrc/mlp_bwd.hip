@@ -565,8 +565,10 @@ static int mlp_bwd_impl(bool bf, const float* packed_fwd, const float* packed_bw
                         const int* maps, float* workspace, void* stream)
 {
     if (!packed_fwd || !packed_bwd || !raw || !d_raw || !saved || !gslots || !d_feat || !gw || !gb || !maps || !workspace) return MVSNERF_EINVAL;
+    // F first: n_feat_out is judged against a supported F (F = 0 used to come back as MVSNERF_EINVAL through n_feat_out > F).  d_feat rows are
+    // written four columns at a time, so the smallest backward is F = 4: F = 2, which the forward and the packs take, is unsupported HERE.
+    if (F < 4 || F > MAX_F || (F & 1) || N < 0 || S < 1) return MVSNERF_EUNSUPPORTED;
     if (n_feat_out < 4 || n_feat_out > F || (n_feat_out & 3) || !mvs_aligned16(d_feat)) return MVSNERF_EINVAL;
-    if (F < 2 || F > MAX_F || (F & 1) || N < 0 || S < 1) return MVSNERF_EUNSUPPORTED;
     const int64_t P = N * S;
     if (P == 0) return MVSNERF_OK;
     hipStream_t st = (hipStream_t)stream;

@@ -61,6 +61,12 @@ def test_backward_entry_takes_wide_feature_rows():
         assert call(36, 40) == EINVAL and call(36, 34) == EINVAL    # more columns than features; not a multiple of four
         for F in (42, 37):
             assert call(F, 8) == EUNSUPPORTED, F
+        # F is judged before n_feat_out, and the backward starts at F = 4 (d_feat rows are written four columns at a time): F = 0 was MVSNERF_EINVAL
+        # through n_feat_out > F, and F = 2, which the forward and the packs take, had no n_feat_out at all
+        for F in (0, 2):
+            assert call(F, 8) == EUNSUPPORTED and call(F, 4) == EUNSUPPORTED, F
+        assert call(4, 4) == 0 and call(4, 8) == EINVAL
+        assert fn(p, p, 20, p, p, p, 0, 0, p, p, 8, gp, gp, p, p, 0) == EUNSUPPORTED and call(20, 8, N=-1) == EUNSUPPORTED     # S = 0, N < 0
         assert fn(0, p, 42, p, p, p, 0, 1, p, p, 8, gp, gp, p, p, 0) == EINVAL
 
 
