@@ -535,6 +535,31 @@ int mvsnerf_source_images_fwd(const unsigned char* images_rgba, const int64_t* i
 size_t mvsnerf_resample_u8_workspace_bytes(int M, int Hin, int Win, int Hout, int Wout);
 int mvsnerf_resample_u8_fwd(const unsigned char* src, int M, int Hin, int Win, unsigned char* dst, int Hout, int Wout, const int* xwin, const int* xkk,
                             int xks, const int* ywin, const int* ykk, int yks, int alpha_mode, void* workspace, void* stream);
+/* ---- LPIPS-VGG, the third column of the reference's tables (renderer.ipynb: lpips.LPIPS(net='vgg') per held-out view): the VGG-16 trunk and the five
+ *      1x1 heads on channel-last fp32 activations act[n][y][x][C] (csrc/lpips.hip).  Every entry is one layer, so each can be tested alone. ----
+ * Supported (Cin, Cout): (3, 64) = conv1_1, and Cin, Cout in {64, 128, 256, 512}; C of the pool and the head in {64, 128, 256, 512}.
+ * conv_packed_floats: Cin Cout 9 + Cout (weights in MFMA fragment order, then the bias); 0 for an unsupported pair.  Runs without a GPU.
+ * conv_pack: w [Cout][Cin][3][3] and b [Cout] (torch's layout, on the device) -> packed.
+ * conv_fwd: out[n][y][x][co] = relu(b[co] + sum_{ci,ky,kx} w[co][ci][ky][kx] in[n][y+ky-1][x+kx-1][ci]), taps outside the image contributing 0; exact fp32
+ *   (v_mfma_f32_32x32x2_f32; one fmaf chain per output in a fixed order, so image n of a batch has the bits of the image alone).  For Cin == 3 the input
+ *   is an image in [0,1] and every tap INSIDE the image is first scaled as LPIPS's scaling layer does: ((2 x - 1) - shift_c) / scale_c with
+ *   shift = (-.030, -.088, -.188), scale = (.458, .448, .450); padding stays 0.  out [N][H][W][Cout] is fully written.
+ * pool_fwd: max over 2x2 windows at stride 2, out [N][H/2][W/2][C] (floor: an odd last row or column is dropped; a NaN in a window gives NaN).
+ * head_fwd: f0, f1 [K][h][w][C], lin [C].  Per pixel n0 = sqrt(sum_c f0_c^2) + 1e-10 (n1 likewise), d = sum_c lin_c (f0_c / n0 - f1_c / n1)^2 in double;
+ *   the layer value of frame k is the mean of d over its h w pixels: per-workgroup partial sums in workspace, then one summing launch in a fixed order (no
+ *   atomics; an all-zero feature vector gives 0, never NaN).  layer_out[k] (may be NULL) receives the value; total[k] (may be NULL, not both) receives it
+ *   (accumulate == 0) or has it added (accumulate != 0), so five calls on one stream leave the metric in total.  workspace: head_workspace_bytes(K, h, w, C)
+ *   bytes, 8-byte aligned (0 for arguments the entry refuses; runs without a GPU).
+ * MVSNERF_EINVAL: a NULL pointer or a size < 1; MVSNERF_EUNSUPPORTED: another channel count, H or W < 2 for the pool, H W max(Cin, Cout) >= 2^31 or a grid of
+ *   2^31 workgroups; MVSNERF_EALIGN: activations / packed weights not 16-byte (the conv1_1 image, the head's maps and lin: 4-byte; doubles: 8-byte) aligned.
+ *   All before the first launch. */
+size_t mvsnerf_lpips_conv_packed_floats(int Cin, int Cout);
+int mvsnerf_lpips_conv_pack(const float* w, const float* b, int Cin, int Cout, float* packed, void* stream);
+int mvsnerf_lpips_conv_fwd(const float* in, const float* packed, int N, int H, int W, int Cin, int Cout, float* out, void* stream);
+int mvsnerf_lpips_pool_fwd(const float* in, int N, int H, int W, int C, float* out, void* stream);
+size_t mvsnerf_lpips_head_workspace_bytes(int K, int h, int w, int C);
+int mvsnerf_lpips_head_fwd(const float* f0, const float* f1, const float* lin, int K, int h, int w, int C, double* layer_out, double* total,
+                           int accumulate, void* workspace, void* stream);
 
 #ifdef __cplusplus
 }

@@ -290,6 +290,12 @@ SIGNATURES = {
     "mvsnerf_source_images_fwd": (_c_i, [_c_fp, _c_fp] + [_c_i] * 4 + [ctypes.POINTER(ctypes.c_float)] * 2 + [_c_fp, _c_fp]),
     "mvsnerf_resample_u8_workspace_bytes": (ctypes.c_size_t, [_c_i] * 5),
     "mvsnerf_resample_u8_fwd": (_c_i, [_c_fp] + [_c_i] * 3 + [_c_fp, _c_i, _c_i, _c_fp, _c_fp, _c_i, _c_fp, _c_fp, _c_i, _c_i, _c_fp, _c_fp]),
+    "mvsnerf_lpips_conv_packed_floats": (ctypes.c_size_t, [_c_i, _c_i]),
+    "mvsnerf_lpips_conv_pack": (_c_i, [_c_fp, _c_fp, _c_i, _c_i, _c_fp, _c_fp]),
+    "mvsnerf_lpips_conv_fwd": (_c_i, [_c_fp, _c_fp] + [_c_i] * 5 + [_c_fp, _c_fp]),
+    "mvsnerf_lpips_pool_fwd": (_c_i, [_c_fp] + [_c_i] * 4 + [_c_fp, _c_fp]),
+    "mvsnerf_lpips_head_workspace_bytes": (ctypes.c_size_t, [_c_i] * 4),
+    "mvsnerf_lpips_head_fwd": (_c_i, [_c_fp] * 3 + [_c_i] * 4 + [_c_fp, _c_fp, _c_i, _c_fp, _c_fp]),
 }
 
 _lib = None

@@ -1842,6 +1842,84 @@ def frame_metrics(pred, gt, depth_pred=None, depth_gt=None, win_size=7, data_ran
     return out
 
 
+# ------------------------------------------------------------------ LPIPS-VGG layers (csrc/lpips.hip; evaluate.LPIPS strings them together)
+def lpips_conv_packed_floats(Cin, Cout):
+    """Floats of one packed conv layer (weights in MFMA fragment order, then the bias); 0 for a (Cin, Cout) the kernels do not carry.  No GPU needed."""
+    return int(_lib.lib().mvsnerf_lpips_conv_packed_floats(int(Cin), int(Cout)))
+
+
+def lpips_head_workspace_bytes(K, h, w, C):
+    return int(_lib.lib().mvsnerf_lpips_head_workspace_bytes(int(K), int(h), int(w), int(C)))
+
+
+def _lpips_act(x, name, C=None):
+    if not (torch.is_tensor(x) and x.dim() == 4 and (C is None or x.shape[-1] == C)):
+        raise RuntimeError(f"{name}: expected a (N,H,W,{'C' if C is None else C}) tensor, got {tuple(getattr(x, 'shape', ()))}")
+    dev_f32(x, name)
+    return tuple(int(s) for s in x.shape)
+
+
+def lpips_conv_pack(weight, bias):
+    """weight (Cout,Cin,3,3), bias (Cout,) on the GPU -> the packed layer of lpips_conv.  (Cin, Cout) = (3, 64) or both in {64,128,256,512}."""
+    _need_no_grad(weight, bias, op="lpips_conv_pack")
+    if not (torch.is_tensor(weight) and weight.dim() == 4 and tuple(weight.shape[2:]) == (3, 3) and torch.is_tensor(bias) and tuple(bias.shape) == (weight.shape[0],)):
+        raise RuntimeError(f"lpips_conv_pack: weight (Cout,Cin,3,3) and bias (Cout,), got {tuple(getattr(weight, 'shape', ()))} and {tuple(getattr(bias, 'shape', ()))}")
+    Cout, Cin = int(weight.shape[0]), int(weight.shape[1])
+    n = lpips_conv_packed_floats(Cin, Cout)
+    if n == 0:
+        raise RuntimeError(f"lpips_conv_pack: no kernel for a 3x3 convolution {Cin} -> {Cout}")
+    keep = _Keep()
+    pw, pb = keep(weight, "lpips_conv_pack: weight"), keep(bias, "lpips_conv_pack: bias")
+    packed = torch.empty((n,), device=weight.device, dtype=torch.float32)
+    check(_lib.lib().mvsnerf_lpips_conv_pack(pw, pb, Cin, Cout, packed.data_ptr(), stream_ptr()), "lpips_conv_pack")
+    return packed
+
+
+def lpips_conv(x, packed, Cout):
+    """conv3x3 + bias + ReLU (stride 1, zero padding 1) of a channel-last (N,H,W,Cin) fp32 tensor -> (N,H,W,Cout).  Cin == 3 is conv1_1: x is an image in
+    [0,1] and the kernel's loader applies LPIPS's scaling layer to it (padding stays 0 after the scaling)."""
+    _need_no_grad(x, packed, op="lpips_conv")
+    N, H, W, Cin = _lpips_act(x, "lpips_conv: x")
+    if lpips_conv_packed_floats(Cin, Cout) == 0 or not torch.is_tensor(packed) or packed.numel() != lpips_conv_packed_floats(Cin, Cout):
+        raise RuntimeError(f"lpips_conv: packed does not hold a {Cin} -> {Cout} layer")
+    out = torch.empty((N, H, W, int(Cout)), device=x.device, dtype=torch.float32)
+    check(_lib.lib().mvsnerf_lpips_conv_fwd(x.data_ptr(), dev_f32(packed, "lpips_conv: packed"), N, H, W, Cin, int(Cout), out.data_ptr(), stream_ptr()),
+          "lpips_conv_fwd")
+    return out
+
+
+def lpips_pool(x):
+    """maxpool 2x2 / stride 2, floor mode, of a channel-last (N,H,W,C) fp32 tensor -> (N,H//2,W//2,C)."""
+    _need_no_grad(x, op="lpips_pool")
+    N, H, W, C = _lpips_act(x, "lpips_pool: x")
+    out = torch.empty((N, H // 2, W // 2, C), device=x.device, dtype=torch.float32)
+    check(_lib.lib().mvsnerf_lpips_pool_fwd(x.data_ptr(), N, H, W, C, out.data_ptr(), stream_ptr()), "lpips_pool_fwd")
+    return out
+
+
+def lpips_head(f0, f1, lin, layer_out=None, total=None, accumulate=False):
+    """One LPIPS tap layer: f0, f1 (K,h,w,C) fp32, lin (C,) -> layer_out (K,) float64 on the GPU, the frame means of
+    sum_c lin_c (f0_c / n0 - f1_c / n1)^2 with n = sqrt(sum_c f_c^2) + 1e-10.  total (K,) float64, if given, receives the value too (accumulate=False) or has it
+    added.  Two launches, no atomics, no host synchronisation."""
+    _need_no_grad(f0, f1, lin, op="lpips_head")
+    K, h, w, C = _lpips_act(f0, "lpips_head: f0")
+    if _lpips_act(f1, "lpips_head: f1") != (K, h, w, C) or not torch.is_tensor(lin) or tuple(lin.shape) != (C,):
+        raise RuntimeError(f"lpips_head: f1 must be {(K, h, w, C)} and lin ({C},), got {tuple(f1.shape)} and {tuple(getattr(lin, 'shape', ()))}")
+    need = lpips_head_workspace_bytes(K, h, w, C)
+    if need == 0:
+        raise RuntimeError(f"lpips_head: no kernel for C = {C}")
+    if layer_out is None:
+        layer_out = torch.empty((K,), device=f0.device, dtype=torch.float64)
+    for t, name in ((layer_out, "layer_out"), (total, "total")):
+        if t is not None and not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == (K,) and t.device == f0.device):
+            raise RuntimeError(f"lpips_head: {name} must be a contiguous ({K},) float64 tensor on {f0.device}")
+    workspace = torch.empty((need // 8,), device=f0.device, dtype=torch.float64)
+    check(_lib.lib().mvsnerf_lpips_head_fwd(f0.data_ptr(), f1.data_ptr(), dev_f32(lin, "lpips_head: lin"), K, h, w, C, layer_out.data_ptr(),
+                                            0 if total is None else total.data_ptr(), int(bool(accumulate)), workspace.data_ptr(), stream_ptr()),
+          "lpips_head_fwd")
+    return layer_out
+
+
 # ------------------------------------------------------------------ 8-bit video frames (csrc/frames.hip)
 _JET = {}
 
