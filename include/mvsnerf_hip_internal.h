@@ -560,6 +560,34 @@ int mvsnerf_lpips_pool_fwd(const float* in, int N, int H, int W, int C, float* o
 size_t mvsnerf_lpips_head_workspace_bytes(int K, int h, int w, int C);
 int mvsnerf_lpips_head_fwd(const float* f0, const float* f1, const float* lin, int K, int h, int w, int C, double* layer_out, double* total,
                            int accumulate, void* workspace, void* stream);
+/* ---- the depth maps of a scene's views -> a coloured point cloud: the cross-view geometric-consistency filter of the MVSNet line of work and the stable
+ *      compaction of the kept pixels (csrc/depth_fusion.hip).  No counterpart in the reference. ----
+ * Conventions are the bank's (scene_rays above): pixel centres at integer coordinates, camera direction ((x - cx) / fx, (y - cy) / fy, 1), a depth z the
+ *   parameter of o + d z with that unnormalised d (camera-space z); c2w, w2c [M][3][4] (w2c: the inverse of c2w, formed by the caller), K [M][3][3].
+ * depth_consistency: depth [M][H][W] fp32, valid [M][H][W] uint8 or NULL, images_rgba [M][H][W][4] uint8 or NULL (only its alpha bytes are read),
+ *   src_ids [M][n_src] int32 (device).  A depth is INVALID when it is not finite, <= 0, valid is given and 0 there, or images_rgba is given and its alpha
+ *   is 0 there: such a pixel gets seen = 0, fused = 0, mask = 0.  For source j of view r, s = src_ids[r][j] (an id outside [0, M), -1 being the padding,
+ *   or equal to r is skipped and reads nothing): P = o_r + d_r z; q = R_s P + t_s, q.z > 0; (u, v) = (fx_s q.x / q.z + cx_s, fy_s q.y / q.z + cy_s) inside
+ *   [0, W-1] x [0, H-1]; the bilinear cell x0 = min(floor u, W-2), y0 = min(floor v, H-2) with weights u - x0, v - y0, all four taps of depth[s] valid;
+ *   (u, v, z_s) lifted through view s and projected into view r gives (x', y', z').  The pair is consistent iff z' > 0, sqrt((x'-x)^2 + (y'-y)^2) < pix_thr
+ *   and |z' - z| / z < rel_thr.  seen [M][H][W] uint32: bit j; fused [M][H][W] fp32 = (z + sum of z' over consistent sources) / (1 + popcount(seen));
+ *   mask [M][H][W] uint8 = popcount(seen) >= min_views.  fp32 throughout (products may contract into fmas).  One thread per reference pixel; no atomics;
+ *   every output element is written.
+ * point_cloud: the pixels with mask != 0 in flat-ray-index order (view-major, then row-major: torch.nonzero's order), count -> scan -> write, no atomics, two
+ *   runs give the same bytes.  Row j < min(count, capacity): points [.][3] fp32 = o_r + d_r fused, colors [.][3] uint8 = the bank's RGB bytes, n_views [.]
+ *   uint8 = popcount(seen), index [.] int64 = the flat ray index.  *count (device int64) always receives the true total; rows >= capacity are neither read
+ *   nor written, so a caller that guessed too small runs again.  capacity == 0 runs the count alone (every pointer but mask, count and workspace may be NULL).
+ *   workspace: point_cloud_workspace_bytes(M H W) bytes, 4-byte aligned (0 for n_pixels < 1 or >= 2^31; runs without a GPU).
+ * MVSNERF_EINVAL: a NULL required pointer, M, H or W < 1, n_src outside 1..32, min_views < 0, a threshold that is not finite or <= 0, capacity < 0;
+ *   MVSNERF_EUNSUPPORTED: H < 2 or W < 2 (no bilinear cell), M H W >= 2^31; MVSNERF_EALIGN: a float / int32 / uint32 / RGBA array not 4-byte, index or count
+ *   not 8-byte aligned.  All before the first launch. */
+int mvsnerf_depth_consistency_fwd(const float* depth, const unsigned char* valid, const unsigned char* images_rgba, const float* c2w, const float* w2c,
+                                  const float* K, const int* src_ids, int M, int H, int W, int n_src, float pix_thr, float rel_thr, int min_views,
+                                  unsigned* seen, float* fused, unsigned char* mask, void* stream);
+size_t mvsnerf_point_cloud_workspace_bytes(int64_t n_pixels);
+int mvsnerf_point_cloud_fwd(const unsigned char* images_rgba, const float* c2w, const float* K, int M, int H, int W, const float* fused,
+                            const unsigned* seen, const unsigned char* mask, int64_t capacity, float* points, unsigned char* colors,
+                            unsigned char* n_views, int64_t* index, int64_t* count, void* workspace, void* stream);
 
 #ifdef __cplusplus
 }

@@ -296,6 +296,9 @@ SIGNATURES = {
     "mvsnerf_lpips_pool_fwd": (_c_i, [_c_fp] + [_c_i] * 4 + [_c_fp, _c_fp]),
     "mvsnerf_lpips_head_workspace_bytes": (ctypes.c_size_t, [_c_i] * 4),
     "mvsnerf_lpips_head_fwd": (_c_i, [_c_fp] * 3 + [_c_i] * 4 + [_c_fp, _c_fp, _c_i, _c_fp, _c_fp]),
+    "mvsnerf_depth_consistency_fwd": (_c_i, [_c_fp] * 7 + [_c_i] * 4 + [ctypes.c_float, ctypes.c_float, _c_i] + [_c_fp] * 4),
+    "mvsnerf_point_cloud_workspace_bytes": (ctypes.c_size_t, [_c_l]),
+    "mvsnerf_point_cloud_fwd": (_c_i, [_c_fp] * 3 + [_c_i] * 3 + [_c_fp] * 3 + [_c_l] + [_c_fp] * 7),
 }
 
 _lib = None

@@ -1999,3 +1999,87 @@ def frame_u8(rgb, depth=None, minmax=None, lut=None, crop=(0, 0), out=None):
         raise RuntimeError(f"frame_u8: out must be a contiguous uint8 tensor of shape {shape} on {dev}")
     check(_lib.lib().mvsnerf_frame_u8_fwd(p_rgb, p_depth, H, W, p_mm, p_lut, ch, cw, int(depth is not None), out.data_ptr(), stream_ptr()), "frame_u8_fwd")
     return out
+
+
+# ------------------------------------------------------------------ depth maps -> point cloud (csrc/depth_fusion.hip)
+def _fusion_bank(images, c2ws, intrinsics, op):
+    if not (torch.is_tensor(images) and images.is_cuda and images.dtype == torch.uint8 and images.dim() == 4 and images.shape[-1] == 4
+            and images.is_contiguous()):
+        raise RuntimeError(f"{op}: images must be a contiguous (M,H,W,4) uint8 tensor on the GPU (SceneRays.images)")
+    M, H, W = (int(v) for v in images.shape[:3])
+    if tuple(c2ws.shape) != (M, 3, 4) or tuple(intrinsics.shape) != (M, 3, 3):
+        raise RuntimeError(f"{op}: c2ws ({M},3,4) and intrinsics ({M},3,3) expected, got {tuple(c2ws.shape)}, {tuple(intrinsics.shape)}")
+    if images.device.index != torch.cuda.current_device():
+        raise RuntimeError(f"{op}: the bank is on {images.device} but the current device is cuda:{torch.cuda.current_device()}")
+    return M, H, W
+
+
+def _fusion_map(t, dtype, shape, dev, name, op):
+    if not (torch.is_tensor(t) and t.dtype == dtype and tuple(t.shape) == shape and t.device == dev and t.is_contiguous()):
+        raise RuntimeError(f"{op}: {name} must be a contiguous {shape} {dtype} tensor on {dev}, got {tuple(getattr(t, 'shape', ()))} "
+                           f"{getattr(t, 'dtype', None)} {getattr(t, 'device', None)}")
+    return t.data_ptr()
+
+
+def depth_consistency(images, c2ws, w2cs, intrinsics, depths, src_ids, pix_thr=1.0, rel_thr=0.01, min_views=3, valid=None, alpha=True):
+    """The cross-view geometric-consistency filter of the MVSNet line of work over the M depth maps of a bank (mvsnerf_depth_consistency_fwd; the
+    definition is in include/mvsnerf_hip_internal.h): depths (M,H,W) fp32, src_ids (M,n_src) int32 on the device (-1: no view), valid (M,H,W) uint8 | None,
+    w2cs (M,3,4) the inverses of c2ws -> (seen (M,H,W) int32 bit masks, fused (M,H,W) fp32, mask (M,H,W) uint8).  alpha=False leaves the bank's alpha
+    bytes unread (a bank built from three-channel images holds 255 everywhere).  One launch, no atomics, every output element written."""
+    op = "depth_consistency"
+    _need_no_grad(depths, c2ws, w2cs, intrinsics, op=op)
+    M, H, W = _fusion_bank(images, c2ws, intrinsics, op)
+    dev = images.device
+    if tuple(w2cs.shape) != (M, 3, 4):
+        raise RuntimeError(f"{op}: w2cs must be ({M},3,4), got {tuple(w2cs.shape)}")
+    p_depth = _fusion_map(depths, torch.float32, (M, H, W), dev, "depths", op)
+    p_valid = 0 if valid is None else _fusion_map(valid, torch.uint8, (M, H, W), dev, "valid", op)
+    if not (torch.is_tensor(src_ids) and src_ids.dim() == 2 and src_ids.shape[0] == M):
+        raise RuntimeError(f"{op}: src_ids must be ({M},n_src)")
+    n_src = int(src_ids.shape[1])
+    p_src = _fusion_map(src_ids, torch.int32, (M, n_src), dev, "src_ids", op)
+    c = _Keep()
+    seen = torch.empty((M, H, W), device=dev, dtype=torch.int32)
+    fused = torch.empty((M, H, W), device=dev, dtype=torch.float32)
+    mask = torch.empty((M, H, W), device=dev, dtype=torch.uint8)
+    check(_lib.lib().mvsnerf_depth_consistency_fwd(p_depth, p_valid, images.data_ptr() if alpha else 0, c(c2ws, "c2ws"), c(w2cs, "w2cs"),
+                                                   c(intrinsics, "intrinsics"), p_src, M, H, W, n_src, float(pix_thr), float(rel_thr), int(min_views),
+                                                   seen.data_ptr(), fused.data_ptr(), mask.data_ptr(), stream_ptr()), "depth_consistency_fwd")
+    return seen, fused, mask
+
+
+def point_cloud(images, c2ws, intrinsics, fused, seen, mask, capacity, out=None):
+    """The pixels with mask != 0 as a coloured point cloud in flat-ray-index order (mvsnerf_point_cloud_fwd: count -> scan -> write, no atomics, two runs
+    give the same bytes) -> (points (capacity,3) fp32 = o + d * fused, colors (capacity,3) uint8, n_views (capacity,) uint8 = popcount(seen),
+    index (capacity,) int64, count (1,) int64 on the device).  count always holds the true total; rows >= min(count, capacity) are not written.
+    capacity == 0 runs the count alone.  out: the four output tensors to write into (at least capacity rows each); nothing is read from the device."""
+    op = "point_cloud"
+    _need_no_grad(fused, c2ws, intrinsics, op=op)
+    M, H, W = _fusion_bank(images, c2ws, intrinsics, op)
+    dev = images.device
+    capacity = int(capacity)
+    if capacity < 0:
+        raise RuntimeError(f"{op}: capacity must be >= 0, got {capacity}")
+    p_fused = _fusion_map(fused, torch.float32, (M, H, W), dev, "fused", op)
+    p_seen = _fusion_map(seen, torch.int32, (M, H, W), dev, "seen", op)
+    p_mask = _fusion_map(mask, torch.uint8, (M, H, W), dev, "mask", op)
+    lib = _lib.lib()
+    ws_bytes = int(lib.mvsnerf_point_cloud_workspace_bytes(M * H * W))
+    if ws_bytes == 0:
+        raise RuntimeError(f"{op}: {M} x {H} x {W} pixels are outside what the compaction indexes (fewer than 2^31)")
+    if out is None:
+        out = (torch.empty((capacity, 3), device=dev, dtype=torch.float32), torch.empty((capacity, 3), device=dev, dtype=torch.uint8),
+               torch.empty((capacity,), device=dev, dtype=torch.uint8), torch.empty((capacity,), device=dev, dtype=torch.int64))
+    else:
+        for t, dt, tail, name in zip(out, (torch.float32, torch.uint8, torch.uint8, torch.int64), ((3,), (3,), (), ()), ("points", "colors", "n_views", "index")):
+            if not (torch.is_tensor(t) and t.dtype == dt and t.device == dev and t.is_contiguous() and t.dim() == 1 + len(tail)
+                    and tuple(t.shape[1:]) == tail and t.shape[0] >= capacity):
+                raise RuntimeError(f"{op}: out {name} must be a contiguous (>= {capacity},{','.join(map(str, tail))}) {dt} tensor on {dev}")
+    points, colors, n_views, index = out
+    count = torch.empty((1,), device=dev, dtype=torch.int64)
+    ws = torch.empty((ws_bytes // 4,), device=dev, dtype=torch.int32)
+    c = _Keep()
+    ptr = (lambda t: t.data_ptr()) if capacity > 0 else (lambda t: 0)    # (an empty tensor has no address to hand over)
+    check(lib.mvsnerf_point_cloud_fwd(images.data_ptr(), c(c2ws, "c2ws"), c(intrinsics, "intrinsics"), M, H, W, p_fused, p_seen, p_mask, capacity,
+                                      ptr(points), ptr(colors), ptr(n_views), ptr(index), count.data_ptr(), ws.data_ptr(), stream_ptr()), "point_cloud_fwd")
+    return points, colors, n_views, index, count
