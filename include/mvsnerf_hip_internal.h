@@ -588,6 +588,30 @@ size_t mvsnerf_point_cloud_workspace_bytes(int64_t n_pixels);
 int mvsnerf_point_cloud_fwd(const unsigned char* images_rgba, const float* c2w, const float* K, int M, int H, int W, const float* fused,
                             const unsigned* seen, const unsigned char* mask, int64_t capacity, float* points, unsigned char* colors,
                             unsigned char* n_views, int64_t* index, int64_t* count, void* workspace, void* stream);
+/* ---- a (D,H,W) scalar field (a scene's node density) -> a triangle mesh of its level set: marching tetrahedra over the Kuhn split of every grid cell
+ *      (csrc/mesh.hip, DESIGN.md 4n, where the definition is written out).  No counterpart in the reference. ----
+ * field [D][H][W] fp32 (device): node (i,j,k) = field[k][j][i], flat index n = (k H + j) W + i, inside iff field >= level (a NaN is outside).  A node owns
+ *   the edges to the node at +(dx,dy,dz), e = 0..6: (1,0,0) (0,1,0) (0,0,1) (1,1,0) (1,0,1) (0,1,1) (1,1,1).  An edge with exactly one end inside carries a
+ *   vertex at t = (level - s0) / (s1 - s0) from its owner (0.5 when an end is not finite); vertices are ordered by the key n * 8 + e.  Row j of a vertex:
+ *   ndc [.][3] = ((i,j,k) + t (dx,dy,dz)) / (W-1, H-1, D-1); vertices [.][3] = box[0..2] + ndc * (box[3..5] - box[0..2]) (box: 6 HOST floats, lo then hi), or
+ *   P0 + t (P1 - P0) (positions [D][H][W][3], device: the nodes' positions), or the grid coordinates themselves (neither); vertex_edge [.] int64 = the key.
+ *   fp32, every operation rounded on its own, IEEE division.  faces [.][3] int32 vertex numbers: per cell 6 tetrahedra (one per permutation of the axes,
+ *   lexicographic), ordered by cell, tetrahedron, triangle; counter-clockwise seen from the side where the field is below the level.
+ * count (device, int64 [2]) always receives the true numbers of vertices and faces.  Rows >= cap_vertices / cap_faces are not written; both capacities 0
+ *   runs the count alone (the output pointers of a capacity of 0 may be NULL).  classify -> scan -> vertices -> faces, no atomics, two runs give the same bytes.
+ * workspace: mesh_workspace_bytes(D, H, W) bytes (5 per node + 16 per workgroup of 256 nodes), 4-byte aligned; 0 for a shape the entry refuses (runs
+ *   without a GPU).
+ * mesh_dirs: dirs [n][3] = vertices [n][3] - origin (3 device floats).  mesh_rgb_u8: rgb [n][3] uint8 = trunc(clamp(c, 0, 1) * 255) of the first three of
+ *   the four floats of row rgba [n][4] (NaN -> 0: the rule of frame_u8).  n == 0 launches nothing.
+ * MVSNERF_EINVAL: a NULL pointer that is needed, a capacity or n < 0; MVSNERF_EUNSUPPORTED: D, H or W < 2, D H W > 2^27, a level that is not finite, both
+ *   positions and box, n >= 2^31; MVSNERF_EALIGN: a float / int32 array or the workspace not 4-byte, vertex_edge or count not 8-byte, rgba not 16-byte
+ *   aligned.  All before the first launch. */
+size_t mvsnerf_mesh_workspace_bytes(int D, int H, int W);
+int mvsnerf_mesh_extract_fwd(const float* field, int D, int H, int W, float level, const float* positions, const float* box, int64_t cap_vertices,
+                             int64_t cap_faces, float* vertices, float* ndc, int64_t* vertex_edge, int* faces, int64_t* count, void* workspace,
+                             void* stream);
+int mvsnerf_mesh_dirs_fwd(const float* vertices, const float* origin, int64_t n, float* dirs, void* stream);
+int mvsnerf_mesh_rgb_u8_fwd(const float* rgba, int64_t n, unsigned char* rgb, void* stream);
 
 #ifdef __cplusplus
 }

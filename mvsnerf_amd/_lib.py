@@ -299,6 +299,10 @@ SIGNATURES = {
     "mvsnerf_depth_consistency_fwd": (_c_i, [_c_fp] * 7 + [_c_i] * 4 + [ctypes.c_float, ctypes.c_float, _c_i] + [_c_fp] * 4),
     "mvsnerf_point_cloud_workspace_bytes": (ctypes.c_size_t, [_c_l]),
     "mvsnerf_point_cloud_fwd": (_c_i, [_c_fp] * 3 + [_c_i] * 3 + [_c_fp] * 3 + [_c_l] + [_c_fp] * 7),
+    "mvsnerf_mesh_workspace_bytes": (ctypes.c_size_t, [_c_i] * 3),
+    "mvsnerf_mesh_extract_fwd": (_c_i, [_c_fp] + [_c_i] * 3 + [ctypes.c_float, _c_fp, ctypes.POINTER(ctypes.c_float), _c_l, _c_l] + [_c_fp] * 7),
+    "mvsnerf_mesh_dirs_fwd": (_c_i, [_c_fp, _c_fp, _c_l, _c_fp, _c_fp]),
+    "mvsnerf_mesh_rgb_u8_fwd": (_c_i, [_c_fp, _c_l, _c_fp, _c_fp]),
 }
 
 _lib = None

@@ -4,6 +4,10 @@
 device.  `fuse_depths` runs the cross-view geometric-consistency filter of the MVSNet line of work over the M depth maps (reproject each pixel into its
 source views and back, keep it where enough views agree, average the agreeing depths) and compacts the kept pixels into points, colours and view counts,
 all on the device (csrc/depth_fusion.hip).  The reference has no counterpart; the result is not pinned against any external fusion tool.
+
+Geometry from density: `extract_mesh` turns a (D,H,W) field - a scene's node density, ops.node_density - into the triangle mesh of its level set by marching
+tetrahedra over the Kuhn split of every cell (csrc/mesh.hip), `vertex_colors` asks the radiance network for a colour per vertex and `scene_mesh`
+does both for a fine-tuned scene.  Not pinned against any external mesher either.
 """
 import math
 
@@ -128,10 +132,185 @@ def fuse_depths(scene, depths, src_ids=None, n_src=4, pix_thr=1.0, rel_thr=0.01,
     return PointCloud(points, colors, n_views, index, count, fused, mask.view(torch.bool), seen, src)
 
 
+class TriangleMesh:
+    """What extract_mesh and scene_mesh return.
+        vertices (V,3) fp32 world (box= or positions=; grid coordinates without either), ndc (V,3) fp32: the coordinates ops.volume_sample resolves
+        faces (T,3) int32 vertex numbers, counter-clockwise seen from the side where the field is below the level
+        vertex_edge (V,) int64, ascending: node * 8 + e, the grid edge a vertex lies on (node = (k H + j) W + i, e = 0..6 the owned edge)
+        colors (V,3) uint8 or None
+        count   (2,) int64 on the device: the true numbers of vertices and faces (the first min(count, rows) rows of each array are meaningful when a
+                capacity was given; a count above it means the mesh was cut and the call wants repeating)"""
+
+    def __init__(self, vertices, ndc, faces, vertex_edge, count, colors=None):
+        self.vertices, self.ndc, self.faces, self.vertex_edge, self.count, self.colors = vertices, ndc, faces, vertex_edge, count, colors
+
+
+def _mesh_args(field, level, positions, box, capacity, who):
+    """The refusals of extract_mesh, before the library is touched -> (level, box as a (2,3) fp32 host tensor | None, capacity pair | None)."""
+    if not torch.is_tensor(field) or field.dtype != torch.float32:
+        raise TypeError(f"{who}: field must be a float32 tensor of shape (D,H,W), got {getattr(field, 'dtype', type(field).__name__)}")
+    if field.dim() != 3 or min(field.shape) < 2:
+        raise ValueError(f"{who}: field must be (D,H,W) with every dimension >= 2 (a cell), got {tuple(field.shape)}")
+    D, H, W = (int(v) for v in field.shape)
+    if D * H * W > ops.MESH_MAX_NODES:
+        raise ValueError(f"{who}: at most 2^27 nodes (vertex and face numbers are int32), got {D} x {H} x {W}")
+    level = float(level)
+    if not math.isfinite(level):
+        raise ValueError(f"{who}: level must be finite, got {level}")
+    if positions is not None and box is not None:
+        raise ValueError(f"{who}: positions (a table of node positions) and box (lo, hi) exclude each other")
+    if positions is not None:
+        if not torch.is_tensor(positions) or positions.dtype != torch.float32:
+            raise TypeError(f"{who}: positions must be a float32 tensor of shape ({D},{H},{W},3), got {getattr(positions, 'dtype', type(positions).__name__)}")
+        if tuple(positions.shape) != (D, H, W, 3):
+            raise ValueError(f"{who}: positions must be ({D},{H},{W},3), one position per node, got {tuple(positions.shape)}")
+        if positions.device != field.device:
+            raise ValueError(f"{who}: positions must be on the field's device {field.device}, got {positions.device}")
+    if box is not None:
+        box = torch.as_tensor(box).detach().to("cpu", torch.float32)
+        if box.numel() != 6 or not bool(torch.isfinite(box).all()):
+            raise ValueError(f"{who}: box must be (lo, hi), 2 x 3 finite numbers, got {tuple(box.shape)}")
+        box = box.reshape(2, 3)
+    if capacity is not None:
+        try:
+            cap = (int(capacity[0]), int(capacity[1]))
+            ok = len(capacity) == 2 and min(cap) >= 0
+        except (TypeError, ValueError, IndexError):
+            ok = False
+        if not ok:
+            raise ValueError(f"{who}: capacity must be None or a pair (max_vertices, max_faces) of numbers >= 0, got {capacity!r}")
+        capacity = cap
+    return level, box, capacity
+
+
+@torch.no_grad()
+def extract_mesh(field, level, positions=None, box=None, capacity=None):
+    """The level set of a scalar field on a grid as a TriangleMesh: marching tetrahedra over the Kuhn split of every cell (csrc/mesh.hip).
+        field       (D,H,W) fp32 on the GPU, e.g. a scene's node density; a node is inside iff field >= level (NaN: outside; write -inf into nodes to mask)
+        level       finite
+        positions   (D,H,W,3) fp32 node positions on the field's device (ops.voxel_points(...)[1] of a frustum volume): vertices interpolate them
+        box         (lo, hi), 2 x 3 numbers: vertices = lo + ndc * (hi - lo) (a box volume's bbox_3d).  Neither: vertices are grid coordinates.
+        capacity    None: the counts are read from the device once and the arrays have exactly V and T rows.  A pair (max_vertices, max_faces): nothing
+                    is read from the device, mesh.count holds the true totals and rows past them are not written.
+    The surface is closed and consistently oriented wherever it does not touch the grid border; a positions table with a mirrored mapping flips the
+    winding."""
+    level, box, capacity = _mesh_args(field, level, positions, box, capacity, "extract_mesh")
+    with torch.cuda.device(field.device):
+        vertices, ndc, vertex_edge, faces, count = ops.mesh_extract(field.contiguous(), level, None if positions is None else positions.contiguous(),
+                                                                    box, capacity)
+    return TriangleMesh(vertices, ndc, faces, vertex_edge, count)
+
+
+def _scene_sources(system):
+    """(the keywords of ops.node_density but dilate, the system's reference pose) - train._density_sources, as the systems' own density methods call it."""
+    from . import train
+    if isinstance(system, train.MVSSystemFusion):
+        system._need_volume()
+        F = system.args.feat_dim
+        pose = system.pose_source_ref
+        return train._density_sources(system.network_fn, F, system.volume.feat_volume.detach(), pose, (F - 8) // 4), pose
+    if isinstance(system, train.MVSSystemFinetune):
+        V = system.imgs.shape[1]
+        vol = system.volume.feat_volume.detach()
+        H, W = system.imgs.shape[-2:]
+        src = train._density_sources(system.network_fn, system.args.feat_dim, vol, system.pose_source, V, system.imgs[0] if vol.shape[1] == 8 else None,
+                                     near_far=system.near_far_source, ref_hw=(int(H), int(W)), pad=system.args.pad,
+                                     lindisp=bool(getattr(system.args, "use_disp", False)))
+        return src, system.pose_source
+    raise TypeError(f"a fine-tuned scene (MVSSystemFinetune or MVSSystemFusion) expected, got {type(system).__name__}")
+
+
+@torch.no_grad()
+def vertex_colors(system, mesh, origin=None, chunk=262144):
+    """(rows,3) uint8: the radiance network's colour at each vertex of `mesh`, seen from `origin` - a world point (3 numbers), default the centre of
+    the system's reference camera.  Per chunk of rows: ops.gather (8-channel volume and source images, at mesh.vertices / mesh.ndc) or
+    ops.gather_colorvol (colour volume, at mesh.ndc) on rows shaped (n,1,3) -> ops.dir_feature(vertices - origin, w2c_ref, normalize=True) ->
+    ops.mlp_forward(alpha_only=False) with N = n, S = 1 (the way ops.node_density queries nodes) -> trunc(clamp(rgb, 0, 1) * 255).  The sources are
+    train._density_sources', so any network mlp_forward runs works.  The count is read from the device once: rows past min(count, rows) - a mesh
+    with a caller-given capacity has such - are left 0."""
+    chunk = int(chunk)
+    if chunk < 1:
+        raise ValueError(f"vertex_colors: chunk must be >= 1, got {chunk}")
+    src, pose = _scene_sources(system)
+    vol_cl, F = src["vol_cl"], int(system.args.feat_dim)
+    dev = vol_cl.device
+    alt = {k: v for k, v in src.items() if k not in ("vol_cl", "packed", "w2cs", "imgs", "intrinsics", "camera")}
+    with torch.cuda.device(dev):
+        rows = min(int(mesh.count[0].item()), int(mesh.vertices.shape[0]))
+        colors = torch.zeros((int(mesh.vertices.shape[0]), 3), device=dev, dtype=torch.uint8)
+        o = pose["c2ws"][0][:3, 3] if origin is None else torch.as_tensor(origin, dtype=torch.float32).reshape(3)
+        o = o.to(dev, torch.float32).contiguous()
+        w2c_ref = pose["w2cs"][0].contiguous()
+        for a in range(0, rows, chunk):
+            n = min(chunk, rows - a)
+            v, ndc = mesh.vertices[a:a + n], mesh.ndc[a:a + n].view(n, 1, 3)
+            if "imgs" in src:
+                feat, _ = ops.gather(vol_cl, src["imgs"], src["w2cs"], src["intrinsics"], v.view(n, 1, 3), ndc)
+            else:
+                feat, _ = ops.gather_colorvol(vol_cl, ndc)
+            dirs = ops.dir_feature(ops.mesh_dirs(v, o), w2c_ref, normalize=True)
+            raw = ops.mlp_forward(src["packed"], F, ndc.data_ptr(), 3, feat.data_ptr(), F, dirs.data_ptr(), 3, n, 1, 0, dev, **alt)
+            colors[a:a + n] = ops.mesh_rgb_u8(raw)
+    return colors
+
+
+@torch.no_grad()
+def scene_mesh(system, level, colors=True, origin=None, dilate=0, capacity=None):
+    """The surface sigma = level of a fine-tuned scene as a TriangleMesh in world coordinates.  MVSSystemFusion: the field is the box volume's node
+    density (ops.node_density) and box = bbox_3d.  MVSSystemFinetune: the field is the render-space node density and positions are the world positions
+    of the frustum's nodes (ops.voxel_points with the reference camera).  dilate: ops.node_density's.  colors: vertex_colors(system, mesh, origin).
+    No attribute of the system is assigned: system.density_volume stays what it was."""
+    from . import train
+    src, pose = _scene_sources(system)
+    with torch.cuda.device(src["vol_cl"].device):
+        field = ops.node_density(dilate=dilate, **src)
+        if isinstance(system, train.MVSSystemFusion):
+            mesh = extract_mesh(field, level, box=system.bbox_3d, capacity=capacity)
+        else:
+            D, H, W = field.shape
+            Hi, Wi = system.imgs.shape[-2:]      # the reference view, as _density_sources hands it to ops.node_density (a colour volume's sources hold none)
+            positions = ops.voxel_points(D, H, W, K_ref=pose["intrinsics"][0], c2w_ref=pose["c2ws"][0], near_far=system.near_far_source,
+                                         ref_hw=(int(Hi), int(Wi)), pad=system.args.pad, lindisp=bool(getattr(system.args, "use_disp", False)),
+                                         device=field.device)[1]
+            mesh = extract_mesh(field, level, positions=positions.view(D, H, W, 3), capacity=capacity)
+    if colors:
+        mesh.colors = vertex_colors(system, mesh, origin)
+    return mesh
+
+
+def _mesh_ply(path, mesh):
+    nv = min(int(mesh.count[0].item()), int(mesh.vertices.shape[0]))
+    nf = min(int(mesh.count[1].item()), int(mesh.faces.shape[0]))
+    xyz = mesh.vertices[:nv].detach().cpu().numpy()
+    rgb = np.full((nv, 3), 128, np.uint8) if mesh.colors is None else mesh.colors[:nv].detach().cpu().numpy()
+    tri = mesh.faces[:nf].detach().cpu().numpy()
+    if xyz.ndim != 2 or xyz.shape[1] != 3 or rgb.shape != xyz.shape or rgb.dtype != np.uint8 or tri.ndim != 2 or tri.shape[1] != 3:
+        raise ValueError(f"save_ply: vertices (V,3) float, colors (V,3) uint8 and faces (T,3) int, got {xyz.shape}, {rgb.shape} {rgb.dtype}, {tri.shape}")
+    rec = np.empty(nv, dtype=PLY_VERTEX)
+    for k, name in enumerate(("x", "y", "z")):
+        rec[name] = xyz[:, k]
+    for k, name in enumerate(("red", "green", "blue")):
+        rec[name] = rgb[:, k]
+    frec = np.empty(nf, dtype=PLY_FACE)
+    frec["n"], frec["v"] = 3, tri
+    header = "ply\nformat binary_little_endian 1.0\nelement vertex %d\n" % nv
+    header += "".join(f"property {'float' if PLY_VERTEX[name] == np.dtype('<f4') else 'uchar'} {name}\n" for name in PLY_VERTEX.names)
+    header += "element face %d\nproperty list uchar int vertex_indices\nend_header\n" % nf
+    with open(path, "wb") as f:
+        f.write(header.encode("ascii"))
+        f.write(rec.tobytes())
+        f.write(frec.tobytes())
+    return nv, nf
+
+
 def save_ply(path, cloud):
     """A binary little-endian PLY of the cloud's points and colours: x y z float, red green blue uchar, 15 bytes per vertex.  Host side (numpy), next to
     utils.save_frames; takes a PointCloud or a (points, colors) pair.  Of a PointCloud with a caller-given capacity the first min(count, capacity) rows are
-    written.  Returns the number of vertices."""
+    written.  Returns the number of vertices.
+    A TriangleMesh: the same vertex records (colours (128,128,128) when mesh.colors is None), then `element face T` with `property list uchar int
+    vertex_indices`, 13 bytes per face; the first min(count, rows) rows of each array are written.  Returns (V, T)."""
+    if isinstance(cloud, TriangleMesh):
+        return _mesh_ply(path, cloud)
     if isinstance(cloud, PointCloud):
         n = min(int(cloud.count.item()), int(cloud.points.shape[0]))
         points, colors = cloud.points[:n], cloud.colors[:n]
@@ -155,3 +334,4 @@ def save_ply(path, cloud):
 
 
 PLY_VERTEX = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")])
+PLY_FACE = np.dtype([("n", "u1"), ("v", "<i4", 3)])

@@ -2083,3 +2083,83 @@ def point_cloud(images, c2ws, intrinsics, fused, seen, mask, capacity, out=None)
     check(lib.mvsnerf_point_cloud_fwd(images.data_ptr(), c(c2ws, "c2ws"), c(intrinsics, "intrinsics"), M, H, W, p_fused, p_seen, p_mask, capacity,
                                       ptr(points), ptr(colors), ptr(n_views), ptr(index), count.data_ptr(), ws.data_ptr(), stream_ptr()), "point_cloud_fwd")
     return points, colors, n_views, index, count
+
+
+# ------------------------------------------------------------------ a density volume -> a triangle mesh (csrc/mesh.hip)
+MESH_MAX_NODES = 1 << 27
+
+
+def mesh_extract(field, level, positions=None, box=None, capacity=None):
+    """Marching tetrahedra over the Kuhn split of the cells of field (D,H,W) fp32 (mvsnerf_mesh_extract_fwd; the definition is in DESIGN.md 4n and
+    include/mvsnerf_hip_internal.h) -> (vertices (V,3) fp32, ndc (V,3) fp32, vertex_edge (V,) int64, faces (T,3) int32, count (2,) int64 on the device).
+    positions: the (D,H,W,3) fp32 table of node positions; box: (lo, hi) as 2 x 3 numbers, read on the host; neither: vertices are grid coordinates.
+    capacity None: the count runs alone, is read from the device once, and the outputs have exactly V and T rows.  A pair (max_vertices, max_faces):
+    nothing is read from the device, the outputs have that many rows, count holds the true totals and rows past them (or past the capacity) are not
+    written.  classify -> scan -> vertices -> faces, no atomics: two runs give the same bytes."""
+    op = "mesh_extract"
+    _need_no_grad(field, positions, op=op)
+    if not (torch.is_tensor(field) and field.dim() == 3):
+        raise RuntimeError(f"{op}: field must be a (D,H,W) tensor")
+    D, H, W = (int(v) for v in field.shape)
+    dev = field.device
+    p_field = dev_f32(field, f"{op}: field")
+    p_pos = 0
+    if positions is not None:
+        if tuple(positions.shape) != (D, H, W, 3):
+            raise RuntimeError(f"{op}: positions must be ({D},{H},{W},3), got {tuple(positions.shape)}")
+        p_pos = dev_f32(positions, f"{op}: positions")
+    c_box = None
+    if box is not None:
+        vals = [float(v) for v in torch.as_tensor(box, dtype=torch.float32).reshape(-1).tolist()]
+        if len(vals) != 6:
+            raise RuntimeError(f"{op}: box must hold (lo, hi), 2 x 3 numbers")
+        c_box = (ctypes.c_float * 6)(*vals)
+    lib = _lib.lib()
+    ws_bytes = int(lib.mvsnerf_mesh_workspace_bytes(D, H, W))
+    if ws_bytes == 0:
+        raise RuntimeError(f"{op}: a ({D},{H},{W}) field is outside what the kernels index (every dimension >= 2, at most 2^27 nodes)")
+    ws = torch.empty(((ws_bytes + 3) // 4,), device=dev, dtype=torch.int32)
+    count = torch.empty((2,), device=dev, dtype=torch.int64)
+
+    def run(cap_v, cap_f):
+        out = (torch.empty((cap_v, 3), device=dev, dtype=torch.float32), torch.empty((cap_v, 3), device=dev, dtype=torch.float32),
+               torch.empty((cap_v,), device=dev, dtype=torch.int64), torch.empty((cap_f, 3), device=dev, dtype=torch.int32))
+        ptr = [t.data_ptr() if t.numel() else 0 for t in out]            # (an empty tensor has no address to hand over)
+        check(lib.mvsnerf_mesh_extract_fwd(p_field, D, H, W, float(level), p_pos, c_box, cap_v, cap_f, *ptr, count.data_ptr(), ws.data_ptr(),
+                                           stream_ptr()), "mesh_extract_fwd")
+        return out
+
+    if capacity is None:
+        run(0, 0)
+        cap_v, cap_f = (int(v) for v in count.tolist())                  # the one host read
+        if cap_v == 0 and cap_f == 0:
+            return (torch.empty((0, 3), device=dev, dtype=torch.float32), torch.empty((0, 3), device=dev, dtype=torch.float32),
+                    torch.empty((0,), device=dev, dtype=torch.int64), torch.empty((0, 3), device=dev, dtype=torch.int32), count)
+    else:
+        cap_v, cap_f = int(capacity[0]), int(capacity[1])
+        if cap_v < 0 or cap_f < 0:
+            raise RuntimeError(f"{op}: capacity must be a pair of numbers >= 0, got {capacity}")
+    return (*run(cap_v, cap_f), count)
+
+
+def mesh_dirs(vertices, origin):
+    """vertices (n,3) fp32, origin (3,) fp32 on the device -> (n,3) rows vertices - origin (mvsnerf_mesh_dirs_fwd)."""
+    _need_no_grad(vertices, origin, op="mesh_dirs")
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or origin.numel() != 3:
+        raise RuntimeError(f"mesh_dirs: vertices (n,3) and origin (3,), got {tuple(vertices.shape)} and {tuple(origin.shape)}")
+    n = int(vertices.shape[0])
+    out = torch.empty((n, 3), device=vertices.device, dtype=torch.float32)
+    check(_lib.lib().mvsnerf_mesh_dirs_fwd(dev_f32(vertices, "mesh_dirs: vertices") if n else 0, dev_f32(origin, "mesh_dirs: origin"), n,
+                                           out.data_ptr() if n else 0, stream_ptr()), "mesh_dirs_fwd")
+    return out
+
+
+def mesh_rgb_u8(raw):
+    """raw (n,4) fp32 (the MLP's rgb + sigma rows) -> (n,3) uint8 = trunc(clamp(rgb, 0, 1) * 255), NaN -> 0 (mvsnerf_mesh_rgb_u8_fwd: frame_u8's rule)."""
+    _need_no_grad(raw, op="mesh_rgb_u8")
+    if raw.dim() != 2 or raw.shape[1] != 4:
+        raise RuntimeError(f"mesh_rgb_u8: raw must be (n,4), got {tuple(raw.shape)}")
+    n = int(raw.shape[0])
+    out = torch.empty((n, 3), device=raw.device, dtype=torch.uint8)
+    check(_lib.lib().mvsnerf_mesh_rgb_u8_fwd(dev_f32(raw, "mesh_rgb_u8: raw") if n else 0, n, out.data_ptr() if n else 0, stream_ptr()), "mesh_rgb_u8_fwd")
+    return out
