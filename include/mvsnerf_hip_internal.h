@@ -612,6 +612,39 @@ int mvsnerf_mesh_extract_fwd(const float* field, int D, int H, int W, float leve
                              void* stream);
 int mvsnerf_mesh_dirs_fwd(const float* vertices, const float* origin, int64_t n, float* dirs, void* stream);
 int mvsnerf_mesh_rgb_u8_fwd(const float* rgba, int64_t n, unsigned char* rgb, void* stream);
+/* mesh_extract_masked: mesh_extract with a node mask, valid [D][H][W] uint8 (device) or NULL, any non-zero byte = valid.  An owned edge carries a vertex only
+ *   if both its ends are valid and a tetrahedron emits faces only if its four corners are valid; the field is still read at invalid nodes.  Equivalently: the
+ *   unmasked extraction with every vertex whose edge has an invalid end and every face that uses such a vertex dropped, and the rest renumbered (the triangles
+ *   of every tetrahedron case touch all four corners).  Vertices that no surviving face uses are kept; the surface is closed only away from invalid nodes.
+ *   mesh_extract is this entry with valid = NULL.  Codes, workspace and capacities as mesh_extract. */
+int mvsnerf_mesh_extract_masked_fwd(const float* field, const unsigned char* valid, int D, int H, int W, float level, const float* positions,
+                                    const float* box, int64_t cap_vertices, int64_t cap_faces, float* vertices, float* ndc, int64_t* vertex_edge, int* faces,
+                                    int64_t* count, void* workspace, void* stream);
+/* ---- the depth maps of a scene's views -> a truncated signed distance volume (Curless-Levoy / KinectFusion) on a (D,H,W) grid of nodes over a world box, and
+ *      a mesh's vertex colours from it (csrc/tsdf.hip, DESIGN.md 4o, where the definition is written out).  No counterpart in the reference. ----
+ * Conventions: the bank's (depth_consistency above: pixel centres at integer coordinates, depth = camera-space z, w2c [M][3][4], K [M][3][3]) and the mesher's
+ *   (node (i,j,k) = [k][j][i], n = (k H + j) W + i).  box: 6 HOST floats, lo then hi; node position X = lo + ((i,j,k) / (W-1, H-1, D-1)) * (hi - lo), the
+ *   operations of mesh_extract's box mapping.
+ * tsdf_integrate: for a node and each view m of view_ids [n_views] (device int32; NULL: the views 0..M-1; an id outside [0, M) is skipped), in the list's
+ *   order, each step only if the one before held:  1. q = ((w0 X + w1 Y) + w2 Z) + w3 per row of w2c_m, q.z > z_min;  2. u = fx q.x / q.z + cx,
+ *   v = fy q.y / q.z + cy, 0 <= u + 0.5 < W_img, 0 <= v + 0.5 < H_img, the NEAREST pixel x = floor(u + 0.5), y = floor(v + 0.5);  3. d = depth[m][y][x] is
+ *   finite, > 0, valid (when given) != 0 there and, when alpha != 0, the image's alpha byte != 0;  4. sdf = d - q.z >= -trunc;  5. tsum += min(sdf / trunc, 1),
+ *   wsum += 1;  6. if sdf <= trunc: csum[0:3] += images_rgba[m][y][x][0:3], cw += 1.  Outputs: tsdf [D][H][W] fp32 = tsum / wsum (+1 where wsum == 0);
+ *   weight [D][H][W] int32 = wsum; colors [D][H][W][4] uint8 = ((2 csum + cw) / (2 cw) in integers, 255), four zero bytes where cw == 0, one 32-bit store.
+ *   fp32, every operation rounded on its own, IEEE division; one thread per node, no atomics, two runs give the same bytes; pixel indices are 64-bit.
+ * tsdf_vertex_colors: row r < min(count[0], rows) (count: device int64) of colors [rows][3] uint8 from the ends n = vertex_edge[r] >> 3 and its neighbour
+ *   along owned edge vertex_edge[r] & 7: t = (0 - f0) / (f1 - f0) on f = -tsdf (0.5 when an end is not finite), byte = clamp(floor(c0 + t (c1 - c0) + 0.5),
+ *   0, 255) per channel of node_colors [D][H][W][4]; only one end with alpha 255: that end's bytes; neither, or a key outside the grid: 0.  Rows past the
+ *   count are not written.  rows == 0 launches nothing.
+ * MVSNERF_EINVAL: a NULL pointer that is needed (valid and view_ids may be NULL), rows < 0; MVSNERF_EUNSUPPORTED: D, H or W < 2, D H W > 2^27, trunc not
+ *   finite or <= 0, z_min not finite or < 0, a box that is not finite, M < 1, M or n_views >= 2^22, n_views < 1 with view_ids, an image smaller than 1 x 1
+ *   or larger than 2^24 in a dimension, rows >= 2^31; MVSNERF_EALIGN: a float / int32 / RGBA array not 4-byte, vertex_edge or count not 8-byte aligned.
+ *   All before the first launch. */
+int mvsnerf_tsdf_integrate_fwd(const float* depth, const unsigned char* valid, const unsigned char* images_rgba, int alpha, const float* w2c, const float* K,
+                               const int* view_ids, int n_views, int M, int H_img, int W_img, const float* box, int D, int H, int W, float trunc,
+                               float z_min, float* tsdf, int* weight, unsigned char* colors, void* stream);
+int mvsnerf_tsdf_vertex_colors_fwd(const float* tsdf, const unsigned char* node_colors, int D, int H, int W, const int64_t* vertex_edge,
+                                   const int64_t* count, int64_t rows, unsigned char* colors, void* stream);
 
 #ifdef __cplusplus
 }

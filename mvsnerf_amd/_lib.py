@@ -303,6 +303,10 @@ SIGNATURES = {
     "mvsnerf_mesh_extract_fwd": (_c_i, [_c_fp] + [_c_i] * 3 + [ctypes.c_float, _c_fp, ctypes.POINTER(ctypes.c_float), _c_l, _c_l] + [_c_fp] * 7),
     "mvsnerf_mesh_dirs_fwd": (_c_i, [_c_fp, _c_fp, _c_l, _c_fp, _c_fp]),
     "mvsnerf_mesh_rgb_u8_fwd": (_c_i, [_c_fp, _c_l, _c_fp, _c_fp]),
+    "mvsnerf_mesh_extract_masked_fwd": (_c_i, [_c_fp, _c_fp] + [_c_i] * 3 + [ctypes.c_float, _c_fp, ctypes.POINTER(ctypes.c_float), _c_l, _c_l] + [_c_fp] * 7),
+    "mvsnerf_tsdf_integrate_fwd": (_c_i, [_c_fp] * 3 + [_c_i] + [_c_fp] * 3 + [_c_i] * 4 + [ctypes.POINTER(ctypes.c_float)] + [_c_i] * 3
+                                   + [ctypes.c_float, ctypes.c_float] + [_c_fp] * 4),
+    "mvsnerf_tsdf_vertex_colors_fwd": (_c_i, [_c_fp, _c_fp] + [_c_i] * 3 + [_c_fp, _c_fp, _c_l, _c_fp, _c_fp]),
 }
 
 _lib = None

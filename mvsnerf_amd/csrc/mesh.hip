@@ -15,6 +15,9 @@
 // mesh_faces_kernel      (a launch of its own: it reads vbase and mask of nodes of other workgroups) in-workgroup scan of the cells' face counts + the
 //                        offset; the case of each tetrahedron comes from MT_CASE; the vertex of edge e of node m is vbase[m] + popcount(mask[m] & ((1 << e) - 1)).
 // mesh_dirs_kernel, mesh_rgb_u8_kernel   rows vertex - origin; bytes trunc(clamp(rgb, 0, 1) * 255) of the first three of four floats (frames.hip's rule).
+// valid (optional, a byte per node, non-zero = valid): an owned edge carries a vertex only if both its ends are valid, a tetrahedron emits faces only if its
+// four corners are valid.  The field is still read at invalid nodes; nothing that touches them survives.  The same as the unmasked extraction with every
+// vertex on an edge with an invalid end and every face using such a vertex dropped, and the rest renumbered.
 // No atomics: the order is what the scans produce, two runs give the same bytes.  Rows >= capacity are never written.
 // Arithmetic: fp32, every operation rounded on its own (no contraction), IEEE division - what numpy does on float32 arrays.
 #include "common.h"
@@ -68,11 +71,13 @@ struct MeshGrid {
     const float* field;                // [D][H][W]
     int D, H, W, HW, N;                // N = D H W <= 2^27
     float level;
+    const unsigned char* valid;        // [D][H][W] or NULL: a node with a zero byte carries no vertex and no face (the mask)
 };
 
 __device__ __forceinline__ int corner_offset(const MeshGrid& g, int c) { return (c & 1) + ((c >> 1) & 1) * g.W + (c >> 2) * g.HW; }
 
-// bits 0..7: corner c of the cell at node n is inside; bits 8..15: corner c is in the grid.  Reads nothing outside the field.
+// bits 0..7: corner c of the cell at node n is inside; bits 8..15: corner c is in the grid; bits 16..23: corner c is valid (every corner in the grid
+// without a mask).  Reads nothing outside the field.
 __device__ __forceinline__ unsigned cell_corners(const MeshGrid& g, int n, int i, int j, int k)
 {
     const bool hx = i + 1 < g.W, hy = j + 1 < g.H, hz = k + 1 < g.D;
@@ -82,7 +87,8 @@ __device__ __forceinline__ unsigned cell_corners(const MeshGrid& g, int n, int i
         const bool in_grid = (!(c & 1) || hx) && (!(c & 2) || hy) && (!(c & 4) || hz);
         if (in_grid) {
             const float s = g.field[n + corner_offset(g, c)];
-            bits |= (0x100u | (s >= g.level ? 1u : 0u)) << c;
+            const unsigned ok = (!g.valid || g.valid[n + corner_offset(g, c)] != 0) ? 0x10000u : 0u;
+            bits |= (ok | 0x100u | (s >= g.level ? 1u : 0u)) << c;
         }
     }
     return bits;
@@ -92,14 +98,18 @@ __device__ __forceinline__ unsigned owned_edges(unsigned corners)
 {
     const unsigned own = corners & 1u;
     unsigned mask = 0u;
+    if (!((corners >> 16) & 1u)) return mask;                            // an invalid owner
 #pragma unroll
     for (int c = 1; c < 8; ++c)
-        if (((corners >> (8 + c)) & 1u) && ((corners >> c) & 1u) != own) mask |= 1u << edge_of(c);
+        if (((corners >> (16 + c)) & 1u) && ((corners >> c) & 1u) != own) mask |= 1u << edge_of(c);     // (valid implies in the grid)
     return mask;
 }
 
+// 0 (no face) for a tetrahedron with an invalid corner: every triangle of every case touches all four corners
 __device__ __forceinline__ unsigned tet_case(unsigned corners, int p)
 {
+    const unsigned need = 0x10000u | (0x10000u << tet_corner(p, 1)) | (0x10000u << tet_corner(p, 2)) | 0x800000u;
+    if ((corners & need) != need) return 0u;
     return (corners & 1u) | (((corners >> tet_corner(p, 1)) & 1u) << 1) | (((corners >> tet_corner(p, 2)) & 1u) << 2) | (((corners >> 7) & 1u) << 3);
 }
 __device__ __forceinline__ int case_triangles(unsigned cs)
@@ -333,9 +343,9 @@ extern "C" size_t mvsnerf_mesh_workspace_bytes(int D, int H, int W)
     return (size_t)n * 5 + (size_t)mesh_blocks(n) * 4 * sizeof(int);
 }
 
-extern "C" int mvsnerf_mesh_extract_fwd(const float* field, int D, int H, int W, float level, const float* positions, const float* box,
-                                        int64_t cap_vertices, int64_t cap_faces, float* vertices, float* ndc, int64_t* vertex_edge, int* faces,
-                                        int64_t* count, void* workspace, void* stream)
+extern "C" int mvsnerf_mesh_extract_masked_fwd(const float* field, const unsigned char* valid, int D, int H, int W, float level, const float* positions,
+                                               const float* box, int64_t cap_vertices, int64_t cap_faces, float* vertices, float* ndc, int64_t* vertex_edge,
+                                               int* faces, int64_t* count, void* workspace, void* stream)
 {
     if (!field || !count || !workspace || cap_vertices < 0 || cap_faces < 0) return MVSNERF_EINVAL;
     if (cap_vertices > 0 && (!vertices || !ndc || !vertex_edge)) return MVSNERF_EINVAL;
@@ -351,7 +361,7 @@ extern "C" int mvsnerf_mesh_extract_fwd(const float* field, int D, int H, int W,
     int* counts = vbase + n;                                             // vcount | fcount
     int* offsets = counts + 2 * nb;                                      // voffset | foffset
     unsigned char* mask = reinterpret_cast<unsigned char*>(offsets + 2 * nb);
-    const MeshGrid g{field, D, H, W, H * W, (int)n, level};
+    const MeshGrid g{field, D, H, W, H * W, (int)n, level, valid};
     mesh_classify_kernel<<<(unsigned)nb, MT_THREADS, 0, st>>>(g, mask, counts, counts + nb);
     MVS_LAUNCH_CHECK();
     mesh_scan_kernel<<<1, MT_SCAN_THREADS, 0, st>>>(counts, (int)nb, offsets, count);
@@ -366,6 +376,14 @@ extern "C" int mvsnerf_mesh_extract_fwd(const float* field, int D, int H, int W,
     mesh_faces_kernel<<<(unsigned)nb, MT_THREADS, 0, st>>>(g, mask, vbase, offsets + nb, cap_faces, faces);
     MVS_LAUNCH_CHECK();
     return MVSNERF_OK;
+}
+
+extern "C" int mvsnerf_mesh_extract_fwd(const float* field, int D, int H, int W, float level, const float* positions, const float* box,
+                                        int64_t cap_vertices, int64_t cap_faces, float* vertices, float* ndc, int64_t* vertex_edge, int* faces,
+                                        int64_t* count, void* workspace, void* stream)
+{
+    return mvsnerf_mesh_extract_masked_fwd(field, nullptr, D, H, W, level, positions, box, cap_vertices, cap_faces, vertices, ndc, vertex_edge, faces, count,
+                                           workspace, stream);
 }
 
 extern "C" int mvsnerf_mesh_dirs_fwd(const float* vertices, const float* origin, int64_t n, float* dirs, void* stream)

@@ -8,6 +8,9 @@ all on the device (csrc/depth_fusion.hip).  The reference has no counterpart; th
 Geometry from density: `extract_mesh` turns a (D,H,W) field - a scene's node density, ops.node_density - into the triangle mesh of its level set by marching
 tetrahedra over the Kuhn split of every cell (csrc/mesh.hip), `vertex_colors` asks the radiance network for a colour per vertex and `scene_mesh`
 does both for a fine-tuned scene.  Not pinned against any external mesher either.
+
+Geometry from depth, as a surface: `fuse_tsdf` integrates the depth maps into a truncated signed distance volume over a world box (csrc/tsdf.hip, DESIGN.md
+4o) and `tsdf_mesh` meshes its zero level, unobserved space masked, with colours from the volume.
 """
 import math
 
@@ -79,6 +82,28 @@ def render_depths(system, scene, **render_rays_kw):
     return torch.stack(out).contiguous()
 
 
+def _depth_args(scene, depths, valid, who):
+    """The refusals of a bank's depth maps and their valid mask, shared by fuse_depths and fuse_tsdf."""
+    M, (H, W) = scene.n_views, scene.hw
+    if not torch.is_tensor(depths) or depths.dtype != torch.float32:
+        raise TypeError(f"{who}: depths must be a float32 tensor of shape ({M},{H},{W}), got {getattr(depths, 'dtype', type(depths).__name__)}")
+    if tuple(depths.shape) != (M, H, W):
+        raise ValueError(f"{who}: depths must be ({M},{H},{W}), one map per view of the bank, got {tuple(depths.shape)}")
+    if depths.device != scene.images.device:
+        raise ValueError(f"{who}: depths must be on the bank's device {scene.images.device}, got {depths.device}")
+    if valid is not None:
+        if not torch.is_tensor(valid) or valid.dtype not in (torch.bool, torch.uint8):
+            raise TypeError(f"{who}: valid must be a bool or uint8 tensor of shape ({M},{H},{W}), got {getattr(valid, 'dtype', type(valid).__name__)}")
+        if tuple(valid.shape) != (M, H, W):
+            raise ValueError(f"{who}: valid must be ({M},{H},{W}), like depths, got {tuple(valid.shape)}")
+        if valid.device != scene.images.device:
+            raise ValueError(f"{who}: valid must be on the bank's device {scene.images.device}, got {valid.device}")
+
+
+def _u8(mask):
+    return (mask.view(torch.uint8) if mask.dtype == torch.bool else mask).contiguous()
+
+
 @torch.no_grad()
 def fuse_depths(scene, depths, src_ids=None, n_src=4, pix_thr=1.0, rel_thr=0.01, min_views=3, valid=None, capacity=None):
     """The M depth maps of `scene` (a SceneRays) -> a PointCloud.
@@ -93,19 +118,7 @@ def fuse_depths(scene, depths, src_ids=None, n_src=4, pix_thr=1.0, rel_thr=0.01,
                     a count above capacity means the cloud was cut and the call wants repeating)."""
     M, (H, W) = scene.n_views, scene.hw
     dev = scene.device
-    if not torch.is_tensor(depths) or depths.dtype != torch.float32:
-        raise TypeError(f"fuse_depths: depths must be a float32 tensor of shape ({M},{H},{W}), got {getattr(depths, 'dtype', type(depths).__name__)}")
-    if tuple(depths.shape) != (M, H, W):
-        raise ValueError(f"fuse_depths: depths must be ({M},{H},{W}), one map per view of the bank, got {tuple(depths.shape)}")
-    if depths.device != scene.images.device:
-        raise ValueError(f"fuse_depths: depths must be on the bank's device {scene.images.device}, got {depths.device}")
-    if valid is not None:
-        if not torch.is_tensor(valid) or valid.dtype not in (torch.bool, torch.uint8):
-            raise TypeError(f"fuse_depths: valid must be a bool or uint8 tensor of shape ({M},{H},{W}), got {getattr(valid, 'dtype', type(valid).__name__)}")
-        if tuple(valid.shape) != (M, H, W):
-            raise ValueError(f"fuse_depths: valid must be ({M},{H},{W}), like depths, got {tuple(valid.shape)}")
-        if valid.device != scene.images.device:
-            raise ValueError(f"fuse_depths: valid must be on the bank's device {scene.images.device}, got {valid.device}")
+    _depth_args(scene, depths, valid, "fuse_depths")
     if H < 2 or W < 2:
         raise ValueError(f"fuse_depths: views of at least 2 x 2 pixels (a bilinear cell), got {H} x {W}")
     ids = _source_ids(scene, src_ids, n_src)
@@ -121,7 +134,7 @@ def fuse_depths(scene, depths, src_ids=None, n_src=4, pix_thr=1.0, rel_thr=0.01,
     w2cs = torch.from_numpy(np.ascontiguousarray(w2c, dtype=np.float32)).to(dev)
     with torch.cuda.device(dev):
         src = torch.from_numpy(ids).to(dev)
-        v8 = None if valid is None else (valid.view(torch.uint8) if valid.dtype == torch.bool else valid).contiguous()
+        v8 = None if valid is None else _u8(valid)
         seen, fused, mask = ops.depth_consistency(scene.images, scene.c2ws, w2cs, scene.intrinsics, depths.contiguous(), src, pix_thr, rel_thr, min_views,
                                                   valid=v8, alpha=scene.has_alpha)
         bank = (scene.images, scene.c2ws, scene.intrinsics, fused, seen, mask)
@@ -145,7 +158,7 @@ class TriangleMesh:
         self.vertices, self.ndc, self.faces, self.vertex_edge, self.count, self.colors = vertices, ndc, faces, vertex_edge, count, colors
 
 
-def _mesh_args(field, level, positions, box, capacity, who):
+def _mesh_args(field, level, positions, box, capacity, who, valid=None):
     """The refusals of extract_mesh, before the library is touched -> (level, box as a (2,3) fp32 host tensor | None, capacity pair | None)."""
     if not torch.is_tensor(field) or field.dtype != torch.float32:
         raise TypeError(f"{who}: field must be a float32 tensor of shape (D,H,W), got {getattr(field, 'dtype', type(field).__name__)}")
@@ -171,6 +184,13 @@ def _mesh_args(field, level, positions, box, capacity, who):
         if box.numel() != 6 or not bool(torch.isfinite(box).all()):
             raise ValueError(f"{who}: box must be (lo, hi), 2 x 3 finite numbers, got {tuple(box.shape)}")
         box = box.reshape(2, 3)
+    if valid is not None:
+        if not torch.is_tensor(valid) or valid.dtype not in (torch.bool, torch.uint8):
+            raise TypeError(f"{who}: valid must be a bool or uint8 tensor of shape ({D},{H},{W}), got {getattr(valid, 'dtype', type(valid).__name__)}")
+        if tuple(valid.shape) != (D, H, W):
+            raise ValueError(f"{who}: valid must be ({D},{H},{W}), a byte per node, got {tuple(valid.shape)}")
+        if valid.device != field.device:
+            raise ValueError(f"{who}: valid must be on the field's device {field.device}, got {valid.device}")
     if capacity is not None:
         try:
             cap = (int(capacity[0]), int(capacity[1]))
@@ -184,7 +204,7 @@ def _mesh_args(field, level, positions, box, capacity, who):
 
 
 @torch.no_grad()
-def extract_mesh(field, level, positions=None, box=None, capacity=None):
+def extract_mesh(field, level, positions=None, box=None, capacity=None, valid=None):
     """The level set of a scalar field on a grid as a TriangleMesh: marching tetrahedra over the Kuhn split of every cell (csrc/mesh.hip).
         field       (D,H,W) fp32 on the GPU, e.g. a scene's node density; a node is inside iff field >= level (NaN: outside; write -inf into nodes to mask)
         level       finite
@@ -192,13 +212,99 @@ def extract_mesh(field, level, positions=None, box=None, capacity=None):
         box         (lo, hi), 2 x 3 numbers: vertices = lo + ndc * (hi - lo) (a box volume's bbox_3d).  Neither: vertices are grid coordinates.
         capacity    None: the counts are read from the device once and the arrays have exactly V and T rows.  A pair (max_vertices, max_faces): nothing
                     is read from the device, mesh.count holds the true totals and rows past them are not written.
+        valid       (D,H,W) bool | uint8 on the field's device, non-zero = valid, or None: an edge carries a vertex only if both its ends are valid and a
+                    tetrahedron emits faces only if its four corners are valid - the unmasked mesh with every vertex on an edge with an invalid end and
+                    every face using such a vertex dropped.  Vertices no surviving face uses are kept; the surface is open along invalid nodes.
     The surface is closed and consistently oriented wherever it does not touch the grid border; a positions table with a mirrored mapping flips the
     winding."""
-    level, box, capacity = _mesh_args(field, level, positions, box, capacity, "extract_mesh")
+    level, box, capacity = _mesh_args(field, level, positions, box, capacity, "extract_mesh", valid)
     with torch.cuda.device(field.device):
         vertices, ndc, vertex_edge, faces, count = ops.mesh_extract(field.contiguous(), level, None if positions is None else positions.contiguous(),
-                                                                    box, capacity)
+                                                                    box, capacity, valid=None if valid is None else _u8(valid))
     return TriangleMesh(vertices, ndc, faces, vertex_edge, count)
+
+
+class TSDFVolume:
+    """What fuse_tsdf returns.
+        tsdf (D,H,W) fp32: the mean truncated signed distance in units of trunc, positive in front of the surface, at most 1; +1 where nothing was seen
+        weight (D,H,W) int32: the number of views that contributed; colors (D,H,W,4) uint8: the mean RGB of the views within trunc of the surface and
+        alpha 255, or four zero bytes where there is none
+        box (2,3) fp32 on the host: (lo, hi), the world positions of nodes (0,0,0) and (W-1,H-1,D-1); trunc: the truncation distance in world units"""
+
+    def __init__(self, tsdf, weight, colors, box, trunc):
+        self.tsdf, self.weight, self.colors, self.box, self.trunc = tsdf, weight, colors, box, trunc
+
+
+@torch.no_grad()
+def fuse_tsdf(scene, depths, box, dims, trunc=None, valid=None, views=None, z_min=0.0):
+    """The M depth maps of `scene` (a SceneRays) -> a TSDFVolume: every node of a dims = (D,H,W) grid over the world box is projected into every view and
+    takes the truncated difference between the depth of its NEAREST pixel and its own (csrc/tsdf.hip).
+        depths, valid   as fuse_depths takes them: holes are depths that are not finite or <= 0, pixels with valid == 0 and pixels of alpha 0
+        box         (lo, hi), 2 x 3 finite numbers with hi > lo: node (i,j,k) sits at lo + (i/(W-1), j/(H-1), k/(D-1)) * (hi - lo)
+        dims        (D,H,W), each >= 2, at most 2^27 nodes
+        trunc       the truncation distance in world units; None: 3 x the longest voxel edge
+        views       a list of distinct view ids (integrated in ascending order), default every view
+        z_min       a node nearer to a camera than this (camera-space z) takes nothing from it
+    Not pinned against any external fusion tool."""
+    who = "fuse_tsdf"
+    M = scene.n_views
+    _depth_args(scene, depths, valid, who)
+    box = torch.as_tensor(box).detach().to("cpu", torch.float32)
+    if box.numel() != 6 or not bool(torch.isfinite(box).all()):
+        raise ValueError(f"{who}: box must be (lo, hi), 2 x 3 finite numbers, got {tuple(box.shape)}")
+    box = box.reshape(2, 3)
+    if not bool((box[1] > box[0]).all()):
+        raise ValueError(f"{who}: box must have hi > lo on every axis, got lo {box[0].tolist()}, hi {box[1].tolist()}")
+    try:
+        D, H, W = (int(v) for v in dims)
+        ok = len(dims) == 3 and all(int(v) == v for v in dims) and min(D, H, W) >= 2
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"{who}: dims must be three integers (D,H,W), each >= 2, got {dims!r}")
+    if D * H * W > ops.MESH_MAX_NODES:
+        raise ValueError(f"{who}: at most 2^27 nodes (the mesher's vertex and face numbers are int32), got {D} x {H} x {W}")
+    if trunc is None:
+        trunc = 3.0 * max(float(box[1, 0] - box[0, 0]) / (W - 1), float(box[1, 1] - box[0, 1]) / (H - 1), float(box[1, 2] - box[0, 2]) / (D - 1))
+    trunc, z_min = float(trunc), float(z_min)
+    if not (math.isfinite(trunc) and trunc > 0):
+        raise ValueError(f"{who}: trunc (world units) must be finite and > 0, got {trunc}")
+    if not (math.isfinite(z_min) and z_min >= 0):
+        raise ValueError(f"{who}: z_min must be finite and >= 0, got {z_min}")
+    ids = None
+    if views is not None:
+        ids = views.cpu().numpy() if torch.is_tensor(views) else np.asarray(views)
+        if ids.ndim != 1 or ids.size < 1 or not np.issubdtype(ids.dtype, np.integer):
+            raise ValueError(f"{who}: views must be a 1-D list of at least one integer view id, got shape {ids.shape} {ids.dtype}")
+        if ids.min() < 0 or ids.max() >= M or len(np.unique(ids)) != ids.size:
+            raise ValueError(f"{who}: views must hold distinct view ids in [0, {M}), got {ids.tolist()}")
+        ids = np.sort(ids).astype(np.int32)
+
+    dev = scene.device
+    w2c = np.linalg.inv(scene._c2w64.numpy())[:, :3, :4]                                 # float64 on the host, rounded once
+    w2cs = torch.from_numpy(np.ascontiguousarray(w2c, dtype=np.float32)).to(dev)
+    with torch.cuda.device(dev):
+        tsdf, weight, colors = ops.tsdf_integrate(scene.images, w2cs, scene.intrinsics, depths.contiguous(), box, (D, H, W), trunc,
+                                                  valid=None if valid is None else _u8(valid), alpha=scene.has_alpha,
+                                                  views=None if ids is None else torch.from_numpy(ids).to(dev), z_min=z_min)
+    return TSDFVolume(tsdf, weight, colors, box, trunc)
+
+
+@torch.no_grad()
+def tsdf_mesh(vol, min_weight=1, colors=True, capacity=None):
+    """The zero level of a TSDFVolume as a TriangleMesh in the volume's world box: extract_mesh(-vol.tsdf, 0.0, box=vol.box, valid=vol.weight >= min_weight),
+    so only space that at least min_weight views observed carries surface and the faces are counter-clockwise seen from the observed side.
+    colors: mesh.colors = the end nodes' colours interpolated at each vertex (ops.tsdf_vertex_colors); rows past the count stay 0."""
+    if not isinstance(vol, TSDFVolume):
+        raise TypeError(f"tsdf_mesh: a TSDFVolume (fuse_tsdf's result) expected, got {type(vol).__name__}")
+    if int(min_weight) != min_weight or int(min_weight) < 1:
+        raise ValueError(f"tsdf_mesh: min_weight must be an integer >= 1 (a node nobody observed has no distance), got {min_weight}")
+    level, box, capacity = _mesh_args(vol.tsdf, 0.0, None, vol.box, capacity, "tsdf_mesh")
+    with torch.cuda.device(vol.tsdf.device):
+        mesh = extract_mesh(-vol.tsdf, level, box=box, valid=vol.weight >= int(min_weight), capacity=capacity)
+        if colors:
+            mesh.colors = ops.tsdf_vertex_colors(vol.tsdf, vol.colors, mesh.vertex_edge, mesh.count)
+    return mesh
 
 
 def _scene_sources(system):

@@ -2089,13 +2089,15 @@ def point_cloud(images, c2ws, intrinsics, fused, seen, mask, capacity, out=None)
 MESH_MAX_NODES = 1 << 27
 
 
-def mesh_extract(field, level, positions=None, box=None, capacity=None):
+def mesh_extract(field, level, positions=None, box=None, capacity=None, valid=None):
     """Marching tetrahedra over the Kuhn split of the cells of field (D,H,W) fp32 (mvsnerf_mesh_extract_fwd; the definition is in DESIGN.md 4n and
     include/mvsnerf_hip_internal.h) -> (vertices (V,3) fp32, ndc (V,3) fp32, vertex_edge (V,) int64, faces (T,3) int32, count (2,) int64 on the device).
     positions: the (D,H,W,3) fp32 table of node positions; box: (lo, hi) as 2 x 3 numbers, read on the host; neither: vertices are grid coordinates.
     capacity None: the count runs alone, is read from the device once, and the outputs have exactly V and T rows.  A pair (max_vertices, max_faces):
     nothing is read from the device, the outputs have that many rows, count holds the true totals and rows past them (or past the capacity) are not
-    written.  classify -> scan -> vertices -> faces, no atomics: two runs give the same bytes."""
+    written.  classify -> scan -> vertices -> faces, no atomics: two runs give the same bytes.
+    valid: a contiguous (D,H,W) uint8 node mask on the field's device (mvsnerf_mesh_extract_masked_fwd): only edges between valid nodes carry vertices and
+    only tetrahedra of four valid nodes emit faces."""
     op = "mesh_extract"
     _need_no_grad(field, positions, op=op)
     if not (torch.is_tensor(field) and field.dim() == 3):
@@ -2108,6 +2110,7 @@ def mesh_extract(field, level, positions=None, box=None, capacity=None):
         if tuple(positions.shape) != (D, H, W, 3):
             raise RuntimeError(f"{op}: positions must be ({D},{H},{W},3), got {tuple(positions.shape)}")
         p_pos = dev_f32(positions, f"{op}: positions")
+    p_valid = 0 if valid is None else _fusion_map(valid, torch.uint8, (D, H, W), dev, "valid", op)
     c_box = None
     if box is not None:
         vals = [float(v) for v in torch.as_tensor(box, dtype=torch.float32).reshape(-1).tolist()]
@@ -2125,8 +2128,8 @@ def mesh_extract(field, level, positions=None, box=None, capacity=None):
         out = (torch.empty((cap_v, 3), device=dev, dtype=torch.float32), torch.empty((cap_v, 3), device=dev, dtype=torch.float32),
                torch.empty((cap_v,), device=dev, dtype=torch.int64), torch.empty((cap_f, 3), device=dev, dtype=torch.int32))
         ptr = [t.data_ptr() if t.numel() else 0 for t in out]            # (an empty tensor has no address to hand over)
-        check(lib.mvsnerf_mesh_extract_fwd(p_field, D, H, W, float(level), p_pos, c_box, cap_v, cap_f, *ptr, count.data_ptr(), ws.data_ptr(),
-                                           stream_ptr()), "mesh_extract_fwd")
+        check(lib.mvsnerf_mesh_extract_masked_fwd(p_field, p_valid, D, H, W, float(level), p_pos, c_box, cap_v, cap_f, *ptr, count.data_ptr(),
+                                                  ws.data_ptr(), stream_ptr()), "mesh_extract_masked_fwd")
         return out
 
     if capacity is None:
@@ -2162,4 +2165,72 @@ def mesh_rgb_u8(raw):
     n = int(raw.shape[0])
     out = torch.empty((n, 3), device=raw.device, dtype=torch.uint8)
     check(_lib.lib().mvsnerf_mesh_rgb_u8_fwd(dev_f32(raw, "mesh_rgb_u8: raw") if n else 0, n, out.data_ptr() if n else 0, stream_ptr()), "mesh_rgb_u8_fwd")
+    return out
+
+
+# ------------------------------------------------------------------ depth maps -> a TSDF volume (csrc/tsdf.hip)
+def tsdf_integrate(images, w2cs, intrinsics, depths, box, dims, trunc, valid=None, alpha=True, views=None, z_min=0.0):
+    """The M depth maps of a bank integrated into a truncated signed distance volume over the world box (lo, hi) (mvsnerf_tsdf_integrate_fwd; the
+    definition is in DESIGN.md 4o and include/mvsnerf_hip_internal.h): depths (M,H,W) fp32, w2cs (M,3,4) the inverses of the bank's poses, valid (M,H,W)
+    uint8 | None, views a 1-D int32 tensor of view ids on the device (integrated in its order) | None for every view, dims = (D,H,W) nodes ->
+    (tsdf (D,H,W) fp32, weight (D,H,W) int32, colors (D,H,W,4) uint8).  alpha=False leaves the bank's alpha bytes untested.  One launch, one thread per
+    node, no atomics, every output element written."""
+    op = "tsdf_integrate"
+    _need_no_grad(depths, w2cs, intrinsics, op=op)
+    if not (torch.is_tensor(images) and images.is_cuda and images.dtype == torch.uint8 and images.dim() == 4 and images.shape[-1] == 4
+            and images.is_contiguous()):
+        raise RuntimeError(f"{op}: images must be a contiguous (M,H,W,4) uint8 tensor on the GPU (SceneRays.images)")
+    M, H, W = (int(v) for v in images.shape[:3])
+    dev = images.device
+    if dev.index != torch.cuda.current_device():
+        raise RuntimeError(f"{op}: the bank is on {dev} but the current device is cuda:{torch.cuda.current_device()}")
+    if tuple(w2cs.shape) != (M, 3, 4) or tuple(intrinsics.shape) != (M, 3, 3):
+        raise RuntimeError(f"{op}: w2cs ({M},3,4) and intrinsics ({M},3,3) expected, got {tuple(w2cs.shape)}, {tuple(intrinsics.shape)}")
+    p_depth = _fusion_map(depths, torch.float32, (M, H, W), dev, "depths", op)
+    p_valid = 0 if valid is None else _fusion_map(valid, torch.uint8, (M, H, W), dev, "valid", op)
+    p_views, n_views = 0, M
+    if views is not None:
+        if not (torch.is_tensor(views) and views.dim() == 1 and views.numel() >= 1):
+            raise RuntimeError(f"{op}: views must be a 1-D tensor of at least one view id")
+        n_views = int(views.numel())
+        p_views = _fusion_map(views, torch.int32, (n_views,), dev, "views", op)
+    vals = [float(v) for v in torch.as_tensor(box, dtype=torch.float32).reshape(-1).tolist()]
+    if len(vals) != 6:
+        raise RuntimeError(f"{op}: box must hold (lo, hi), 2 x 3 numbers")
+    c_box = (ctypes.c_float * 6)(*vals)
+    D, Hn, Wn = (int(v) for v in dims)
+    if min(D, Hn, Wn) < 2 or D * Hn * Wn > MESH_MAX_NODES:
+        raise RuntimeError(f"{op}: a ({D},{Hn},{Wn}) grid is outside what the kernels index (every dimension >= 2, at most 2^27 nodes)")
+    c = _Keep()
+    tsdf = torch.empty((D, Hn, Wn), device=dev, dtype=torch.float32)
+    weight = torch.empty((D, Hn, Wn), device=dev, dtype=torch.int32)
+    colors = torch.empty((D, Hn, Wn, 4), device=dev, dtype=torch.uint8)
+    check(_lib.lib().mvsnerf_tsdf_integrate_fwd(p_depth, p_valid, images.data_ptr(), int(bool(alpha)), c(w2cs, "w2cs"), c(intrinsics, "intrinsics"), p_views,
+                                                n_views, M, H, W, c_box, D, Hn, Wn, float(trunc), float(z_min), tsdf.data_ptr(), weight.data_ptr(),
+                                                colors.data_ptr(), stream_ptr()), "tsdf_integrate_fwd")
+    return tsdf, weight, colors
+
+
+def tsdf_vertex_colors(tsdf, colors, vertex_edge, count):
+    """tsdf (D,H,W) fp32 and colors (D,H,W,4) uint8 of a TSDF volume, vertex_edge (rows,) int64 and count (>= 1,) int64 of a mesh of its zero level, all on
+    one device -> (rows,3) uint8: the two end nodes' colours interpolated at the zero crossing of the edge (mvsnerf_tsdf_vertex_colors_fwd).  Rows past
+    min(count[0], rows) are left 0; nothing is read from the device."""
+    op = "tsdf_vertex_colors"
+    _need_no_grad(tsdf, op=op)
+    if not (torch.is_tensor(tsdf) and tsdf.dim() == 3):
+        raise RuntimeError(f"{op}: tsdf must be a (D,H,W) tensor")
+    D, H, W = (int(v) for v in tsdf.shape)
+    dev = tsdf.device
+    p_tsdf = dev_f32(tsdf, f"{op}: tsdf")
+    p_col = _fusion_map(colors, torch.uint8, (D, H, W, 4), dev, "colors", op)
+    if not (torch.is_tensor(vertex_edge) and vertex_edge.dim() == 1):
+        raise RuntimeError(f"{op}: vertex_edge must be a (rows,) tensor")
+    rows = int(vertex_edge.shape[0])
+    p_edge = _fusion_map(vertex_edge, torch.int64, (rows,), dev, "vertex_edge", op)
+    if not (torch.is_tensor(count) and count.dtype == torch.int64 and count.device == dev and count.dim() == 1 and count.numel() >= 1
+            and count.is_contiguous()):
+        raise RuntimeError(f"{op}: count must be a contiguous int64 tensor of at least one element on {dev} (TriangleMesh.count)")
+    out = torch.zeros((rows, 3), device=dev, dtype=torch.uint8)
+    check(_lib.lib().mvsnerf_tsdf_vertex_colors_fwd(p_tsdf, p_col, D, H, W, p_edge if rows else 0, count.data_ptr(), rows, out.data_ptr() if rows else 0,
+                                                    stream_ptr()), "tsdf_vertex_colors_fwd")
     return out
