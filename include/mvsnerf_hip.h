@@ -162,6 +162,8 @@ int mvsnerf_planesweep_costvar_bwd(const float* feats_cl, const float* proj, con
 /* The same gradient with an ORDER-INDEPENDENT reduction: the source views' sums are accumulated in 64-bit fixed point (integer atomics commute;
  * the scale is derived on the device from max |g_cost| * max |feats|, a contribution is rounded to 2^-36 of the largest possible one), then
  * added to g_feats_cl.  Two runs - and N ranks against one - give bit-identical results; ~0.1 ms slower at config 3 (two extra passes).
+ * The scale comes from the largest FINITE magnitudes; a column sum that is inf or NaN is added to g_feats_cl by a float atomic, so the elements that
+ * mvsnerf_planesweep_costvar_bwd makes non-finite are non-finite here too.
  * workspace_zeroed: mvsnerf_planesweep_costvar_bwd_det_workspace_words(V, C, H, W) int64 words, 8-byte aligned, zeroed before every call. */
 size_t mvsnerf_planesweep_costvar_bwd_det_workspace_words(int V, int C, int H, int W);
 int mvsnerf_planesweep_costvar_bwd_det(const float* feats_cl, const float* proj, const float* depth, int V, int C, int H, int W, int D, int pad,
@@ -364,8 +366,11 @@ int mvsnerf_composite_bwd(const float* raw, const float* z, int64_t N, int S, in
 int mvsnerf_volume_sample_bwd(int D, int H, int W, int C, const float* ndc, int64_t P,
                               const float* g, int g_stride, float* gvol, void* stream);
 /* The same gradient with an ORDER-INDEPENDENT reduction (ABI v12; like mvsnerf_planesweep_costvar_bwd_det): contributions are accumulated in 64-bit fixed point
- * (integer atomics commute; scale from max |g| found on the device: a contribution resolves 2^-40 of the largest one), then added to gvol.  Two runs - and N ranks
- * against one - give bit-identical volume gradients; two extra passes (max, finish) and 8 bytes of zeroed workspace per volume element.
+ * (integer atomics commute; scale from max |g| found on the device: a contribution resolves 2^-40 of the largest one), then added to gvol.  One call gives the
+ * same bits whatever the order of its rows; calls on parts of the rows do NOT add up to the call on all of them (a scale and a float addition per call), so N
+ * ranks reproduce one rank by scattering all rows in one call.  Two extra passes (max, finish) and 8 bytes of zeroed workspace per volume element.
+ * P <= 2^22: MVSNERF_EUNSUPPORTED beyond, before anything is launched (2^22 contributions of at most 2^40 keep an accumulator word at or below 2^62).
+ * An inf or NaN anywhere in g: that call adds by float atomics, as mvsnerf_volume_sample_bwd's generic kernel does, so the non-finite values reach gvol.
  * workspace_zeroed: mvsnerf_volume_sample_bwd_det_workspace_words(D, H, W, C) int64 words, 8-byte aligned, zeroed before every call. */
 size_t mvsnerf_volume_sample_bwd_det_workspace_words(int D, int H, int W, int C);
 int mvsnerf_volume_sample_bwd_det(int D, int H, int W, int C, const float* ndc, int64_t P, const float* g, int g_stride, float* gvol,

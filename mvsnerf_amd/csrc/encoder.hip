@@ -1486,7 +1486,8 @@ __global__ __launch_bounds__(256) void absmax_strided_kernel(const float* __rest
     const int64_t n = n_rows * nc;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
         const int64_t r = i / nc;
-        m = fmaxf(m, fabsf(x[r * ld + c0 + (int)(i - r * nc)]));
+        const float a = fabsf(x[r * ld + c0 + (int)(i - r * nc)]);
+        if (a < __builtin_inff()) m = fmaxf(m, a);                    // the largest FINITE magnitude: an inf or NaN must not cost the finite sums their scale
     }
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
@@ -1525,7 +1526,8 @@ __global__ __launch_bounds__(256) void psw_fix_to_float_kernel(const long long* 
 // additions commute, so the result does not depend on the order in which the columns' atomics arrive (float atomics: last-bit differences
 // from run to run).  fix = {int64 [NSRC][H][W][C] | float bits of max |g_cost|, max |feat|}: a contribution is rounded to a multiple of
 // 2^-k with k = 36 - ceil(log2(max|g| * max|feat|)) (relative 2^-36 of the largest possible contribution: far below fp32's 2^-24) and
-// 2^24.3 voxels x 4 |g| |feat| 2^k stay below 2^63.
+// 2^24.3 voxels x 4 |g| |feat| 2^k stay below 2^63.  The two maxima are those of the FINITE values, and a column sum that is inf or NaN (one such value in
+// g_cost is enough) is added to the gradient by a float atomic instead: the elements the float-atomic variant makes non-finite are non-finite here.
 template <int C, int NSRC, bool FIX>
 __global__ __launch_bounds__(256) void planesweep_bwd_columns_kernel(const float* __restrict__ feat, const float* __restrict__ proj,
                                                                      const float* __restrict__ depth, int H, int W, int D, int pad,
@@ -1563,8 +1565,13 @@ __global__ __launch_bounds__(256) void planesweep_bwd_columns_kernel(const float
 #pragma unroll
         for (int k = 0; k < 4; ++k)
             if (acc[vs][k] != 0.f) {
-                if (FIX) atomicAdd(reinterpret_cast<unsigned long long*>(fix + (int64_t)vs * H * W * C + c + (o[k] >> 2)),
-                                   (unsigned long long)(long long)rintf(acc[vs][k] * fix_scale));
+                if (FIX) {
+                    // a sum that is inf or NaN (or overflows under the scale) has no fixed-point value: (long long)rintf(NaN) is 0 and an inf saturates to a
+                    // finite 2^63, so it goes to the gradient by the float atomic, as in the float-atomic entry, and the element ends non-finite
+                    const float scaled = acc[vs][k] * fix_scale;
+                    if ((__float_as_uint(scaled) & 0x7f800000u) == 0x7f800000u) atomicAdd(gview + (o[k] >> 2), acc[vs][k]);
+                    else atomicAdd(reinterpret_cast<unsigned long long*>(fix + (int64_t)vs * H * W * C + c + (o[k] >> 2)), (unsigned long long)(long long)rintf(scaled));
+                }
                 else atomicAdd(gview + (o[k] >> 2), acc[vs][k]);
                 acc[vs][k] = 0.f;
             }

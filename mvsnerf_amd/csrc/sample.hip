@@ -725,8 +725,15 @@ extern "C" int mvsnerf_volume_sample_bwd(int D, int H, int W, int C, const float
 // The same scatter with an ORDER-INDEPENDENT reduction (round 6; the plane sweep has had one since round 4): float atomics make the volume gradient depend
 // on the order in which samples arrive, and under use_amp one flipped last bit there grows 3-5x per layer through the bf16 encoder backward.  Here every
 // contribution is rounded ONCE to 64-bit fixed point - scale 2^(40 - e) with max |g| < 2^e found on the device, so a contribution resolves 2^-40 of the largest
-// one and 4 M of them fit a word - integer atomics commute, and a last pass adds the sums to gvol.  Two runs, and N ranks against one, give identical bits.
+// one - integer atomics commute, and a last pass adds the sums to gvol.  Two runs of one call give identical bits, in whatever order the rows arrive; calls on
+// parts of the rows do not add up to the call on all of them (each call has its own scale and ends in a float addition), so N ranks scatter the concatenation of
+// their rows in ONE call (ops.volume_grad_from_gathered_rows).
+//   Capacity: a point adds at most one contribution per voxel channel (its eight corners are distinct voxels), |q| <= 2^40 (|g * w| <= max |g| < 2^e), so 2^22
+// points keep every |sum| <= 2^62; the entry refuses P > 2^22 (MVSNERF_EUNSUPPORTED) instead of letting a word wrap.
+//   A non-finite max |g| (an inf or NaN anywhere in g) has no scale: that call's scatter kernel issues the float atomics of volume_sample_bwd_kernel on gvol
+// itself - inf and NaN reach the elements they reach there -, the accumulators stay zero and the finish pass adds nothing.
 // workspace (int64 words, zeroed by the caller): [0] = bit pattern of max |g|, [8 ..] = one accumulator per volume element.
+constexpr int64_t DET_SCATTER_MAX_POINTS = (int64_t)1 << 22;
 __global__ __launch_bounds__(256) void absmax_bits_kernel(const float* __restrict__ g, int64_t P, int C, int g_stride, unsigned* __restrict__ out)
 {
     unsigned m = 0;
@@ -747,12 +754,13 @@ __device__ __forceinline__ int det_exponent(unsigned max_bits)        // e with 
 
 __global__ __launch_bounds__(256) void volume_sample_bwd_det_scatter_kernel(
     int D, int H, int W, int C, const float* __restrict__ ndc, int64_t P, const float* __restrict__ g, int g_stride,
-    const unsigned* __restrict__ max_bits, unsigned long long* __restrict__ acc)
+    const unsigned* __restrict__ max_bits, unsigned long long* __restrict__ acc, float* __restrict__ gvol)
 {
 #pragma clang fp contract(off)      // the forward lookups' weights, bit for bit: contracted, (ix - fx) becomes fma(t, size - 1, -fx) and skips the rounding of ix
     const unsigned mb = *max_bits;
-    if (mb == 0 || mb >= 0x7f800000u) return;                       // all-zero gradient; a non-finite one is left to the float path's semantics (finish reports nothing)
-    const double scale = ldexp(1.0, 40 - det_exponent(mb));
+    if (mb == 0) return;                                            // all-zero gradient
+    const bool float_path = mb >= 0x7f800000u;                      // an inf or NaN in g: no scale exists, this call runs volume_sample_bwd_kernel's float atomics
+    const double scale = float_path ? 0.0 : ldexp(1.0, 40 - det_exponent(mb));
     const int Q = C >> 2;
     const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t p = tid / Q;
@@ -768,7 +776,13 @@ __global__ __launch_bounds__(256) void volume_sample_bwd_det_scatter_kernel(
         const float cxf = fx + (float)xc, cyf = fy + (float)yc, czf = fz + (float)zc;
         if (!((cxf >= 0.0f) && (cxf <= (float)(W - 1)) && (cyf >= 0.0f) && (cyf <= (float)(H - 1)) && (czf >= 0.0f) && (czf <= (float)(D - 1)))) continue;
         const float w = (xc ? (ix - fx) : ((fx + 1.0f) - ix)) * (yc ? (iy - fy) : ((fy + 1.0f) - iy)) * (zc ? (iz - fz) : ((fz + 1.0f) - iz));
-        unsigned long long* dst = acc + ((((int64_t)czf * H + (int)cyf) * W + (int)cxf) * C + ch);
+        const int64_t at = (((int64_t)czf * H + (int)cyf) * W + (int)cxf) * C + ch;
+        if (float_path) {
+#pragma unroll
+            for (int c = 0; c < 4; ++c) atomicAdd(gvol + at + c, gv[c] * w);
+            continue;
+        }
+        unsigned long long* dst = acc + at;
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             const long long q = __double2ll_rn((double)(gv[c] * w) * scale);        // the float product of the atomic path, rounded once more to the fixed grid
@@ -781,7 +795,7 @@ __global__ __launch_bounds__(256) void volume_sample_bwd_det_finish_kernel(const
                                                                            float* __restrict__ gvol)
 {
     const unsigned mb = *max_bits;
-    if (mb == 0 || mb >= 0x7f800000u) return;
+    if (mb == 0 || mb >= 0x7f800000u) return;                       // nothing was accumulated: all-zero gradient, or the scatter kernel ran the float path
     const double inv = ldexp(1.0, det_exponent(mb) - 40);
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const long long q = acc[i];
@@ -801,6 +815,7 @@ extern "C" int mvsnerf_volume_sample_bwd_det(int D, int H, int W, int C, const f
     if (!ndc || !g || !gvol || !workspace_zeroed || D < 1 || H < 1 || W < 1 || P < 0 || g_stride < C) return MVSNERF_EINVAL;
     if (C < 4 || (C & 3)) return MVSNERF_EUNSUPPORTED;
     if ((g_stride & 3) || !mvs_aligned16(g) || (reinterpret_cast<uintptr_t>(workspace_zeroed) & 7)) return MVSNERF_EALIGN;
+    if (P > DET_SCATTER_MAX_POINTS) return MVSNERF_EUNSUPPORTED;     // more points could wrap an accumulator word
     if (P == 0) return MVSNERF_OK;
     hipStream_t st = (hipStream_t)stream;
     unsigned* mb = reinterpret_cast<unsigned*>(workspace_zeroed);
@@ -808,7 +823,7 @@ extern "C" int mvsnerf_volume_sample_bwd_det(int D, int H, int W, int C, const f
     const int64_t n = (int64_t)D * H * W * C;
     absmax_bits_kernel<<<1024, 256, 0, st>>>(g, P, C, g_stride, mb);
     MVS_LAUNCH_CHECK();
-    volume_sample_bwd_det_scatter_kernel<<<mvs_cdiv(P * (C >> 2), 256), 256, 0, st>>>(D, H, W, C, ndc, P, g, g_stride, mb, acc);
+    volume_sample_bwd_det_scatter_kernel<<<mvs_cdiv(P * (C >> 2), 256), 256, 0, st>>>(D, H, W, C, ndc, P, g, g_stride, mb, acc, gvol);
     MVS_LAUNCH_CHECK();
     volume_sample_bwd_det_finish_kernel<<<4096, 256, 0, st>>>(reinterpret_cast<const long long*>(acc), n, mb, gvol);
     MVS_LAUNCH_CHECK();

@@ -1619,9 +1619,10 @@ class RayMarchFunction(torch.autograd.Function):
         return (g_vol, None, None, None, None, None, None, None, None, None, None, *b.grads)
 
 
-VOLUME_BWD_DETERMINISTIC = False   # True: the volume gradient's scatter through 64-bit fixed-point accumulators (integer atomics commute: two runs, and N ranks
-                                   # against one, give bit-identical gradients; mvsnerf_volume_sample_bwd_det) - two extra passes and 8 bytes of zeroed workspace
-                                   # per volume element (300 MB at config 2) instead of float atomics
+VOLUME_BWD_DETERMINISTIC = False   # True: the volume gradient's scatter through 64-bit fixed-point accumulators (mvsnerf_volume_sample_bwd_det; integer atomics
+                                   # commute: one call gives the same bits in whatever order its rows arrive, so two runs are bit-identical) - two extra passes and
+                                   # 8 bytes of zeroed workspace per volume element (300 MB at config 2) instead of float atomics.  N ranks: for a zeroed gvol,
+                                   # volume_grad_from_all_ranks gives every rank the bits of ONE scatter call on all ranks' rows, divided by world
 
 
 def _scatter_hip(gvol_cl, ndc, g):
@@ -1635,16 +1636,38 @@ def _scatter_hip(gvol_cl, ndc, g):
     check(lib.mvsnerf_volume_sample_bwd(D, H, W, C, ndc.data_ptr(), ndc.shape[0], g.data_ptr(), C, gvol_cl.data_ptr(), stream_ptr()), "volume_sample_bwd")
 
 
+def volume_grad_from_gathered_rows(allrows, cnts, width, gvol_cl, scatter=_scatter_hip):
+    """The part of volume_grad_from_all_ranks behind its collectives, a pure function of the gathered buffer: allrows (world * width, C + 4) holds rank r's
+    rows [d_feat (C) | ndc (3) | pad] at [r * width, r * width + cnts[r]).  ONE `scatter` call on the concatenation of the ranks' valid rows in rank order,
+    then gvol_cl /= world.  One call, so that under VOLUME_BWD_DETERMINISTIC there is one fixed-point scale, one rounding per contribution and one workspace
+    whatever the number of ranks: for a zeroed gvol_cl the result is the single-call scatter of all ranks' rows, divided by world, bit for bit and whatever
+    the order of the shards.  With float atomics it is that value to their summation-order noise."""
+    C = gvol_cl.shape[-1]
+    world = len(cnts)
+    if all(n == width for n in cnts):
+        rows = allrows
+    else:
+        rows = torch.cat([allrows[r * width:r * width + n] for r, n in enumerate(cnts)])
+    if rows.shape[0]:
+        scatter(gvol_cl, rows[:, C:C + 3].contiguous(), rows[:, :C].contiguous())     # `scatter` is replaceable so that the CPU (gloo) tests can drive this exchange
+    gvol_cl.div_(world)
+    return gvol_cl
+
+
 def volume_grad_from_all_ranks(d_feat, ndc, gvol_cl, group=None, scatter=_scatter_hip):
     """Data-parallel gradient of a learnable RefVolume WITHOUT reducing the volume-sized tensor (SURVEY.md 5 / 8e "Fine-tune").
 
     The volume gradient is the trilinear scatter of the per-sample feature gradients d_feat (P_local x C).  A dense all-reduce of it moves
     2 x (world-1)/world x 150-246 MB per rank and step over xGMI; the SAMPLE gradients of all ranks are 36 B + 12 B (NDC) per sample -
-    6 MB for 1024 x 128 samples in total.  So: ONE all_gather of [d_feat | ndc] rows, then every rank scatters the samples of ALL ranks
-    into its own gradient volume (0.16 ms for 131 072 samples) and scales by 1/world - the same mean-over-ranks FlatGradAllReduce gives
-    the other parameters.  Every rank ends with the full gradient; the volume parameter takes no part in the flat all-reduce.
-    (The scatter uses float atomics, so replicas can differ in the last bits; MVSSystemFinetune re-broadcasts the volume from rank 0 every
-    `args.dp_volume_resync` steps.)"""
+    6 MB for 1024 x 128 samples in total.  So: ONE all_gather of the counts and ONE of the [d_feat | ndc] rows, then every rank scatters the
+    samples of ALL ranks into its own gradient volume in one call (volume_grad_from_gathered_rows; 0.16 ms for 131 072 samples) and scales by
+    1/world - the same mean-over-ranks FlatGradAllReduce gives the other parameters.  Every rank ends with the full gradient; the volume
+    parameter takes no part in the flat all-reduce.
+
+    For a zeroed gvol_cl the result equals the single-call scatter of all ranks' rows (rank order) divided by world.  Under
+    VOLUME_BWD_DETERMINISTIC that holds bit for bit, so the replicas agree with each other and with one rank that holds every row.  With the
+    float-atomic scatter it holds to the atomics' summation-order noise, so replicas can differ in the last bits; MVSSystemFinetune
+    re-broadcasts the volume from rank 0 every `args.dp_volume_resync` steps."""
     import torch.distributed as dist
     from . import distributed as DD
     C = d_feat.shape[1]
@@ -1661,13 +1684,7 @@ def volume_grad_from_all_ranks(d_feat, ndc, gvol_cl, group=None, scatter=_scatte
     row[:P, C:C + 3] = ndc
     allrows = torch.empty((world * width, C + 4), device=d_feat.device, dtype=torch.float32)
     DD.all_gather_into_tensor(allrows, row, group=group)
-    for r, n in enumerate(cnts):
-        if n == 0:
-            continue
-        blk = allrows[r * width:r * width + n]
-        scatter(gvol_cl, blk[:, C:C + 3].contiguous(), blk[:, :C].contiguous())     # `scatter` is replaceable so that the CPU (gloo) tests can drive this exchange
-    gvol_cl.div_(world)
-    return gvol_cl
+    return volume_grad_from_gathered_rows(allrows, cnts, width, gvol_cl, scatter)
 
 
 def _exchange_samples(dp_samples):

@@ -489,9 +489,11 @@ def test_volume_sample_bwd_deterministic_variant(C, D, H, W, P):
     err_atomic = float((ref.double() - exact).abs().max()) / scale
     record_err(f"volume_sample_bwd_det_vs_exact:C{C}:P{P}", err, tol=2e-5)
     record_err(f"volume_sample_bwd_atomic_vs_exact:C{C}:P{P}", err_atomic, tol=5e-5)
-    # (torch forms the fp32 weights / products with its own roundings: ~1 ulp per contribution, up to ~500 contributions per voxel in the crowded column: measured
-    # 4e-7 at P = 4096, 4e-6 at P = 131072 - the float-atomic kernel sits at the same distance from this reference; what pins the deterministic variant are the
-    # bit-identical repeats above and the scale invariance below)
+    # (torch forms the fp32 weights / products with the SAME roundings as the kernel, which runs plain IEEE operations under `fp contract(off)`:
+    # tests/test_gpu_scatter_det.py predicts the kernel's 64-bit accumulators exactly, torch.equal, from products formed by torch.  The deterministic variant
+    # sits half an fp32 ulp from this reference - measured 3.6e-8, 4.1e-8 and 3.6e-8 of the largest element at the three shapes -, the float-atomic kernel at
+    # its summation-order noise, 2.6e-7 at P = 4096 and 1.1e-6 at P = 131072.  The bounds below predate that finding and stay as they were; what pins the
+    # deterministic variant to its definition is the equality test in that file)
     assert scale > 0 and err < 2e-5, err
     assert err_atomic < 5e-5, err_atomic                                  # the float atomics: summation-order noise of up to ~500 contributions per voxel here
     big = det(gf * 1.0e6)

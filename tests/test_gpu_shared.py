@@ -194,6 +194,22 @@ def _rank_body(rank, world, port, q):
             ref, _ = vol_grad("allreduce", False)
         res["finetune_grad_err"] = float((got - ref).abs().max()) / float(ref.abs().max())
         res["finetune_ok"] = bool(losses is not None and all(l == l for l in losses) and losses[-1] < losses[0])
+        # ---- the same exchange under the fixed-point scatter: every rank ends with the BITS of one scatter call over all ranks' rows, divided by world
+        def seeded_rows(r):
+            gr = torch.Generator().manual_seed(900 + r)
+            n = 301 + 57 * r                                                   # uneven shards
+            return torch.randn((n, 8), generator=gr).to(dev), (torch.rand((n, 3), generator=gr) * 1.1 - 0.05).to(dev)
+        rows = [seeded_rows(r) for r in range(world)]
+        saved = ops.VOLUME_BWD_DETERMINISTIC
+        ops.VOLUME_BWD_DETERMINISTIC = True
+        try:
+            got = ops.volume_grad_from_all_ranks(rows[rank][0], rows[rank][1], torch.zeros((6, 7, 9, 8), device=dev))
+            one = torch.zeros((6, 7, 9, 8), device=dev)
+            ops._scatter_hip(one, torch.cat([n for _, n in rows]), torch.cat([g for g, _ in rows]))
+            one.div_(world)
+        finally:
+            ops.VOLUME_BWD_DETERMINISTIC = saved
+        res["det_exchange_equal"] = bool(torch.equal(got, one)) and float(one.abs().max()) > 0
         q.put((rank, res))
     finally:
         dist.barrier()
@@ -229,6 +245,7 @@ def test_two_ranks_on_one_gpu():
             assert r[k] < GRAD_TOL, f"rank {rank}: {k} = {r[k]}"
         assert r["ray_in_sync"] and r["scene_in_sync"], f"rank {rank}: parameters diverged"
         assert r["ray_finite"] and r["scene_finite"] and r["finetune_ok"]
+        assert r["det_exchange_equal"], f"rank {rank}: the exchanged volume gradient under VOLUME_BWD_DETERMINISTIC is not the single-call scatter / world bit for bit"
 
 
 def test_bench_shared_gpu_dry_run():
