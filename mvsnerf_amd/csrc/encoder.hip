@@ -38,7 +38,30 @@ extern "C" int mvsnerf_nchw_to_nhwc(const float* src, float* dst, int N, int C, 
     return MVSNERF_OK;
 }
 
-// F.interpolate(mode='bilinear', align_corners=False) (models.py:859), planes [NC][Hi][Wi] -> [NC][Ho][Wo]
+// F.interpolate(mode='bilinear', align_corners=False) (models.py:859).  Both resize kernels form every output value through the two helpers
+// below, with every operation spelled out and nothing left to contract: the channel-last form holds the BITS of the planar one
+// (tests/test_gpu_sweep_edges.py).  Left to the compiler, the same source expression was contracted differently in the two kernels and even
+// per channel inside one of them (green took fma(hy, top, ly * bot), red and blue fma(ly, bot, hy * top)): last-bit differences between
+// entries that claim the same operations.  The arithmetic kept is the one red and blue had: the source coordinate in one rounding,
+// fma(scale, o + 0.5, -0.5), top = fma(lx, p01, hx * p00), bottom = fma(hx, p10, lx * p11), value = fma(ly, bottom, hy * top).
+__device__ __forceinline__ void resize_axis(int o, int n_in, int n_out, int& i0, int& i1, float& l, float& h)
+{
+#pragma clang fp contract(off)
+    const float scale = (float)n_in / (float)n_out;                          // area_pixel_compute_scale
+    float f = fmaf(scale, (float)o + 0.5f, -0.5f); if (f < 0.f) f = 0.f;
+    i0 = (int)f;
+    i1 = i0 + (i0 < n_in - 1 ? 1 : 0);
+    l = f - (float)i0; h = 1.f - l;
+}
+__device__ __forceinline__ float resize_blend(const float* __restrict__ p, int Wi, int y0, int y1, int x0, int x1, float ly, float hy, float lx, float hx)
+{
+#pragma clang fp contract(off)
+    const float top = fmaf(lx, p[(int64_t)y0 * Wi + x1], hx * p[(int64_t)y0 * Wi + x0]);
+    const float bot = fmaf(hx, p[(int64_t)y1 * Wi + x0], lx * p[(int64_t)y1 * Wi + x1]);
+    return fmaf(ly, bot, hy * top);
+}
+
+// planes [NC][Hi][Wi] -> [NC][Ho][Wo]
 __global__ __launch_bounds__(256) void resize_bilinear_kernel(const float* __restrict__ src, float* __restrict__ dst,
                                                               int NC, int Hi, int Wi, int Ho, int Wo)
 {
@@ -46,15 +69,11 @@ __global__ __launch_bounds__(256) void resize_bilinear_kernel(const float* __res
     if (i >= (int64_t)NC * Ho * Wo) return;
     const int x = (int)(i % Wo), y = (int)((i / Wo) % Ho);
     const int64_t n = i / ((int64_t)Wo * Ho);
-    const float sh = (float)Hi / (float)Ho, sw = (float)Wi / (float)Wo;     // area_pixel_compute_scale
-    float fy = sh * ((float)y + 0.5f) - 0.5f; if (fy < 0.f) fy = 0.f;
-    float fx = sw * ((float)x + 0.5f) - 0.5f; if (fx < 0.f) fx = 0.f;
-    const int y0 = (int)fy, x0 = (int)fx;
-    const int y1 = y0 + (y0 < Hi - 1 ? 1 : 0), x1 = x0 + (x0 < Wi - 1 ? 1 : 0);
-    const float ly = fy - (float)y0, lx = fx - (float)x0, hy = 1.f - ly, hx = 1.f - lx;
-    const float* p = src + n * Hi * Wi;
-    dst[i] = hy * (hx * p[(int64_t)y0 * Wi + x0] + lx * p[(int64_t)y0 * Wi + x1]) +
-             ly * (hx * p[(int64_t)y1 * Wi + x0] + lx * p[(int64_t)y1 * Wi + x1]);
+    int y0, y1, x0, x1;
+    float ly, hy, lx, hx;
+    resize_axis(y, Hi, Ho, y0, y1, ly, hy);
+    resize_axis(x, Wi, Wo, x0, x1, lx, hx);
+    dst[i] = resize_blend(src + n * Hi * Wi, Wi, y0, y1, x0, x1, ly, hy, lx, hx);
 }
 
 // the same interpolation of N three-channel images written channel-last with a zero fourth channel ([N][Ho][Wo][4]: what the plane sweep reads): one launch
@@ -65,19 +84,13 @@ __global__ __launch_bounds__(256) void resize_bilinear_nhwc4_kernel(const float*
     if (i >= (int64_t)N * Ho * Wo) return;
     int x, y, n;
     mvs_unflatten3(i, Wo, Ho, x, y, n);
-    const float sh = (float)Hi / (float)Ho, sw = (float)Wi / (float)Wo;     // area_pixel_compute_scale
-    float fy = sh * ((float)y + 0.5f) - 0.5f; if (fy < 0.f) fy = 0.f;
-    float fx = sw * ((float)x + 0.5f) - 0.5f; if (fx < 0.f) fx = 0.f;
-    const int y0 = (int)fy, x0 = (int)fx;
-    const int y1 = y0 + (y0 < Hi - 1 ? 1 : 0), x1 = x0 + (x0 < Wi - 1 ? 1 : 0);
-    const float ly = fy - (float)y0, lx = fx - (float)x0, hy = 1.f - ly, hx = 1.f - lx;
+    int y0, y1, x0, x1;
+    float ly, hy, lx, hx;
+    resize_axis(y, Hi, Ho, y0, y1, ly, hy);
+    resize_axis(x, Wi, Wo, x0, x1, lx, hx);
     f32x4 o = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float* p = src + ((int64_t)n * 3 + c) * Hi * Wi;
-        o[c] = hy * (hx * p[(int64_t)y0 * Wi + x0] + lx * p[(int64_t)y0 * Wi + x1]) +
-               ly * (hx * p[(int64_t)y1 * Wi + x0] + lx * p[(int64_t)y1 * Wi + x1]);
-    }
+    for (int c = 0; c < 3; ++c) o[c] = resize_blend(src + ((int64_t)n * 3 + c) * Hi * Wi, Wi, y0, y1, x0, x1, ly, hy, lx, hx);
     *reinterpret_cast<f32x4*>(dst + i * 4) = o;
 }
 
@@ -129,6 +142,8 @@ int mvs_planesweep_launch(const float* feats_cl, const float* imgs_cl, const flo
                           int with_img, int blocked, void* stream, int* guard, const int* run_if);
 
 // stand-alone homo_warp (utils.py:580-630): one source view, NCHW in, (C,D,Hp,Wp) out + grid (D,Hp*Wp,2)
+// A sample coordinate that is not finite gives NaN here (0 * NaN in the blend), as in the CPU reference - on purpose, unlike the plane sweep and its backward
+// kernels, which give such a view four zero weights (planesweep.hip header).  Every load is guarded by its tap's in-image test.
 __global__ __launch_bounds__(256) void homo_warp_kernel(const float* __restrict__ src, const float* __restrict__ P, const float* __restrict__ depth,
                                                         const float* __restrict__ grid_in, int C, int H, int W, int D, int pad,
                                                         float* __restrict__ out, float* __restrict__ grid_out)
@@ -1395,6 +1410,8 @@ extern "C" int mvsnerf_conv3d_c8_blocked_wgrad(const float* x_blocked, int Cin, 
 // var_c = s2*inv - (s*inv)^2 with s = sum of warped values, so for every contributing value w:
 //   d w = g_var * 2*inv*(w - s*inv).   Warped values are bilinear gathers => their gradient is a bilinear scatter
 // (float atomics).  Masks/counts are step functions (no gradient); thumbnails carry no parameters.
+// Both backward kernels ADD to g_feat (the caller hands in zeros), and give a view whose sample coordinate is not finite four zero weights, as the forward
+// sweep does (planesweep.hip header): the three geometry blocks are the same code and must stay so.
 template <int C>
 __global__ __launch_bounds__(256) void planesweep_bwd_kernel(const float* __restrict__ feat, const float* __restrict__ proj, const float* __restrict__ depth,
                                                             int V, int H, int W, int D, int pad, const float* __restrict__ g_cost, int CP, int c_var,

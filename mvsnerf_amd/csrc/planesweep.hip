@@ -12,6 +12,12 @@
 // three processes, 0 of 192 with two streams) and is 3 % FASTER (0.312 vs 0.322 ms: 10 % more VALU instructions, fewer register moves).
 // Nothing in the ISA explains it (waits and hazards nops are the compiler's and are correct for in-order return): treated as a hardware
 // interaction to stay away from, see DESIGN.md section 9.
+//
+// Degenerate geometry (tests/test_gpu_sweep_edges.py, tests/sweep_refs.py).  A source view whose fp32 sample coordinate ix or iy is NOT
+// FINITE (p2 == 0: +-inf and 0/0; an overflowing T / depth) has FOUR ZERO WEIGHTS: every comparison of the `x0in && ...` selects is false for NaN and inf, so
+// the view adds nothing to the voxel's sums and is not counted, and no address is formed from it (`any ? clamp : 0`).  The CPU reference returns NaN on exactly
+// those voxels; the zero is this project's definition (one NaN voxel would poison CostRegNet's batch statistics), shared by the two backward kernels in
+// encoder.hip, whose geometry blocks must stay equal to phase 1 below.  The stand-alone homo_warp_kernel (encoder.hip) deliberately returns the reference's NaN.
 #include "common.h"
 #include "act.h"
 #include "knobs.h"
