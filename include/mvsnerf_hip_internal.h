@@ -645,6 +645,46 @@ int mvsnerf_tsdf_integrate_fwd(const float* depth, const unsigned char* valid, c
                                float z_min, float* tsdf, int* weight, unsigned char* colors, void* stream);
 int mvsnerf_tsdf_vertex_colors_fwd(const float* tsdf, const unsigned char* node_colors, int D, int H, int W, const int64_t* vertex_edge,
                                    const int64_t* count, int64_t rows, unsigned char* colors, void* stream);
+/* ---- geometric scores of clouds and meshes: a uniform grid over a target cloud, the EXACT nearest neighbour within a radius, the DTU / Tanks-and-Temples
+ *      reductions, and points on a mesh (csrc/cloud_metrics.hip, DESIGN.md 4p, where the definitions are written out).  No counterpart in the reference. ----
+ * grid_bounds: bounds [6] (device) = min xyz, max xyz over the rows of points [n][3] whose three coordinates are finite; +inf, -inf when there is none
+ *   (n == 0 included).  workspace: grid_bounds_workspace_bytes(n) bytes, 4-byte aligned (0: n < 0 or n >= 2^31; runs without a GPU).
+ * grid_build: the grid of dx x dy x dz cells of edge `cell` from lo (3 HOST floats).  The cell of a point is floorf((p - lo) * (1.0f / cell)) per axis, clamped
+ *   to [0, dim - 1] (a point outside the box lands in a border cell), flat cell (cz dy + cy) dx + cx.  Rows with a non-finite coordinate are left out.
+ *   cell_start [dx dy dz + 1] int32 = the exclusive prefix of the cells' counts (the last entry: the number of points kept); records [n][4] fp32 = x, y, z
+ *   and the bits of the ORIGINAL row index, grouped by cell, 16-byte aligned; only the first cell_start[cells] records are written.  Integer atomics count
+ *   and place the points: the order of the records inside a cell may differ between two runs, cell_start does not.  n == 0 writes zeros to cell_start.
+ *   workspace: grid_build_workspace_bytes(n, dx, dy, dz) bytes, 4-byte aligned (0 for arguments the entry refuses).
+ * grid_nearest: per row of query [n_query][3] the minimum, in lexicographic order, of (d2, original index) over the grid's points with
+ *   d2 = (dx dx + dy dy) + dz dz <= max_dist max_dist (both fp32, every operation rounded on its own): dist [.] = sqrtf(d2), index [.] int32; +inf and -1
+ *   when there is no such point or a coordinate of the query is not finite.  The same bits for every (lo, cell, dims) the grid was built with, and for a
+ *   query inside or outside the box.  lo, cell, dims: those of grid_build.
+ * cloud_metrics: out [10] doubles (device) = {the sum of the finite entries of dist [n], their number, the number of entries with dist < taus[k] (fp32
+ *   compare), k < n_tau <= 8, zeros behind}; taus: HOST floats.  Two launches, fixed summation order, no atomics.  workspace:
+ *   cloud_metrics_workspace_bytes(n) bytes, 8-byte aligned like out.
+ * mesh_sample: points on the faces [n_faces][3] (int32 rows of vertices [n_vertices][3]).  Per face n = max(1, ceilf(L / spacing)), L its longest edge, an
+ *   edge sqrtf((dx dx + dy dy) + dz dz); the face emits the centroids of the n n sub-triangles of its barycentric lattice: rows j = 0..n-1, in a row
+ *   i = 0..n-1-j the upward triangle, weights (wb, wc) = (3i+1, 3j+1), then (while i < n-1-j) the downward one, (3i+2, 3j+2); point = ((wa A + wb B) +
+ *   wc C) / (3n), wa = 3n - wb - wc.  A face with a non-finite vertex, a vertex number outside [0, n_vertices) or n > 1024 emits nothing.  mesh_count: NULL, or
+ *   the device {vertices, faces} counts of a mesh extracted with a capacity (rows past them are not read).  points [capacity][3] fp32, face [capacity] int32,
+ *   ordered by face and then by lattice order; rows >= min(count[0], capacity) are not written.  count (device, int64 [2]) = {the true number of points, the
+ *   largest n of any face: above 1024 means faces were refused}; capacity == 0 runs the count alone.  No atomics: two runs give the same bytes.
+ *   workspace: mesh_sample_workspace_bytes(n_faces) bytes, 8-byte aligned.
+ * MVSNERF_EINVAL: a NULL pointer that is needed, a negative count or capacity; MVSNERF_EUNSUPPORTED: a count or capacity >= 2^31, a dimension < 1 or more than
+ *   2^24 cells, lo / cell / max_dist / spacing not finite or cell / max_dist / spacing <= 0 (or 1 / cell, max_dist^2 not finite), n_tau > 8; MVSNERF_EALIGN: a
+ *   float / int32 array not 4-byte, records not 16-byte, doubles / int64 / the 8-byte workspaces not 8-byte aligned.  All before the first launch. */
+size_t mvsnerf_grid_bounds_workspace_bytes(int64_t n);
+int mvsnerf_grid_bounds_fwd(const float* points, int64_t n, float* bounds, void* workspace, void* stream);
+size_t mvsnerf_grid_build_workspace_bytes(int64_t n, int dx, int dy, int dz);
+int mvsnerf_grid_build_fwd(const float* points, int64_t n, const float* lo, float cell, int dx, int dy, int dz, int* cell_start, float* records,
+                           void* workspace, void* stream);
+int mvsnerf_grid_nearest_fwd(const float* lo, float cell, int dx, int dy, int dz, const int* cell_start, const float* records, const float* query,
+                             int64_t n_query, float max_dist, float* dist, int* index, void* stream);
+size_t mvsnerf_cloud_metrics_workspace_bytes(int64_t n);
+int mvsnerf_cloud_metrics_fwd(const float* dist, int64_t n, const float* taus, int n_tau, double* out, void* workspace, void* stream);
+size_t mvsnerf_mesh_sample_workspace_bytes(int64_t n_faces);
+int mvsnerf_mesh_sample_fwd(const float* vertices, int64_t n_vertices, const int* faces, int64_t n_faces, const int64_t* mesh_count, float spacing,
+                            int64_t capacity, float* points, int* face, int64_t* count, void* workspace, void* stream);
 
 #ifdef __cplusplus
 }

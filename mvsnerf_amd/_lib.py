@@ -307,6 +307,15 @@ SIGNATURES = {
     "mvsnerf_tsdf_integrate_fwd": (_c_i, [_c_fp] * 3 + [_c_i] + [_c_fp] * 3 + [_c_i] * 4 + [ctypes.POINTER(ctypes.c_float)] + [_c_i] * 3
                                    + [ctypes.c_float, ctypes.c_float] + [_c_fp] * 4),
     "mvsnerf_tsdf_vertex_colors_fwd": (_c_i, [_c_fp, _c_fp] + [_c_i] * 3 + [_c_fp, _c_fp, _c_l, _c_fp, _c_fp]),
+    "mvsnerf_grid_bounds_workspace_bytes": (ctypes.c_size_t, [_c_l]),
+    "mvsnerf_grid_bounds_fwd": (_c_i, [_c_fp, _c_l, _c_fp, _c_fp, _c_fp]),
+    "mvsnerf_grid_build_workspace_bytes": (ctypes.c_size_t, [_c_l] + [_c_i] * 3),
+    "mvsnerf_grid_build_fwd": (_c_i, [_c_fp, _c_l, ctypes.POINTER(ctypes.c_float), ctypes.c_float] + [_c_i] * 3 + [_c_fp] * 4),
+    "mvsnerf_grid_nearest_fwd": (_c_i, [ctypes.POINTER(ctypes.c_float), ctypes.c_float] + [_c_i] * 3 + [_c_fp] * 3 + [_c_l, ctypes.c_float] + [_c_fp] * 3),
+    "mvsnerf_cloud_metrics_workspace_bytes": (ctypes.c_size_t, [_c_l]),
+    "mvsnerf_cloud_metrics_fwd": (_c_i, [_c_fp, _c_l, ctypes.POINTER(ctypes.c_float), _c_i, _c_fp, _c_fp, _c_fp]),
+    "mvsnerf_mesh_sample_workspace_bytes": (ctypes.c_size_t, [_c_l]),
+    "mvsnerf_mesh_sample_fwd": (_c_i, [_c_fp, _c_l, _c_fp, _c_l, _c_fp, ctypes.c_float, _c_l] + [_c_fp] * 5),
 }
 
 _lib = None

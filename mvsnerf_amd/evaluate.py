@@ -131,6 +131,76 @@ def ssim_hip(rgb, img, win_size=7, data_range=None, K1=0.01, K2=0.03):
     return row[:, ops.M_SSIM0:ops.M_SSIM2 + 1].sum(1) / (3.0 * row[:, ops.M_N_SSIM])
 
 
+# ---- geometry: DTU's accuracy / completeness and the Tanks-and-Temples precision / recall / F-score of clouds and meshes (csrc/cloud_metrics.hip)
+
+def _cloud_of(x, name):
+    """x as ((n,3) fp32 tensor | None, mesh | None): a tensor, a TriangleMesh (sampled later), or anything with .points."""
+    from . import geometry
+    if isinstance(x, geometry.TriangleMesh):
+        geometry._cloud_tensor(x.vertices, f"{name}.vertices", "cloud_metrics")
+        return None, x
+    if not torch.is_tensor(x) and hasattr(x, "points"):
+        x = x.points
+    return geometry._cloud_tensor(x, name, "cloud_metrics"), None
+
+
+def cloud_metrics(pred, gt, max_dist, taus=(0.5, 1.0, 2.0), grids=None, spacing=None):
+    """How far a reconstruction is from a scan, on the device.  pred, gt: (n,3) fp32 tensors on the GPU, a geometry.PointCloud (its .points) or anything
+    with .points, or a geometry.TriangleMesh, which is sampled with geometry.sample_mesh(mesh, spacing=spacing) first (spacing= is then required).
+    One exact nearest-neighbour query within max_dist per direction (geometry.PointGrid), then a two-launch float64 reduction per direction.  Returns a
+    dict of float64 tensors on the device; nothing is read back (a grid that has to find its own box reads six floats, see PointGrid):
+        accuracy        the mean of the finite distances from pred to gt - DTU's mean(D(D < MaxDist)); NaN when there is none
+        completeness    the same from gt to pred;   overall = (accuracy + completeness) / 2
+        n_accuracy, n_completeness      how many distances were finite
+        precision       (n_tau,) the share of ALL pred points with dist < tau (tau rounded to fp32, an fp32 compare); 0 for an empty pred
+        recall          (n_tau,) the same over all gt points;   fscore = 2 P R / (P + R), 0 where P + R == 0
+        dist_pred, index_pred (fp32, int32; +inf and -1 where nothing is within max_dist), dist_gt, index_gt: for a caller's own observation mask
+    taus: 1 to 8 numbers (the default is DTU-style millimetres).  grids: (PointGrid over gt, PointGrid over pred) of an earlier call with the same clouds
+    and max_dist, reused as they are.  A PointCloud fused with a capacity carries unwritten rows past its count: pass cloud.points[:n]."""
+    from . import geometry, ops
+    who = "cloud_metrics"
+    r = geometry._radius(max_dist, who)
+    try:
+        taus = [float(t) for t in taus]
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: taus must be 1..{ops.CLOUD_METRICS_MAX_TAUS} numbers, got {taus!r}") from None
+    if not 1 <= len(taus) <= ops.CLOUD_METRICS_MAX_TAUS or any(np.isnan(t) for t in taus):
+        raise ValueError(f"{who}: taus must be 1..{ops.CLOUD_METRICS_MAX_TAUS} numbers, none of them NaN, got {taus!r}")
+    clouds = [_cloud_of(pred, "pred"), _cloud_of(gt, "gt")]
+    if any(m is not None for _, m in clouds) and spacing is None:
+        raise ValueError(f"{who}: a TriangleMesh is scored through its surface samples: pass spacing= (geometry.sample_mesh)")
+    if grids is not None:
+        if not (isinstance(grids, (tuple, list)) and len(grids) == 2 and all(isinstance(g, geometry.PointGrid) for g in grids)):
+            raise ValueError(f"{who}: grids must be a pair (PointGrid over gt, PointGrid over pred)")
+        if any(g.max_dist != r for g in grids):
+            raise ValueError(f"{who}: grids were built for max_dist {[g.max_dist for g in grids]}, not {r}")
+    P, G = (t if m is None else geometry.sample_mesh(m, spacing).points for t, m in clouds)
+    if P.device != G.device:
+        raise ValueError(f"{who}: pred and gt must be on one device, got {P.device} and {G.device}")
+    if grids is None:
+        grids = (geometry.PointGrid(G, r), geometry.PointGrid(P, r))
+    elif grids[0].n != G.shape[0] or grids[1].n != P.shape[0]:
+        raise ValueError(f"{who}: grids hold {grids[0].n} gt and {grids[1].n} pred points, the clouds {G.shape[0]} and {P.shape[0]}")
+    out = {}
+    rows = []
+    for cloud, grid, side in ((P, grids[0], "pred"), (G, grids[1], "gt")):
+        dist, index = grid.nearest(cloud)
+        with torch.cuda.device(cloud.device):
+            rows.append(ops.cloud_metrics_row(dist, taus))
+        out[f"dist_{side}"], out[f"index_{side}"] = dist, index
+    k = len(taus)
+    (rp, rg), (n_p, n_g) = rows, (int(P.shape[0]), int(G.shape[0]))
+    out["accuracy"], out["completeness"] = rp[0] / rp[1], rg[0] / rg[1]                   # 0 / 0 = NaN: nothing within max_dist
+    out["overall"] = (out["accuracy"] + out["completeness"]) / 2.0
+    out["n_accuracy"], out["n_completeness"] = rp[1], rg[1]
+    # (a tensor divisor: torch divides a GPU tensor by a Python number as a product with its reciprocal, which is not the correctly rounded share)
+    out["precision"] = rp[2:2 + k] / torch.full_like(rp[2:2 + k], n_p) if n_p else torch.zeros_like(rp[2:2 + k])
+    out["recall"] = rg[2:2 + k] / torch.full_like(rg[2:2 + k], n_g) if n_g else torch.zeros_like(rg[2:2 + k])
+    s = out["precision"] + out["recall"]
+    out["fscore"] = torch.where(s > 0, 2.0 * out["precision"] * out["recall"] / torch.where(s > 0, s, torch.ones_like(s)), torch.zeros_like(s))
+    return out
+
+
 # ---- LPIPS-VGG on the GPU (csrc/lpips.hip through ops.lpips_*)
 
 VGG_CONVS = (0, 2, 5, 7, 10, 12, 14, 17, 19, 21, 24, 26, 28)           # indices of the 13 convolutions in torchvision's vgg16().features

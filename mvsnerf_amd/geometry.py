@@ -11,6 +11,9 @@ does both for a fine-tuned scene.  Not pinned against any external mesher either
 
 Geometry from depth, as a surface: `fuse_tsdf` integrates the depth maps into a truncated signed distance volume over a world box (csrc/tsdf.hip, DESIGN.md
 4o) and `tsdf_mesh` meshes its zero level, unobserved space masked, with colours from the volume.
+
+Geometry, measured: `PointGrid` answers exact nearest-neighbour queries within a radius between clouds of millions of points and `sample_mesh` puts points on a
+mesh (csrc/cloud_metrics.hip); `evaluate.cloud_metrics` builds DTU's accuracy / completeness and the Tanks-and-Temples F-score on them.
 """
 import math
 
@@ -382,6 +385,139 @@ def scene_mesh(system, level, colors=True, origin=None, dilate=0, capacity=None)
     if colors:
         mesh.colors = vertex_colors(system, mesh, origin)
     return mesh
+
+
+# ---- how far two products are from each other: a point grid, the exact nearest neighbour within a radius, points on a mesh (csrc/cloud_metrics.hip,
+#      DESIGN.md 4p; evaluate.cloud_metrics puts the DTU / Tanks-and-Temples scores on top)
+GRID_CELL_FACTOR = 0.5      # cell=None: the edge is max_dist * this (DESIGN.md 4p holds the measurement behind the choice)
+GRID_CELL_CAP = 1 << 22     # ... grown by a quarter at a time until the table has at most this many cells (16 MiB of cell starts); ops.GRID_MAX_CELLS is the kernels' limit
+
+
+def _cloud_tensor(t, name, who):
+    if not torch.is_tensor(t) or t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != 3:
+        raise ValueError(f"{who}: {name} must be a float32 tensor of shape (n,3), got {type(t).__name__} {getattr(t, 'dtype', '')} "
+                         f"{tuple(getattr(t, 'shape', ()))}")
+    if t.shape[0] >= 1 << 31:
+        raise ValueError(f"{who}: {name} must hold fewer than 2^31 rows, got {t.shape[0]}")
+    return t
+
+
+def _radius(max_dist, who):
+    """max_dist as the fp32 number the kernels use; its square must be a finite, positive fp32 number too."""
+    try:
+        r = float(max_dist)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: max_dist must be a finite number > 0, got {max_dist!r}") from None
+    with np.errstate(over="ignore"):
+        r32 = np.float32(r) if math.isfinite(r) else np.float32("nan")
+        sq = r32 * r32
+    if not (r > 0 and math.isfinite(float(r32)) and math.isfinite(float(sq)) and float(sq) > 0):
+        raise ValueError(f"{who}: max_dist must be finite and > 0 (and so must its fp32 square), got {max_dist!r}")
+    return float(r32)
+
+
+class PointGrid:
+    """A uniform grid over a target cloud for exact nearest-neighbour queries within max_dist.
+        points      (n,3) fp32 on the GPU, 0 <= n < 2^31; rows with a non-finite coordinate are left out and are never anyone's neighbour
+        max_dist    finite, > 0: the search radius of `nearest`
+        cell        None: max_dist * GRID_CELL_FACTOR; or the edge of a cell.  Either is grown until the table has at most GRID_CELL_CAP cells.
+        box         None: the bounds of the finite rows, from a min / max reduction on the device and ONE host read of six floats (the host sizes the
+                    cell table); or (lo, hi), 2 x 3 finite numbers: nothing is read from the device.  Points outside the box land in its border cells.
+    No result of `nearest` depends on cell or box.  Attributes: lo (3 floats), cell, dims (dx, dy, dz), cell_start (cells + 1,) int32, records (n,4) fp32
+    (x, y, z, the bits of the original row; grouped by cell, the first cell_start[-1] rows are written)."""
+
+    def __init__(self, points, max_dist, cell=None, box=None):
+        who = "PointGrid"
+        _cloud_tensor(points, "points", who)
+        self.max_dist = _radius(max_dist, who)
+        if cell is not None:
+            cell = float(cell)
+            with np.errstate(over="ignore", divide="ignore"):
+                ok = math.isfinite(cell) and cell > 0 and math.isfinite(float(np.float32(cell))) and math.isfinite(float(np.float32(1) / np.float32(cell)))
+            if not ok:
+                raise ValueError(f"{who}: cell must be None or a finite edge > 0 with a finite fp32 reciprocal, got {cell}")
+        if box is not None:
+            if not torch.is_tensor(box) and all(isinstance(b, np.ndarray) for b in box):
+                box = np.stack([np.asarray(b, dtype=np.float32).reshape(-1) for b in box])       # (a list of arrays is the slow path of torch.as_tensor)
+            box = torch.as_tensor(box).detach().to("cpu", torch.float32)
+            if box.numel() != 6 or not bool(torch.isfinite(box).all()) or bool((box.reshape(2, 3)[1] < box.reshape(2, 3)[0]).any()):
+                raise ValueError(f"{who}: box must be (lo, hi), 2 x 3 finite numbers with lo <= hi, got {tuple(box.shape)}")
+            box = box.reshape(2, 3).tolist()
+        self.n = int(points.shape[0])
+        self.device = points.device
+        with torch.cuda.device(self.device):
+            points = points.contiguous()
+            if box is None:
+                box = [[0.0] * 3, [0.0] * 3]
+                if self.n:
+                    b = ops.grid_bounds(points).tolist()                               # the one host read
+                    if all(math.isfinite(v) for v in b):                              # (no finite row: the grid is empty, any box does)
+                        box = [b[:3], b[3:]]
+            self.lo, self.cell, self.dims = _grid_layout(box[0], box[1], self.max_dist * GRID_CELL_FACTOR if cell is None else cell, GRID_CELL_CAP)
+            self.cell_start, self.records = ops.grid_build(points, self.lo, self.cell, self.dims)
+
+    @torch.no_grad()
+    def nearest(self, query):
+        """query (N,3) fp32 on the grid's device -> (dist (N,) fp32, index (N,) int32): the grid point with the smallest d2 = (dx dx + dy dy) + dz dz (fp32,
+        every operation rounded on its own) among those with d2 <= max_dist max_dist, the lowest original index among equals, dist = sqrt(d2); +inf and -1
+        when there is none or the query row is not finite.  Exact: the grid only decides which points are looked at."""
+        _cloud_tensor(query, "query", "PointGrid.nearest")
+        if query.device != self.device:
+            raise ValueError(f"PointGrid.nearest: query must be on the grid's device {self.device}, got {query.device}")
+        with torch.cuda.device(self.device):
+            return ops.grid_nearest(self.lo, self.cell, self.dims, self.cell_start, self.records, query.contiguous(), self.max_dist)
+
+
+def _grid_layout(lo, hi, cell, cap):
+    """(lo, cell as the fp32 number, (dx, dy, dz)): dim = floor((hi - lo) / cell) + 1 per axis, the edge grown by a quarter until dx dy dz <= cap."""
+    lo = [float(np.float32(v)) for v in lo]
+    ext = [max(float(h) - l, 0.0) for l, h in zip(lo, hi)]
+    cell = float(np.float32(cell))
+    while True:
+        dims = tuple(int(e // cell) + 1 for e in ext)
+        if dims[0] * dims[1] * dims[2] <= cap:
+            return lo, cell, dims
+        cell = float(np.float32(cell * 1.25))
+
+
+class MeshSamples(tuple):
+    """What sample_mesh returns: the pair (points (P,3) fp32, face (P,) int32), with .points, .face and .count - (2,) int64 on the device: the true number
+    of points (above the rows when a capacity was given and was too small) and the largest subdivision n of any face."""
+
+    def __new__(cls, points, face, count):
+        self = super().__new__(cls, (points, face))
+        self.points, self.face, self.count = points, face, count
+        return self
+
+
+@torch.no_grad()
+def sample_mesh(mesh, spacing, capacity=None):
+    """Points on the surface of a TriangleMesh about `spacing` apart, the same bytes every run (csrc/cloud_metrics.hip).
+    Per face n = max(1, ceil(L / spacing)) with L its longest edge; the face emits the centroids of the n n congruent sub-triangles of its barycentric
+    lattice (rows j = 0..n-1 from the edge AB towards C, in a row i = 0..n-1-j from A towards B: the upward triangle, then the downward one).  A face with
+    a non-finite vertex emits nothing; a zero-area face emits its n n points like any other.  Ordered by face, then by lattice order.
+        capacity    None: the count is read from the device once, the outputs have exactly P rows, and a face that needs n > 1024 raises RuntimeError.
+                    An integer: nothing is read from the device; .count[0] is the true P (rows past it are not written), a face with n > 1024 emits
+                    nothing and .count[1] > 1024 says so.
+    Of a mesh extracted with a capacity only the first min(mesh.count, rows) vertices and faces are read."""
+    who = "sample_mesh"
+    if not (hasattr(mesh, "vertices") and hasattr(mesh, "faces")):
+        raise ValueError(f"{who}: a TriangleMesh (vertices, faces) expected, got {type(mesh).__name__}")
+    _cloud_tensor(mesh.vertices, "mesh.vertices", who)
+    if not torch.is_tensor(mesh.faces) or mesh.faces.dtype != torch.int32 or mesh.faces.dim() != 2 or mesh.faces.shape[1] != 3:
+        raise ValueError(f"{who}: mesh.faces must be an int32 tensor of shape (T,3), got {getattr(mesh.faces, 'dtype', '')} {tuple(getattr(mesh.faces, 'shape', ()))}")
+    try:
+        spacing = float(spacing)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: spacing must be a finite number > 0, got {spacing!r}") from None
+    if not (math.isfinite(spacing) and spacing > 0 and math.isfinite(float(np.float32(spacing))) and float(np.float32(spacing)) > 0):
+        raise ValueError(f"{who}: spacing must be finite and > 0, got {spacing}")
+    if capacity is not None and not 0 <= int(capacity) < 1 << 31:
+        raise ValueError(f"{who}: capacity must be None or in [0, 2^31), got {capacity}")
+    with torch.cuda.device(mesh.vertices.device):
+        points, face, count = ops.mesh_sample(mesh.vertices.contiguous(), mesh.faces.contiguous(), spacing, None if capacity is None else int(capacity),
+                                              mesh_count=getattr(mesh, "count", None))
+    return MeshSamples(points, face, count)
 
 
 def _mesh_ply(path, mesh):

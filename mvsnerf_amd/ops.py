@@ -2251,3 +2251,140 @@ def tsdf_vertex_colors(tsdf, colors, vertex_edge, count):
     check(_lib.lib().mvsnerf_tsdf_vertex_colors_fwd(p_tsdf, p_col, D, H, W, p_edge if rows else 0, count.data_ptr(), rows, out.data_ptr() if rows else 0,
                                                     stream_ptr()), "tsdf_vertex_colors_fwd")
     return out
+
+
+# ------------------------------------------------------------------ point grid, nearest neighbour, cloud metrics, points on a mesh (csrc/cloud_metrics.hip)
+GRID_MAX_CELLS = 1 << 24
+CLOUD_METRICS_MAX_TAUS = 8
+CLOUD_METRICS_ROW = 2 + CLOUD_METRICS_MAX_TAUS       # sum of the finite distances, their number, the numbers below each tau
+MESH_SAMPLE_MAX_N = 1024
+
+
+def _cloud_rows(t, name, op):
+    """A contiguous (n,3) fp32 tensor on the current GPU, n < 2^31 -> (n, pointer or 0 for n == 0)."""
+    if not (torch.is_tensor(t) and t.dim() == 2 and t.shape[1] == 3):
+        raise RuntimeError(f"{op}: {name} must be an (n,3) tensor, got {tuple(getattr(t, 'shape', ()))}")
+    n = int(t.shape[0])
+    if n >= 1 << 31:
+        raise RuntimeError(f"{op}: {name} holds {n} rows; the kernels index fewer than 2^31")
+    return n, (dev_f32(t, f"{op}: {name}") if n else 0)
+
+
+def grid_bounds(points):
+    """points (n,3) fp32 -> (6,) fp32 on the device: min xyz, max xyz over the rows whose coordinates are all finite (+inf, -inf when there is none).  Two
+    launches, min / max only: the same bits every run (mvsnerf_grid_bounds_fwd)."""
+    op = "grid_bounds"
+    _need_no_grad(points, op=op)
+    n, p = _cloud_rows(points, "points", op)
+    lib = _lib.lib()
+    ws = torch.empty((int(lib.mvsnerf_grid_bounds_workspace_bytes(n)) // 4,), device=points.device, dtype=torch.float32)
+    out = torch.empty((6,), device=points.device, dtype=torch.float32)
+    check(lib.mvsnerf_grid_bounds_fwd(p, n, out.data_ptr(), ws.data_ptr(), stream_ptr()), "grid_bounds_fwd")
+    return out
+
+
+def grid_build(points, lo, cell, dims):
+    """The uniform grid over points (n,3) fp32 (mvsnerf_grid_build_fwd): lo three host numbers, cell the edge, dims = (dx, dy, dz) cells ->
+    (cell_start (dx dy dz + 1,) int32, records (n,4) fp32: x, y, z and the bits of the original row, grouped by cell; the first cell_start[-1] rows are
+    written).  A point outside the box lands in a border cell; a row with a non-finite coordinate is left out.  The order inside a cell may differ
+    between runs."""
+    op = "grid_build"
+    _need_no_grad(points, op=op)
+    n, p = _cloud_rows(points, "points", op)
+    dx, dy, dz = (int(v) for v in dims)
+    lib = _lib.lib()
+    ws_bytes = int(lib.mvsnerf_grid_build_workspace_bytes(n, dx, dy, dz))
+    if ws_bytes == 0:
+        raise RuntimeError(f"{op}: a grid of {dx} x {dy} x {dz} cells is outside what the kernels index (every dimension >= 1, at most 2^24 cells)")
+    dev = points.device
+    cell_start = torch.empty((dx * dy * dz + 1,), device=dev, dtype=torch.int32)
+    records = torch.empty((n, 4), device=dev, dtype=torch.float32)
+    ws = torch.empty((ws_bytes // 4,), device=dev, dtype=torch.int32)
+    c_lo = (ctypes.c_float * 3)(*[float(v) for v in lo])
+    check(lib.mvsnerf_grid_build_fwd(p, n, c_lo, float(cell), dx, dy, dz, cell_start.data_ptr(), records.data_ptr() if n else 0, ws.data_ptr(),
+                                     stream_ptr()), "grid_build_fwd")
+    return cell_start, records
+
+
+def grid_nearest(lo, cell, dims, cell_start, records, query, max_dist):
+    """The exact nearest grid point within max_dist of every row of query (n,3) fp32 (mvsnerf_grid_nearest_fwd) -> (dist (n,) fp32, index (n,) int32):
+    the lowest original index among equal squared distances, +inf and -1 where nothing is within max_dist or the query is not finite."""
+    op = "grid_nearest"
+    _need_no_grad(query, op=op)
+    n, p = _cloud_rows(query, "query", op)
+    dx, dy, dz = (int(v) for v in dims)
+    dev = query.device
+    p_start = _fusion_map(cell_start, torch.int32, (dx * dy * dz + 1,), dev, "cell_start", op)
+    if not (torch.is_tensor(records) and records.dtype == torch.float32 and records.dim() == 2 and records.shape[1] == 4 and records.device == dev
+            and records.is_contiguous()):
+        raise RuntimeError(f"{op}: records must be a contiguous (n,4) float32 tensor on {dev}")
+    dist = torch.empty((n,), device=dev, dtype=torch.float32)
+    index = torch.empty((n,), device=dev, dtype=torch.int32)
+    c_lo = (ctypes.c_float * 3)(*[float(v) for v in lo])
+    check(_lib.lib().mvsnerf_grid_nearest_fwd(c_lo, float(cell), dx, dy, dz, p_start, records.data_ptr() if records.shape[0] else 0, p, n, float(max_dist),
+                                              dist.data_ptr() if n else 0, index.data_ptr() if n else 0, stream_ptr()), "grid_nearest_fwd")
+    return dist, index
+
+
+def cloud_metrics_row(dist, taus):
+    """dist (n,) fp32 on the device, taus up to 8 host numbers -> (CLOUD_METRICS_ROW,) float64 on the device: the sum of the finite distances, their
+    number, the number of distances below each tau (fp32 compare), zeros behind (mvsnerf_cloud_metrics_fwd: two launches, fixed order, no atomics)."""
+    op = "cloud_metrics_row"
+    _need_no_grad(dist, op=op)
+    if not (torch.is_tensor(dist) and dist.dim() == 1):
+        raise RuntimeError(f"{op}: dist must be an (n,) tensor")
+    n = int(dist.shape[0])
+    taus = [float(t) for t in taus]
+    if len(taus) > CLOUD_METRICS_MAX_TAUS:
+        raise RuntimeError(f"{op}: at most {CLOUD_METRICS_MAX_TAUS} thresholds, got {len(taus)}")
+    p = dev_f32(dist, f"{op}: dist") if n else 0
+    lib = _lib.lib()
+    ws_bytes = int(lib.mvsnerf_cloud_metrics_workspace_bytes(n))
+    if ws_bytes == 0:
+        raise RuntimeError(f"{op}: {n} distances are outside what the kernels index (fewer than 2^31)")
+    ws = torch.empty((ws_bytes // 8,), device=dist.device, dtype=torch.float64)
+    out = torch.empty((CLOUD_METRICS_ROW,), device=dist.device, dtype=torch.float64)
+    c_taus = (ctypes.c_float * max(len(taus), 1))(*taus)
+    check(lib.mvsnerf_cloud_metrics_fwd(p, n, c_taus, len(taus), out.data_ptr(), ws.data_ptr(), stream_ptr()), "cloud_metrics_fwd")
+    return out
+
+
+def mesh_sample(vertices, faces, spacing, capacity=None, mesh_count=None):
+    """Points on the faces (T,3) int32 of vertices (V,3) fp32 at about `spacing` apart (mvsnerf_mesh_sample_fwd; the lattice is written out in DESIGN.md 4p)
+    -> (points (P,3) fp32, face (P,) int32, count (2,) int64 on the device: the true number of points, the largest subdivision n of any face).
+    capacity None: the count runs alone and is read from the device once; a face that needs n > 1024 raises.  An integer: nothing is read from the
+    device, the outputs have that many rows, rows past count[0] are not written and a face with n > 1024 emits nothing (count[1] tells).
+    mesh_count: the (2,) int64 device counts of a mesh extracted with a capacity: rows past them are not read."""
+    op = "mesh_sample"
+    _need_no_grad(vertices, op=op)
+    V, p_v = _cloud_rows(vertices, "vertices", op)
+    dev = vertices.device
+    if not (torch.is_tensor(faces) and faces.dim() == 2 and faces.shape[1] == 3):
+        raise RuntimeError(f"{op}: faces must be a (T,3) tensor, got {tuple(getattr(faces, 'shape', ()))}")
+    T = int(faces.shape[0])
+    p_f = _fusion_map(faces, torch.int32, (T, 3), dev, "faces", op) if T else 0
+    p_mc = 0 if mesh_count is None else _fusion_map(mesh_count, torch.int64, (2,), dev, "mesh_count", op)
+    lib = _lib.lib()
+    ws_bytes = int(lib.mvsnerf_mesh_sample_workspace_bytes(T))
+    if ws_bytes == 0:
+        raise RuntimeError(f"{op}: {T} faces are outside what the kernels index (fewer than 2^31)")
+    ws = torch.empty((ws_bytes // 8,), device=dev, dtype=torch.int64)
+    count = torch.empty((2,), device=dev, dtype=torch.int64)
+
+    def run(cap):
+        points = torch.empty((cap, 3), device=dev, dtype=torch.float32)
+        face = torch.empty((cap,), device=dev, dtype=torch.int32)
+        check(lib.mvsnerf_mesh_sample_fwd(p_v, V, p_f, T, p_mc, float(spacing), cap, points.data_ptr() if cap else 0, face.data_ptr() if cap else 0,
+                                          count.data_ptr(), ws.data_ptr(), stream_ptr()), "mesh_sample_fwd")
+        return points, face
+
+    if capacity is None:
+        run(0)
+        total, n_max = (int(v) for v in count.tolist())                  # the one host read
+        if n_max > MESH_SAMPLE_MAX_N:
+            raise RuntimeError(f"{op}: unsupported shape: a face needs {n_max} subdivisions at spacing {float(spacing)} (at most {MESH_SAMPLE_MAX_N}); "
+                               "sample with a larger spacing")
+        if total >= 1 << 31:
+            raise RuntimeError(f"{op}: unsupported shape: {total} points (fewer than 2^31); sample with a larger spacing")
+        capacity = total
+    return (*run(int(capacity)), count)
