@@ -437,7 +437,13 @@ int mvsnerf_mlp_fwd_split(const void* packed_split, const float* packed_f32, int
  * One Adam update of n fp32 tensors in ONE launch per 84 tensors (host arrays of device pointers; contiguous tensors; tensors whose size is a multiple of
  * four must be 16-byte aligned):  m += (1 - beta1)(g - m);  v = beta2 v + (1 - beta2) g^2;  p -= step_size * m / (sqrt(v) / bc2_sqrt + eps)  with
  * step_size = lr / (1 - beta1^step) and bc2_sqrt = sqrt(1 - beta2^step) computed by the caller.  torch's fused Adam needs three ~25 us launches for
- * the 78 tensors of the generalizable step; mvsnerf_amd.optim.Adam (a torch.optim.Adam subclass, same state_dict) calls this instead. */
+ * the 78 tensors of the generalizable step; mvsnerf_amd.optim.Adam (a torch.optim.Adam subclass, same state_dict) calls this instead.
+ * Sizes and alignment: numel[i] < 0 is MVSNERF_EINVAL.  A tensor with numel[i] == 0 takes no part: its four pointers are not read and may be null or
+ * misaligned (torch hands out a null data_ptr() for an empty tensor).  With numel[i] > 0 a null pointer is MVSNERF_EINVAL; when numel[i] is a multiple
+ * of four, p[i], g[i], m[i] and v[i] are accessed 16 bytes at a time and each must be 16-byte aligned (MVSNERF_EALIGN), any other size needs the 4-byte
+ * alignment of a float only.  numel[i] >= 2^40, or 2^30 workgroups of 1024 elements in one launch of 84 tensors, is MVSNERF_EUNSUPPORTED.  All n tensors
+ * are checked before the first launch: a refused call has written nothing, whichever tensor it was refused for.  n == 0 is a no-op (the tables may be
+ * null).  Only the elements of p, m and v are written; g is read. */
 int mvsnerf_adam_step_multi(int n, float* const* p, const float* const* g, float* const* m, float* const* v, const int64_t* numel,
                             double step_size, double beta1, double beta2, double eps, double bc2_sqrt, void* stream);
 
