@@ -35,6 +35,7 @@
 //                         bisection of the faces' offsets, so a large face does not hold a lane back.  Ordered by face, then by lattice order; no atomics.
 // Arithmetic: fp32, every operation rounded on its own (no contraction), IEEE division and square root.
 #include "common.h"
+#include "scan_dev.h"
 #include <limits.h>
 #include <math.h>
 
@@ -68,31 +69,12 @@ __device__ __forceinline__ int cell_axis(const PointGridDesc& g, float p, int a)
     return (int)fminf(fmaxf(c, 0.0f), (float)(g.dim[a] - 1));
 }
 
-__device__ __forceinline__ float wave_min(float v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fminf(v, __shfl_down(v, off, 64));
-    return v;
-}
-__device__ __forceinline__ float wave_max(float v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_down(v, off, 64));
-    return v;
-}
-__device__ __forceinline__ double wave_sum(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
-
 // lo / hi of the workgroup's threads -> out[6] by thread 0; every thread of the workgroup calls it
 __device__ __forceinline__ void block_bounds(float lo[3], float hi[3], float* __restrict__ out)
 {
     __shared__ float s[CM_THREADS / 64][6];
 #pragma unroll
-    for (int k = 0; k < 3; ++k) { lo[k] = wave_min(lo[k]); hi[k] = wave_max(hi[k]); }
+    for (int k = 0; k < 3; ++k) { lo[k] = mvs_wave_min_down(lo[k]); hi[k] = mvs_wave_max_down(hi[k]); }
     if ((threadIdx.x & 63) == 0)
         for (int k = 0; k < 3; ++k) { s[threadIdx.x >> 6][k] = lo[k]; s[threadIdx.x >> 6][3 + k] = hi[k]; }
     __syncthreads();
@@ -137,23 +119,6 @@ __global__ __launch_bounds__(CM_THREADS) void grid_count_kernel(const float* __r
     atomicAdd(&counts[c], 1);
 }
 
-// exclusive prefix of v over the workgroup's CM_THREADS threads; s_tot: 4 ints of LDS.  Every thread of the workgroup calls it.
-__device__ __forceinline__ int block_exclusive(int v, int* s_tot)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int o = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += o;
-    }
-    if (lane == 63) s_tot[wave] = incl;
-    __syncthreads();
-    int pre = incl - v;
-    for (int w = 0; w < wave; ++w) pre += s_tot[w];
-    return pre;
-}
-
 // m entries, 2048 per workgroup: bsum[b] = the sum of workgroup b's entries
 __global__ __launch_bounds__(CM_THREADS) void grid_scan_part_kernel(const int* __restrict__ v, int m, int* __restrict__ bsum)
 {
@@ -163,34 +128,15 @@ __global__ __launch_bounds__(CM_THREADS) void grid_scan_part_kernel(const int* _
 #pragma unroll
     for (int j = 0; j < CM_SCAN_ITEMS; ++j)
         if (first + j < m) sum += v[first + j];
-    const int pre = block_exclusive(sum, s_tot);
+    const int pre = mvs_block_exclusive<CM_THREADS>(sum, s_tot);
     if (threadIdx.x == CM_THREADS - 1) bsum[blockIdx.x] = pre + sum;
 }
 
-// ONE workgroup: bsum[nb] -> its exclusive prefix, in place (nb <= 2^13 + 1)
+// ONE workgroup: bsum[nb] -> its exclusive prefix, in place (nb <= 2^13 + 1; the total is the number of finite points, < 2^31)
 __global__ __launch_bounds__(CM_SCAN_TOP) void grid_scan_top_kernel(int* __restrict__ bsum, int nb)
 {
     __shared__ int s_tot[CM_SCAN_TOP / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int c = (nb + CM_SCAN_TOP - 1) / CM_SCAN_TOP;
-    const int b = threadIdx.x * c < nb ? threadIdx.x * c : nb, e = b + c < nb ? b + c : nb;
-    int sum = 0;
-    for (int i = b; i < e; ++i) sum += bsum[i];
-    int incl = sum;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int o = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += o;
-    }
-    if (lane == 63) s_tot[wave] = incl;
-    __syncthreads();
-    int run = incl - sum;
-    for (int w = 0; w < wave; ++w) run += s_tot[w];
-    for (int i = b; i < e; ++i) {
-        const int t = bsum[i];
-        bsum[i] = run;
-        run += t;
-    }
+    mvs_block_scan_runs<CM_SCAN_TOP>(nb, [&](int i) { return bsum[i]; }, [&](int i, int pre) { bsum[i] = pre; }, s_tot);
 }
 
 // v[m] (counts) -> its exclusive prefix, in place, from the workgroups' offsets
@@ -204,7 +150,7 @@ __global__ __launch_bounds__(CM_THREADS) void grid_scan_kernel(int* __restrict__
         c[j] = first + j < m ? v[first + j] : 0;
         sum += c[j];
     }
-    int run = boff[blockIdx.x] + block_exclusive(sum, s_tot);
+    int run = boff[blockIdx.x] + mvs_block_exclusive<CM_THREADS>(sum, s_tot);
 #pragma unroll
     for (int j = 0; j < CM_SCAN_ITEMS; ++j) {
         if (first + j < m) v[first + j] = run;
@@ -296,7 +242,7 @@ __device__ __forceinline__ void block_row_sum(double row[CM_ROW], double* __rest
 {
     __shared__ double s[CM_THREADS / 64][CM_ROW];
 #pragma unroll
-    for (int k = 0; k < CM_ROW; ++k) row[k] = wave_sum(row[k]);
+    for (int k = 0; k < CM_ROW; ++k) row[k] = mvs_wave_sum_down(row[k]);
     if ((threadIdx.x & 63) == 0)
         for (int k = 0; k < CM_ROW; ++k) s[threadIdx.x >> 6][k] = row[k];
     __syncthreads();
@@ -373,15 +319,13 @@ __global__ __launch_bounds__(CM_THREADS) void sample_count_kernel(MeshSoup m, in
     const int64_t f = (int64_t)blockIdx.x * CM_THREADS + threadIdx.x;
     float A[3], B[3], C[3];
     const int n = f < m.T ? face_n(m, f, A, B, C) : 0;
-    const int cnt = face_points(n);
-    const int pre = block_exclusive(cnt, s_tot);
-    int mx = n;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) mx = max(mx, __shfl_down(mx, off, 64));
+    const int mx = mvs_wave_max_down(n);
     if ((threadIdx.x & 63) == 0) s_max[threadIdx.x >> 6] = mx;
-    __syncthreads();
-    if (threadIdx.x == CM_THREADS - 1) bsum[blockIdx.x] = pre + cnt;
-    if (threadIdx.x == 0) bmax[blockIdx.x] = max(max(s_max[0], s_max[1]), max(s_max[2], s_max[3]));
+    const int total = mvs_block_sum<CM_THREADS>(mvs_wave_sum_down(face_points(n)), s_tot);             // (its barrier covers s_max too)
+    if (threadIdx.x == 0) {
+        bsum[blockIdx.x] = total;
+        bmax[blockIdx.x] = max(max(s_max[0], s_max[1]), max(s_max[2], s_max[3]));
+    }
 }
 
 // ONE workgroup: boff = exclusive prefix of bsum (int64), count[0] = the total, count[1] = the largest n
@@ -390,33 +334,15 @@ __global__ __launch_bounds__(SM_SCAN_THREADS) void sample_scan_kernel(const int6
 {
     __shared__ int64_t s_tot[SM_SCAN_THREADS / 64];
     __shared__ int s_max[SM_SCAN_THREADS / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int c = (nb + SM_SCAN_THREADS - 1) / SM_SCAN_THREADS;                          // nb <= 2^23: threadIdx.x * c < 2^23 + 2^10
-    const int b = threadIdx.x * c < nb ? threadIdx.x * c : nb, e = b + c < nb ? b + c : nb;
-    int64_t sum = 0;
     int mx = 0;
-    for (int i = b; i < e; ++i) { sum += bsum[i]; mx = max(mx, bmax[i]); }
-    int64_t incl = sum;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int64_t o = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += o;
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) mx = max(mx, __shfl_down(mx, off, 64));
-    if (lane == 63) s_tot[wave] = incl;
-    if (lane == 0) s_max[wave] = mx;
-    __syncthreads();
-    int64_t run = incl - sum;
-    for (int w = 0; w < wave; ++w) run += s_tot[w];
-    for (int i = b; i < e; ++i) {
-        boff[i] = run;
-        run += bsum[i];
-    }
+    for (int i = threadIdx.x; i < nb; i += SM_SCAN_THREADS) mx = max(mx, bmax[i]);       // (a maximum: any order)
+    mx = mvs_wave_max_down(mx);
+    if ((threadIdx.x & 63) == 0) s_max[threadIdx.x >> 6] = mx;
+    // nb <= 2^23: the run arithmetic stays below 2^23 + 2^10, and the total below 2^23 * 2^28.  (The scan's barrier covers s_max too.)
+    const int64_t total = mvs_block_scan_runs<SM_SCAN_THREADS>(nb, [&](int i) { return bsum[i]; }, [&](int i, int64_t pre) { boff[i] = pre; }, s_tot);
     if (threadIdx.x == 0) {
-        int64_t total = 0;
         int all = 0;
-        for (int w = 0; w < SM_SCAN_THREADS / 64; ++w) { total += s_tot[w]; all = max(all, s_max[w]); }
+        for (int w = 0; w < SM_SCAN_THREADS / 64; ++w) all = max(all, s_max[w]);
         count[0] = total;
         count[1] = all;
     }
@@ -429,7 +355,7 @@ __global__ __launch_bounds__(CM_THREADS) void sample_offsets_kernel(MeshSoup m, 
     const int64_t f = (int64_t)blockIdx.x * CM_THREADS + threadIdx.x;
     float A[3], B[3], C[3];
     const int cnt = f < m.T ? face_points(face_n(m, f, A, B, C)) : 0;
-    const int pre = block_exclusive(cnt, s_tot);
+    const int pre = mvs_block_exclusive<CM_THREADS>(cnt, s_tot);
     if (f < m.T) foff[f] = boff[blockIdx.x] + pre;
 }
 
@@ -462,7 +388,6 @@ __global__ __launch_bounds__(CM_THREADS) void sample_points_kernel(MeshSoup m, c
     face[p] = (int)lo;
 }
 
-inline bool misaligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
 inline bool rows_ok(int64_t n) { return n >= 0 && n < ((int64_t)1 << 31); }
 
 // dims >= 1 and dx dy dz <= 2^24
@@ -497,7 +422,7 @@ extern "C" int mvsnerf_grid_bounds_fwd(const float* points, int64_t n, float* bo
 {
     if (!bounds || !workspace || n < 0 || (n > 0 && !points)) return MVSNERF_EINVAL;
     if (!rows_ok(n)) return MVSNERF_EUNSUPPORTED;
-    if (misaligned(points, 4) || misaligned(bounds, 4) || misaligned(workspace, 4)) return MVSNERF_EALIGN;
+    if (mvs_misaligned(points, 4) || mvs_misaligned(bounds, 4) || mvs_misaligned(workspace, 4)) return MVSNERF_EALIGN;
     hipStream_t st = (hipStream_t)stream;
     const int nb = (int)((n + CM_THREADS * CM_BOUNDS_ROWS - 1) / (CM_THREADS * CM_BOUNDS_ROWS));      // <= 2^20
     float* part = static_cast<float*>(workspace);
@@ -525,7 +450,7 @@ extern "C" int mvsnerf_grid_build_fwd(const float* points, int64_t n, const floa
     int64_t cells;
     PointGridDesc g;
     if (!rows_ok(n) || !grid_cells(dx, dy, dz, &cells) || !grid_desc(lo, cell, dx, dy, dz, &g)) return MVSNERF_EUNSUPPORTED;
-    if (misaligned(points, 4) || misaligned(cell_start, 4) || misaligned(records, 16) || misaligned(workspace, 4)) return MVSNERF_EALIGN;
+    if (mvs_misaligned(points, 4) || mvs_misaligned(cell_start, 4) || mvs_misaligned(records, 16) || mvs_misaligned(workspace, 4)) return MVSNERF_EALIGN;
     hipStream_t st = (hipStream_t)stream;
     const int m = (int)cells + 1;
     const int nbs = (int)scan_blocks(m);                                                 // <= 2^13 + 1
@@ -562,7 +487,7 @@ extern "C" int mvsnerf_grid_nearest_fwd(const float* lo, float cell, int dx, int
     if (!rows_ok(n_query) || !grid_cells(dx, dy, dz, &cells) || !grid_desc(lo, cell, dx, dy, dz, &g)) return MVSNERF_EUNSUPPORTED;
     const float r2 = max_dist * max_dist;
     if (!(isfinite(max_dist) && max_dist > 0.0f && isfinite(r2))) return MVSNERF_EUNSUPPORTED;
-    if (misaligned(cell_start, 4) || misaligned(records, 16) || misaligned(query, 4) || misaligned(dist, 4) || misaligned(index, 4)) return MVSNERF_EALIGN;
+    if (mvs_misaligned(cell_start, 4) || mvs_misaligned(records, 16) || mvs_misaligned(query, 4) || mvs_misaligned(dist, 4) || mvs_misaligned(index, 4)) return MVSNERF_EALIGN;
     if (n_query == 0) return MVSNERF_OK;
     grid_nearest_kernel<<<mvs_cdiv(n_query, CM_THREADS), CM_THREADS, 0, (hipStream_t)stream>>>(g, cell_start, reinterpret_cast<const float4*>(records), query,
                                                                                               n_query, r2, dist, index);
@@ -581,7 +506,7 @@ extern "C" int mvsnerf_cloud_metrics_fwd(const float* dist, int64_t n, const flo
 {
     if (!out || !workspace || n < 0 || (n > 0 && !dist) || n_tau < 0 || (n_tau > 0 && !taus)) return MVSNERF_EINVAL;
     if (!rows_ok(n) || n_tau > CM_MAX_TAUS) return MVSNERF_EUNSUPPORTED;
-    if (misaligned(dist, 4) || misaligned(out, 8) || misaligned(workspace, 8)) return MVSNERF_EALIGN;
+    if (mvs_misaligned(dist, 4) || mvs_misaligned(out, 8) || mvs_misaligned(workspace, 8)) return MVSNERF_EALIGN;
     hipStream_t st = (hipStream_t)stream;
     MetricTaus t{};
     t.n = n_tau;
@@ -611,8 +536,8 @@ extern "C" int mvsnerf_mesh_sample_fwd(const float* vertices, int64_t n_vertices
     if (!count || !workspace || n_vertices < 0 || n_faces < 0 || capacity < 0) return MVSNERF_EINVAL;
     if ((n_vertices > 0 && !vertices) || (n_faces > 0 && !faces) || (capacity > 0 && (!points || !face))) return MVSNERF_EINVAL;
     if (!rows_ok(n_vertices) || !rows_ok(n_faces) || !rows_ok(capacity) || !(isfinite(spacing) && spacing > 0.0f)) return MVSNERF_EUNSUPPORTED;
-    if (misaligned(vertices, 4) || misaligned(faces, 4) || misaligned(mesh_count, 8) || misaligned(points, 4) || misaligned(face, 4) ||
-        misaligned(count, 8) || misaligned(workspace, 8))
+    if (mvs_misaligned(vertices, 4) || mvs_misaligned(faces, 4) || mvs_misaligned(mesh_count, 8) || mvs_misaligned(points, 4) || mvs_misaligned(face, 4) ||
+        mvs_misaligned(count, 8) || mvs_misaligned(workspace, 8))
         return MVSNERF_EALIGN;
     hipStream_t st = (hipStream_t)stream;
     const int nb = (int)((n_faces + CM_THREADS - 1) / CM_THREADS);                       // <= 2^23

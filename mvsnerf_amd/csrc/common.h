@@ -10,7 +10,9 @@
         if (e__ != hipSuccess) return (int)e__;             \
     } while (0)
 
-static inline bool mvs_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+// a: a power of two.  A NULL pointer is aligned (the entries test for NULL on their own)
+static inline bool mvs_misaligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
+static inline bool mvs_aligned16(const void* p) { return !mvs_misaligned(p, 16); }
 static inline unsigned mvs_cdiv(int64_t a, int64_t b) { return (unsigned)((a + b - 1) / b); }
 
 // Raising a kernel's dynamic-LDS cap is a per-DEVICE attribute: remember it per device (bit d of *done_mask), so that a process that

@@ -13,12 +13,13 @@
 //                      A source id outside [0, M) (-1 is the padding) or equal to r is skipped: no id makes the kernel read outside the inputs.
 // cloud_count_kernel   a workgroup owns PC_TILE = 1024 consecutive pixels, four rounds of 256; each wave ballots its mask bytes and counts the bits, the
 //                      four waves' counts meet in LDS -> one count per workgroup.
-// cloud_scan_kernel    ONE workgroup: exclusive scan of the workgroup counts (a thread owns a contiguous run; shuffle scan inside a wave, the four wave
-//                      totals through LDS) and the total -> *count (int64).  One level: fewer than 2^21 workgroup counts.
+// cloud_scan_kernel    ONE workgroup: exclusive scan of the workgroup counts (scan_dev.h) and the total -> *count (int64).  One level: fewer than 2^21
+//                      workgroup counts.
 // cloud_write_kernel   ballots the mask bytes again; a kept pixel's slot is the workgroup's offset + the bits of the words in front of its own (through
 //                      LDS) + mbcnt of its own word: slot order = flat-ray-index order (view-major, then row-major), the order of torch.nonzero, and every
 //                      run gives the same bytes.  A slot >= capacity is not written.  (sparse.hip's live_* kernels are the pattern.)
 #include "common.h"
+#include "scan_dev.h"
 #include <math.h>
 
 namespace {
@@ -124,40 +125,24 @@ __global__ __launch_bounds__(DC_THREADS) void depth_consistency_kernel(FusionVie
 __global__ __launch_bounds__(PC_THREADS) void cloud_count_kernel(const unsigned char* __restrict__ mask, int64_t n, int* __restrict__ counts)
 {
     __shared__ int s_cnt[PC_THREADS / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int c = 0;
+    int c = 0;                                                           // the wave's count, in every lane of it
 #pragma unroll
     for (int r = 0; r < PC_ROUNDS; ++r) {
         const int64_t t = (int64_t)blockIdx.x * PC_TILE + r * PC_THREADS + threadIdx.x;
         const bool keep = t < n && mask[t] != 0;
         c += __popcll(__ballot(keep));
     }
-    if (lane == 0) s_cnt[wave] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) counts[blockIdx.x] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+    const int total = mvs_block_sum<PC_THREADS>(c, s_cnt);
+    if (threadIdx.x == 0) counts[blockIdx.x] = total;
 }
 
 __global__ __launch_bounds__(PC_SCAN_THREADS) void cloud_scan_kernel(const int* __restrict__ counts, int nb, int* __restrict__ offsets,
                                                                      int64_t* __restrict__ count)
 {
     __shared__ int s_tot[PC_SCAN_THREADS / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int c = (nb + PC_SCAN_THREADS - 1) / PC_SCAN_THREADS;          // run length: nb <= 2^21, so threadIdx.x * c stays far inside 32 bits
-    const int b = threadIdx.x * c < nb ? threadIdx.x * c : nb, e = b + c < nb ? b + c : nb;
-    int sum = 0;                                                         // the total is < 2^31 (one bit per pixel)
-    for (int i = b; i < e; ++i) sum += counts[i];
-    int incl = sum;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int o = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += o;
-    }
-    if (lane == 63) s_tot[wave] = incl;
-    __syncthreads();
-    int run = incl - sum;
-    for (int w = 0; w < wave; ++w) run += s_tot[w];
-    for (int i = b; i < e; ++i) { offsets[i] = run; run += counts[i]; }
-    if (threadIdx.x == 0) *count = (int64_t)s_tot[0] + s_tot[1] + s_tot[2] + s_tot[3];
+    // nb <= 2^21, so the run arithmetic stays far inside 32 bits; the total is < 2^31 (one bit per pixel)
+    const int total = mvs_block_scan_runs<PC_SCAN_THREADS>(nb, [&](int i) { return counts[i]; }, [&](int i, int pre) { offsets[i] = pre; }, s_tot);
+    if (threadIdx.x == 0) *count = total;
 }
 
 __global__ __launch_bounds__(PC_THREADS) void cloud_write_kernel(FusionViews v, const float* __restrict__ fused, const unsigned* __restrict__ seen,
@@ -180,10 +165,7 @@ __global__ __launch_bounds__(PC_THREADS) void cloud_write_kernel(FusionViews v, 
     for (int r = 0; r < PC_ROUNDS; ++r) {
         if (!((m[r] >> lane) & 1ull)) continue;
         const int w = r * (PC_THREADS / 64) + wave;
-        int pre = 0;
-        for (int k = 0; k < w; ++k) pre += s_pop[k];
-        const int rank = __builtin_amdgcn_mbcnt_hi((unsigned)(m[r] >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m[r], 0u));
-        const int64_t j = base + pre + rank;
+        const int64_t j = base + mvs_tile_rank(s_pop, w, m[r]);
         if (j < 0 || j >= capacity) continue;                            // the caller's rows and no others
         const int64_t t = (int64_t)blockIdx.x * PC_TILE + r * PC_THREADS + threadIdx.x;         // < n: the ballot sets no bit past the end
         int x, y, view;
@@ -197,8 +179,6 @@ __global__ __launch_bounds__(PC_THREADS) void cloud_write_kernel(FusionViews v, 
         index[j] = t;
     }
 }
-
-inline bool misaligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
 
 // M, H, W of both entries: sizes < 1 are MVSNERF_EINVAL, H or W < 2 (no bilinear cell) and M H W >= 2^31 MVSNERF_EUNSUPPORTED
 int fusion_sizes(int M, int H, int W, int64_t* n)
@@ -222,8 +202,8 @@ extern "C" int mvsnerf_depth_consistency_fwd(const float* depth, const unsigned 
     if (n_src < 1 || n_src > 32 || min_views < 0 || !(isfinite(pix_thr) && pix_thr > 0.0f) || !(isfinite(rel_thr) && rel_thr > 0.0f)) return MVSNERF_EINVAL;
     int64_t n;
     if (int rc = fusion_sizes(M, H, W, &n)) return rc;
-    if (misaligned(depth, 4) || misaligned(images_rgba, 4) || misaligned(c2w, 4) || misaligned(w2c, 4) || misaligned(K, 4) || misaligned(src_ids, 4) ||
-        misaligned(seen, 4) || misaligned(fused, 4))
+    if (mvs_misaligned(depth, 4) || mvs_misaligned(images_rgba, 4) || mvs_misaligned(c2w, 4) || mvs_misaligned(w2c, 4) || mvs_misaligned(K, 4) || mvs_misaligned(src_ids, 4) ||
+        mvs_misaligned(seen, 4) || mvs_misaligned(fused, 4))
         return MVSNERF_EALIGN;
     const int tiles = (int)(((int64_t)H * W + DC_THREADS - 1) / DC_THREADS);
     const FusionViews v{depth, valid, images_rgba, c2w, w2c, K, M, H, W};
@@ -247,8 +227,8 @@ extern "C" int mvsnerf_point_cloud_fwd(const unsigned char* images_rgba, const f
     if (capacity > 0 && (!images_rgba || !c2w || !K || !fused || !seen || !points || !colors || !n_views || !index)) return MVSNERF_EINVAL;
     int64_t n;
     if (int rc = fusion_sizes(M, H, W, &n)) return rc;
-    if (misaligned(images_rgba, 4) || misaligned(c2w, 4) || misaligned(K, 4) || misaligned(fused, 4) || misaligned(seen, 4) || misaligned(points, 4) ||
-        misaligned(index, 8) || misaligned(count, 8) || misaligned(workspace, 4))
+    if (mvs_misaligned(images_rgba, 4) || mvs_misaligned(c2w, 4) || mvs_misaligned(K, 4) || mvs_misaligned(fused, 4) || mvs_misaligned(seen, 4) || mvs_misaligned(points, 4) ||
+        mvs_misaligned(index, 8) || mvs_misaligned(count, 8) || mvs_misaligned(workspace, 4))
         return MVSNERF_EALIGN;
     hipStream_t st = (hipStream_t)stream;
     const int64_t nb = cloud_blocks(n);

@@ -10,6 +10,7 @@
 //                            index is computed once per pixel.  The colour table (768 bytes) is staged in LDS.
 // Arithmetic: fp32, every operation rounded on its own (no contraction), IEEE division - what numpy does on float32 arrays.
 #include "common.h"
+#include "scan_dev.h"
 #include <float.h>
 #include <math.h>
 
@@ -28,15 +29,6 @@ __device__ __forceinline__ float nan_to_num_f(float x)
     return x;
 }
 
-__device__ __forceinline__ void wave_minmax(float& lo, float& hi)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        lo = fminf(lo, __shfl_down(lo, off, 64));
-        hi = fmaxf(hi, __shfl_down(hi, off, 64));
-    }
-}
-
 __global__ __launch_bounds__(DR_THREADS) void depth_range_part_kernel(const float* __restrict__ depth, int64_t n, float* __restrict__ part)
 {
     __shared__ float s_lo[DR_THREADS / 64], s_hi[DR_THREADS / 64];
@@ -46,7 +38,7 @@ __global__ __launch_bounds__(DR_THREADS) void depth_range_part_kernel(const floa
         if (x > 0.f) lo = fminf(lo, x);
         hi = fmaxf(hi, x);
     }
-    wave_minmax(lo, hi);
+    lo = mvs_wave_min_down(lo); hi = mvs_wave_max_down(hi);
     if ((threadIdx.x & 63) == 0) { s_lo[threadIdx.x >> 6] = lo; s_hi[threadIdx.x >> 6] = hi; }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -59,7 +51,7 @@ __global__ __launch_bounds__(64) void depth_range_final_kernel(const float* __re
 {
     float lo = INFINITY, hi = -FLT_MAX;
     for (int i = threadIdx.x; i < nparts; i += 64) { lo = fminf(lo, part[2 * i]); hi = fmaxf(hi, part[2 * i + 1]); }
-    wave_minmax(lo, hi);
+    lo = mvs_wave_min_down(lo); hi = mvs_wave_max_down(hi);
     if (threadIdx.x == 0) { out2[0] = lo; out2[1] = hi; }
 }
 

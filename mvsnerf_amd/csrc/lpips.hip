@@ -18,6 +18,7 @@
 //                          partials in a fixed order and divides by the pixel count.  No atomics: two calls give equal bits, frame k of a batch the bits of
 //                          the frame alone.
 #include "common.h"
+#include "scan_dev.h"
 
 namespace {
 
@@ -260,8 +261,7 @@ __global__ __launch_bounds__(64) void lpips_head_sum_kernel(const double* __rest
     const int k = blockIdx.x, lane = threadIdx.x;
     double v = 0.0;
     for (int t = lane; t < nblk; t += 64) v += partial[(size_t)k * nblk + t];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    v = mvs_wave_sum_down(v);
     if (lane == 0) {
         v /= (double)npix;
         if (layer_out) layer_out[k] = v;

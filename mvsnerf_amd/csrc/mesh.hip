@@ -7,9 +7,8 @@
 //
 // mesh_classify_kernel   one thread per node: the 8 corners of its cell (neighbouring threads run along W) -> the 7-bit owned-edge mask (1 byte) and the
 //                        workgroup's numbers of vertices (mask bits) and faces (0..12 per cell).
-// mesh_scan_kernel       ONE workgroup of 1024: exclusive offsets of both arrays of workgroup counts and the two totals -> count[2] (int64).  A thread owns a
-//                        contiguous run; shuffle scan inside a wave, the 16 wave totals through LDS (depth_fusion.hip's cloud_scan_kernel, with the vertex
-//                        and the face count of a workgroup carried in the two halves of one 64-bit word: one pass for both).
+// mesh_scan_kernel       ONE workgroup of 1024: exclusive offsets of both arrays of workgroup counts and the two totals -> count[2] (int64): the scan
+//                        of scan_dev.h with the vertex and the face count of a workgroup carried in the two halves of one 64-bit word - one pass for both.
 // mesh_vertices_kernel   in-workgroup scan of the mask popcounts + the workgroup's offset -> vbase[node] (int32, every node); rows < capacity of
 //                        vertices, ndc and vertex_edge.
 // mesh_faces_kernel      (a launch of its own: it reads vbase and mask of nodes of other workgroups) in-workgroup scan of the cells' face counts + the
@@ -21,6 +20,7 @@
 // No atomics: the order is what the scans produce, two runs give the same bytes.  Rows >= capacity are never written.
 // Arithmetic: fp32, every operation rounded on its own (no contraction), IEEE division - what numpy does on float32 arrays.
 #include "common.h"
+#include "scan_dev.h"
 #include <math.h>
 
 #pragma clang fp contract(off)
@@ -127,29 +127,6 @@ __device__ __forceinline__ int cell_faces(unsigned corners)
     return f;
 }
 
-__device__ __forceinline__ int wave_sum(int v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
-// exclusive prefix of v over the workgroup's MT_THREADS threads; s_tot: 4 ints of LDS.  Every thread of the workgroup calls it.
-__device__ __forceinline__ int block_exclusive(int v, int* s_tot)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int o = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += o;
-    }
-    if (lane == 63) s_tot[wave] = incl;
-    __syncthreads();
-    int pre = incl - v;
-    for (int w = 0; w < wave; ++w) pre += s_tot[w];
-    return pre;
-}
-
 __global__ __launch_bounds__(MT_THREADS) void mesh_classify_kernel(MeshGrid g, unsigned char* __restrict__ mask, int* __restrict__ vcount,
                                                                    int* __restrict__ fcount)
 {
@@ -165,13 +142,13 @@ __global__ __launch_bounds__(MT_THREADS) void mesh_classify_kernel(MeshGrid g, u
         nv = __popc(m);
         nf = cell_faces(corners);
     }
-    nv = wave_sum(nv);
-    nf = wave_sum(nf);
-    if ((threadIdx.x & 63) == 0) { s_v[threadIdx.x >> 6] = nv; s_f[threadIdx.x >> 6] = nf; }
-    __syncthreads();
+    nv = mvs_wave_sum_down(nv);
+    nf = mvs_wave_sum_down(nf);
+    if ((threadIdx.x & 63) == 0) s_f[threadIdx.x >> 6] = nf;
+    nv = mvs_block_sum<MT_THREADS>(nv, s_v);                             // (its barrier covers s_f too)
     if (threadIdx.x == 0) {
-        vcount[blockIdx.x] = s_v[0] + s_v[1] + s_v[2] + s_v[3];
-        fcount[blockIdx.x] = s_f[0] + s_f[1] + s_f[2] + s_f[3];
+        vcount[blockIdx.x] = nv;
+        fcount[blockIdx.x] = mvs_waves_total<MT_THREADS>(s_f);
     }
 }
 
@@ -181,32 +158,12 @@ __global__ __launch_bounds__(MT_SCAN_THREADS) void mesh_scan_kernel(const int* _
 {
     typedef unsigned long long u64;
     __shared__ u64 s_tot[MT_SCAN_THREADS / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int* vcount = counts;
-    const int* fcount = counts + nb;
-    const int c = (nb + MT_SCAN_THREADS - 1) / MT_SCAN_THREADS;          // run length: nb <= 2^19, so threadIdx.x * c < 2^19 + 2^10
-    const int b = threadIdx.x * c < nb ? threadIdx.x * c : nb, e = b + c < nb ? b + c : nb;
-    // both sums in one word, faces above vertices: the vertex total is < 7 * 2^27 < 2^32, so nothing carries over, and the face total < 12 * 2^27 < 2^31
-    u64 sum = 0;
-    for (int i = b; i < e; ++i) sum += (u64)(unsigned)vcount[i] | ((u64)(unsigned)fcount[i] << 32);
-    u64 incl = sum;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const u64 o = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += o;
-    }
-    if (lane == 63) s_tot[wave] = incl;
-    __syncthreads();
-    u64 run = incl - sum;
-    for (int w = 0; w < wave; ++w) run += s_tot[w];
-    for (int i = b; i < e; ++i) {
-        offsets[i] = (int)(unsigned)run;
-        offsets[nb + i] = (int)(unsigned)(run >> 32);
-        run += (u64)(unsigned)vcount[i] | ((u64)(unsigned)fcount[i] << 32);
-    }
+    // both sums in one word, faces above vertices: the vertex total is < 7 * 2^27 < 2^32, so nothing carries over, and the face total < 12 * 2^27 < 2^31.
+    // nb <= 2^19, so the run arithmetic stays below 2^19 + 2^10
+    const u64 total = mvs_block_scan_runs<MT_SCAN_THREADS>(
+        nb, [&](int i) { return (u64)(unsigned)counts[i] | ((u64)(unsigned)counts[nb + i] << 32); },
+        [&](int i, u64 pre) { offsets[i] = (int)(unsigned)pre; offsets[nb + i] = (int)(unsigned)(pre >> 32); }, s_tot);
     if (threadIdx.x == 0) {
-        u64 total = 0;
-        for (int w = 0; w < MT_SCAN_THREADS / 64; ++w) total += s_tot[w];
         count[0] = (int64_t)(total & 0xffffffffull);
         count[1] = (int64_t)(total >> 32);
     }
@@ -226,7 +183,7 @@ __global__ __launch_bounds__(MT_THREADS) void mesh_vertices_kernel(MeshGrid g, M
     __shared__ int s_tot[MT_THREADS / 64];
     const int n = blockIdx.x * MT_THREADS + threadIdx.x;
     const unsigned m = n < g.N ? mask[n] : 0u;
-    const int base = voffset[blockIdx.x] + block_exclusive(__popc(m), s_tot);
+    const int base = voffset[blockIdx.x] + mvs_block_exclusive<MT_THREADS>((int)__popc(m), s_tot);
     if (n >= g.N) return;
     vbase[n] = base;
     if (!m || base >= capacity) return;
@@ -273,7 +230,7 @@ __global__ __launch_bounds__(MT_THREADS) void mesh_faces_kernel(MeshGrid g, cons
         corners = cell_corners(g, n, i, j, k);
     }
     const int nf = cell_faces(corners);
-    const int base = foffset[blockIdx.x] + block_exclusive(nf, s_tot);
+    const int base = foffset[blockIdx.x] + mvs_block_exclusive<MT_THREADS>(nf, s_tot);
     if (!nf || base >= capacity) return;
     int64_t row = base;
 #pragma unroll
@@ -319,8 +276,6 @@ __global__ __launch_bounds__(256) void mesh_rgb_u8_kernel(const float* __restric
     for (int k = 0; k < 3; ++k) rgb[t * 3 + k] = (unsigned char)(int)(fminf(fmaxf(v[k], 0.f), 1.f) * 255.f);      // NaN -> 0
 }
 
-inline bool misaligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
-
 inline int64_t mesh_blocks(int64_t n) { return (n + MT_THREADS - 1) / MT_THREADS; }
 
 // D, H, W >= 2 and D H W <= 2^27
@@ -352,8 +307,8 @@ extern "C" int mvsnerf_mesh_extract_masked_fwd(const float* field, const unsigne
     if (cap_faces > 0 && !faces) return MVSNERF_EINVAL;
     int64_t n;
     if (!mesh_nodes(D, H, W, &n) || !isfinite(level) || (positions && box)) return MVSNERF_EUNSUPPORTED;
-    if (misaligned(field, 4) || misaligned(positions, 4) || misaligned(vertices, 4) || misaligned(ndc, 4) || misaligned(vertex_edge, 8) ||
-        misaligned(faces, 4) || misaligned(count, 8) || misaligned(workspace, 4))
+    if (mvs_misaligned(field, 4) || mvs_misaligned(positions, 4) || mvs_misaligned(vertices, 4) || mvs_misaligned(ndc, 4) || mvs_misaligned(vertex_edge, 8) ||
+        mvs_misaligned(faces, 4) || mvs_misaligned(count, 8) || mvs_misaligned(workspace, 4))
         return MVSNERF_EALIGN;
     hipStream_t st = (hipStream_t)stream;
     const int64_t nb = mesh_blocks(n);                                   // <= 2^19
@@ -390,7 +345,7 @@ extern "C" int mvsnerf_mesh_dirs_fwd(const float* vertices, const float* origin,
 {
     if (n < 0 || !origin || (n > 0 && (!vertices || !dirs))) return MVSNERF_EINVAL;
     if (n >= ((int64_t)1 << 31)) return MVSNERF_EUNSUPPORTED;
-    if (misaligned(vertices, 4) || misaligned(origin, 4) || misaligned(dirs, 4)) return MVSNERF_EALIGN;
+    if (mvs_misaligned(vertices, 4) || mvs_misaligned(origin, 4) || mvs_misaligned(dirs, 4)) return MVSNERF_EALIGN;
     if (n == 0) return MVSNERF_OK;
     mesh_dirs_kernel<<<mvs_cdiv(n * 3, 256), 256, 0, (hipStream_t)stream>>>(vertices, origin, n * 3, dirs);      // < 2^25 workgroups
     MVS_LAUNCH_CHECK();
@@ -401,7 +356,7 @@ extern "C" int mvsnerf_mesh_rgb_u8_fwd(const float* rgba, int64_t n, unsigned ch
 {
     if (n < 0 || (n > 0 && (!rgba || !rgb))) return MVSNERF_EINVAL;
     if (n >= ((int64_t)1 << 31)) return MVSNERF_EUNSUPPORTED;
-    if (misaligned(rgba, 16)) return MVSNERF_EALIGN;
+    if (mvs_misaligned(rgba, 16)) return MVSNERF_EALIGN;
     if (n == 0) return MVSNERF_OK;
     mesh_rgb_u8_kernel<<<mvs_cdiv(n, 256), 256, 0, (hipStream_t)stream>>>(rgba, n, rgb);
     MVS_LAUNCH_CHECK();

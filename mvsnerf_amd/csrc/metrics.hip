@@ -15,6 +15,7 @@
 //                             then a fixed shuffle tree over the 16 lanes, all in double.  The order depends on H, W and WIN only: frame k of a batch has
 //                             the bits of the same frame alone.
 #include "common.h"
+#include "scan_dev.h"
 
 #pragma clang fp contract(off)      // pred == gt must give bit-equal x / y / xy moments and a quotient of exactly 1: every fused product below is an explicit fmaf
 
@@ -153,12 +154,7 @@ __global__ __launch_bounds__(MT_THREADS) void frame_metrics_tile_kernel(MetricsP
 
     // ---- fixed-order reduction: shuffle tree inside each wave, then the four waves in order
 #pragma unroll
-    for (int e = 0; e < ROW; ++e) {
-        double v = acc[e];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-        acc[e] = v;
-    }
+    for (int e = 0; e < ROW; ++e) acc[e] = mvs_wave_sum_down(acc[e]);
     if ((tid & 63) == 0) {
 #pragma unroll
         for (int e = 0; e < ROW; ++e) s_red[tid >> 6][e] = acc[e];

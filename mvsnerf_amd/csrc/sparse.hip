@@ -8,8 +8,7 @@
 //
 // live_count_kernel    a workgroup owns LS_TILE = 1024 consecutive samples, four rounds of 256; each wave ballots its 64 predicates, stores the
 //                      ballot word (16 words per workgroup) and counts its bits; the four waves' counts meet in LDS -> one count per workgroup.
-// live_scan_kernel     ONE workgroup: exclusive scan of the workgroup counts (a thread owns a contiguous run; shuffle scan inside a wave, the four
-//                      wave totals through LDS) and the total -> *count.
+// live_scan_kernel     ONE workgroup: exclusive scan of the workgroup counts (scan_dev.h) and the total -> *count.
 // live_write_kernel    reads the ballot words back (the predicate is evaluated once): a live lane's slot is the workgroup's offset + the bits of
 //                      the words in front of its own (through LDS) + mbcnt of its own word.  Slot order = sample order: idx is ascending, the
 //                      order of torch.nonzero, and every run gives the same bytes.  Nothing is placed with an atomic and no workgroup waits on
@@ -35,6 +34,7 @@
 #include "common.h"
 #include "composite_wave.h"
 #include "density_cell.h"
+#include "scan_dev.h"
 #include <math.h>
 
 #pragma clang fp contract(off)
@@ -83,7 +83,7 @@ __device__ __forceinline__ void live_count_tile(const float* __restrict__ densit
 {
     __shared__ int s_cnt[LS_THREADS / 64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int n = 0;
+    int n = 0;                                                          // the wave's count, in every lane of it
 #pragma unroll
     for (int r = 0; r < LS_ROUNDS; ++r) {
         const int64_t t = (int64_t)blockIdx.x * LS_TILE + r * LS_THREADS + threadIdx.x;
@@ -103,9 +103,8 @@ __device__ __forceinline__ void live_count_tile(const float* __restrict__ densit
         if (lane == 0) masks[(int64_t)blockIdx.x * LS_WORDS + r * (LS_THREADS / 64) + wave] = m;      // all 16 words, the tail's zeros too
         n += __popcll(m);
     }
-    if (lane == 0) s_cnt[wave] = n;
-    __syncthreads();
-    if (threadIdx.x == 0) counts[blockIdx.x] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+    const int total = mvs_block_sum<LS_THREADS>(n, s_cnt);
+    if (threadIdx.x == 0) counts[blockIdx.x] = total;
 }
 
 __global__ __launch_bounds__(LS_THREADS) void live_count_kernel(const float* __restrict__ density, int D, int H, int W, float thr,
@@ -125,23 +124,9 @@ __global__ __launch_bounds__(LS_THREADS) void live_count_range_kernel(const floa
 __global__ __launch_bounds__(SCAN_THREADS) void live_scan_kernel(const int* __restrict__ counts, int nb, int* __restrict__ offsets, int* __restrict__ count)
 {
     __shared__ int s_tot[SCAN_THREADS / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int c = (nb + SCAN_THREADS - 1) / SCAN_THREADS;                // run length: nb < 2^21 + 1, so threadIdx.x * c stays far inside 32 bits
-    const int b = threadIdx.x * c, e = b + c < nb ? b + c : nb;
-    int sum = 0;
-    for (int i = b; i < e; ++i) sum += counts[i];
-    int incl = sum;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int o = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += o;
-    }
-    if (lane == 63) s_tot[wave] = incl;
-    __syncthreads();
-    int run = incl - sum;
-    for (int w = 0; w < wave; ++w) run += s_tot[w];
-    for (int i = b; i < e; ++i) { offsets[i] = run; run += counts[i]; }
-    if (threadIdx.x == 0) *count = s_tot[0] + s_tot[1] + s_tot[2] + s_tot[3];
+    // nb < 2^21 + 1, so the run arithmetic stays far inside 32 bits; the total is <= P < 2^31
+    const int total = mvs_block_scan_runs<SCAN_THREADS>(nb, [&](int i) { return counts[i]; }, [&](int i, int pre) { offsets[i] = pre; }, s_tot);
+    if (threadIdx.x == 0) *count = total;
 }
 
 template <bool RANGE>
@@ -166,10 +151,7 @@ __device__ __forceinline__ void live_write_tile(const unsigned long long* __rest
         const int w = r * (LS_THREADS / 64) + wave;
         const unsigned long long m = s_mask[w];
         if (!((m >> lane) & 1ull)) continue;
-        int pre = 0;
-        for (int k = 0; k < w; ++k) pre += s_pop[k];
-        const int rank = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-        const int64_t j = (int64_t)base + pre + rank;                   // < count <= P: inside every output
+        const int64_t j = (int64_t)base + mvs_tile_rank(s_pop, w, m);   // < count <= P: inside every output
         int64_t t = (int64_t)blockIdx.x * LS_TILE + r * LS_THREADS + threadIdx.x;             // < P: the count pass sets no bit past the end
         if (t >= P || j >= P) continue;
         unsigned ray = 0;

@@ -212,8 +212,6 @@ __global__ __launch_bounds__(256) void tsdf_vertex_colors_kernel(const float* __
     colors[r * 3 + 0] = out[0]; colors[r * 3 + 1] = out[1]; colors[r * 3 + 2] = out[2];
 }
 
-inline bool misaligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
-
 // D, H, W >= 2 and D H W <= 2^27
 inline bool tsdf_nodes(int D, int H, int W, int64_t* n)
 {
@@ -236,8 +234,8 @@ extern "C" int mvsnerf_tsdf_integrate_fwd(const float* depth, const unsigned cha
     if (M < 1 || M >= (1 << 22) || H_img < 1 || W_img < 1 || H_img > (1 << 24) || W_img > (1 << 24) || (view_ids && (n_views < 1 || n_views >= (1 << 22)))) return MVSNERF_EUNSUPPORTED;
     for (int k = 0; k < 6; ++k)
         if (!isfinite(box[k])) return MVSNERF_EUNSUPPORTED;
-    if (misaligned(depth, 4) || misaligned(images_rgba, 4) || misaligned(w2c, 4) || misaligned(K, 4) || misaligned(view_ids, 4) || misaligned(tsdf, 4) ||
-        misaligned(weight, 4) || misaligned(colors, 4))
+    if (mvs_misaligned(depth, 4) || mvs_misaligned(images_rgba, 4) || mvs_misaligned(w2c, 4) || mvs_misaligned(K, 4) || mvs_misaligned(view_ids, 4) || mvs_misaligned(tsdf, 4) ||
+        mvs_misaligned(weight, 4) || mvs_misaligned(colors, 4))
         return MVSNERF_EALIGN;
     const TsdfViews v{depth, valid, reinterpret_cast<const uchar4*>(images_rgba), w2c, K, view_ids, view_ids ? n_views : M, alpha ? 1 : 0, M, H_img, W_img};
     TsdfGrid g{D, H, W, (int)n, {box[0], box[1], box[2]}, {box[3] - box[0], box[4] - box[1], box[5] - box[2]}, trunc, z_min};
@@ -254,7 +252,7 @@ extern "C" int mvsnerf_tsdf_vertex_colors_fwd(const float* tsdf, const unsigned 
     if (!tsdf || !node_colors || !count || rows < 0 || (rows > 0 && (!vertex_edge || !colors))) return MVSNERF_EINVAL;
     int64_t n;
     if (!tsdf_nodes(D, H, W, &n) || rows >= ((int64_t)1 << 31)) return MVSNERF_EUNSUPPORTED;
-    if (misaligned(tsdf, 4) || misaligned(node_colors, 4) || misaligned(vertex_edge, 8) || misaligned(count, 8)) return MVSNERF_EALIGN;
+    if (mvs_misaligned(tsdf, 4) || mvs_misaligned(node_colors, 4) || mvs_misaligned(vertex_edge, 8) || mvs_misaligned(count, 8)) return MVSNERF_EALIGN;
     if (rows == 0) return MVSNERF_OK;
     tsdf_vertex_colors_kernel<<<mvs_cdiv(rows, 256), 256, 0, (hipStream_t)stream>>>(tsdf, reinterpret_cast<const uchar4*>(node_colors), D, H, W, vertex_edge,
                                                                                    count, rows, colors);

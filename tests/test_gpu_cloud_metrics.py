@@ -140,6 +140,30 @@ def test_results_do_not_depend_on_the_grid():
     _same(*(x.cpu().numpy() for x in grid.nearest(_t(q))), want_d, want_i, "capped")
 
 
+def test_cell_start_where_the_top_scan_owns_runs_of_two():
+    """128 x 128 x 129 = 2113536 cells: the cells + 1 counts make 1033 scan workgroups of 2048 entries, so the 1024 threads of the one-workgroup scan over
+    their sums (in place; csrc/scan_dev.h) own runs of c = 2 and threads 517..1023 own nothing.  Integers throughout: compared exactly."""
+    dims = (128, 128, 129)
+    cells = dims[0] * dims[1] * dims[2]
+    assert (cells + 1 + 2047) // 2048 == 1033
+    g = np.random.default_rng(129)
+    t = g.uniform(-0.02, 1.02, (5000, 3)).astype(F)                                  # some rows outside the box: they land in its border cells
+    t[::97, g.integers(0, 3)] = np.nan
+    t[5] = (np.inf, 0.5, 0.5)
+    lo, cell = np.zeros(3, dtype=F), F(1.0 / 128)
+    ref = R.grid_build(t, lo, cell, dims)
+    ids = torch.tensor([c for c, rows in ref.items() for _ in rows], dtype=torch.int64)
+    n_finite = int(np.isfinite(t).all(axis=1).sum())
+    assert len(ids) == n_finite and 4900 < n_finite < 5000 and int(ids.max()) > cells - dims[0] * dims[1]      # the last z-layer is used
+    counts = torch.bincount(ids, minlength=cells + 1)
+    want = (torch.cumsum(counts, 0) - counts).to(torch.int32)
+    cell_start, records = ops.grid_build(_t(t), lo.tolist(), float(cell), dims)
+    assert cell_start.dtype == torch.int32 and cell_start.shape == (cells + 1,)
+    assert torch.equal(cell_start.cpu(), want) and int(cell_start[-1]) == n_finite
+    idx = records[:n_finite, 3].cpu().numpy().copy().view(np.int32)
+    assert sorted(idx.tolist()) == np.nonzero(np.isfinite(t).all(axis=1))[0].tolist()
+
+
 @pytest.fixture(scope="module")
 def uniform():
     t, q, max_dist = CASES["uniform"]
@@ -255,6 +279,33 @@ def test_sample_mesh_is_the_float32_restatement():
     # a mesh extracted with a capacity: rows past its counts are not read
     got = geometry.sample_mesh(_mesh(v2, f2, count=_t(np.asarray([5, 3]), torch.int64)), 0.5)
     assert got.count.tolist() == [25, 4] and got.face.cpu().numpy().tolist() == want_f[:25].tolist()
+
+
+def test_sample_mesh_where_the_scan_owns_runs_of_two():
+    """1024 x 256 + 300 faces: 1026 workgroup sums, so the 1024 threads of the int64 scan (csrc/scan_dev.h) own runs of c = 2 and threads 513..1023 own
+    nothing.  The spacing is above every edge, so a face emits one point or none.  The float32 restatement runs once on 400 distinct faces (a face's point
+    depends on its own corners alone); the mesh draws its faces from those."""
+    g = np.random.default_rng(1026)
+    T = 1024 * 256 + 300
+    assert (T + 255) // 256 == 1026
+    v = g.integers(-8, 9, (300, 3)).astype(F)                                        # edges <= 16 sqrt(3) < 28
+    v[17] = (np.nan, 0, 0)
+    base = g.integers(0, 300, (400, 3)).astype(np.int32)
+    base[0] = (5, 5, 5); base[1] = (5, 6, 5)                                         # zero area: a point like any other
+    base[2] = (0, 1, 300); base[3] = (-1, 0, 1); base[4] = (17, 1, 2)                # outside the mesh, a NaN corner: nothing
+    base_p, base_f, base_n = R.sample32(v, base, 32.0)
+    assert set(base_n.tolist()) == {0, 1} and base_n[:5].tolist() == [1, 1, 0, 0, 0] and len(base_p) == int(base_n.sum())
+    row = np.cumsum(base_n) - base_n                                                 # the restatement's row of a base face that emits
+    pick = g.integers(0, 400, T)
+    pick[:256] = 2                                                                   # a workgroup that emits nothing
+    keep = base_n[pick] == 1
+    want_f = np.nonzero(keep)[0].astype(np.int32)
+    want_p = base_p[row[pick[keep]]]
+    got = geometry.sample_mesh(_mesh(v, base[pick]), 32.0)
+    assert got.count.tolist() == [len(want_f), 1] and 0.9 * T < len(want_f) < T - 256
+    assert torch.equal(got.face.cpu(), torch.from_numpy(want_f)) and got.points.cpu().numpy().tobytes() == want_p.tobytes()
+    cut = geometry.sample_mesh(_mesh(v, base[pick]), 32.0, capacity=1000)            # the scan's total does not depend on the capacity
+    assert cut.count.tolist() == got.count.tolist() and torch.equal(cut.face, got.face[:1000])
 
 
 def test_sample_mesh_capacity_and_refusal():

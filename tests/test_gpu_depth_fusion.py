@@ -333,6 +333,41 @@ def test_two_runs_give_the_same_bytes(big, big_cloud):
         assert x.dtype == y.dtype and x.shape == y.shape and torch.equal(x.view(torch.uint8), y.view(torch.uint8)), name
 
 
+@pytest.mark.parametrize("M,H,W", [(5, 231, 229), (4, 256, 256), (5, 109, 481)])
+def test_scan_runs_of_two(M, H, W):
+    """The one-workgroup scan of the compaction (256 threads over the counts of 1024-pixel workgroups; csrc/scan_dev.h) where a thread owns more than one
+    count.  5 x 231 x 229 = 264495 pixels: 259 counts, runs of c = 2, threads 130..255 own nothing.  4 x 256 x 256 = 256 x 1024 pixels: 256 counts, c = 1,
+    every run full.  5 x 109 x 481 = 256 x 1024 + 1 pixels: 257 counts, the step to c = 2, the last non-empty run (thread 128) holds one count.  The mask
+    is a seeded Bernoulli draw and fused / seen are arbitrary: ops.point_cloud takes them as they are.  Integer outputs are compared exactly; points as in
+    test_compaction (4 x the float32 restatement's distance from the float64 one on the same fused depths)."""
+    n = M * H * W
+    assert (n + 1023) // 1024 == {264495: 259, 262144: 256, 262145: 257}[n]
+    rs = np.random.RandomState(n % 1000)
+    c2w, K = R.rig_cameras(H, W, M)
+    c2w32, w2c32 = R.rounded_cameras(c2w)
+    K32 = K.astype(np.float32)
+    rgba = rs.randint(0, 256, (M, H, W, 4)).astype(np.uint8)
+    fused = rs.uniform(300.0, 1000.0, (M, H, W)).astype(np.float32)
+    seen = rs.randint(0, 1 << 31, (M, H, W)).astype(np.uint32)
+    mask = (rs.random_sample((M, H, W)) < 0.5).astype(np.uint8)
+    dev = lambda a: torch.from_numpy(a).to(DEV)
+    m8 = dev(mask)
+    want = torch.nonzero(m8.reshape(-1)).reshape(-1)
+    N = int(want.numel())
+    assert 0 < N < n
+    pts, col, nv, idx, count = ops.point_cloud(dev(rgba), dev(c2w32), dev(K32), dev(fused), dev(seen.view(np.int32)), m8, N + 3)
+    assert int(count.item()) == N
+    assert idx.dtype == torch.int64 and torch.equal(idx[:N], want)
+    p64 = R.Reference(fused, c2w32, w2c32, K32).compact(mask, fused, seen, rgba)
+    p32 = R.Reference(fused, c2w32, w2c32, K32, dtype=np.float32).compact(mask, fused, seen, rgba)
+    assert torch.equal(idx[:N].cpu(), torch.from_numpy(p64[3]))
+    assert torch.equal(col[:N].cpu(), torch.from_numpy(p64[1])) and torch.equal(nv[:N].cpu(), torch.from_numpy(p64[2]))
+    tol = 4.0 * float(np.abs(p32[0].astype(np.float64) - p64[0]).max())
+    err = float(np.abs(pts[:N].cpu().numpy().astype(np.float64) - p64[0]).max())
+    print(f"[{M} x {H} x {W}] points: GPU abs err {err:.2e}, tolerance 4 x {tol / 4:.2e}")
+    assert tol > 0 and err <= tol, (err, tol)
+
+
 class _AnalyticSystem:
     """render_rays of a system whose scene is the rig's: the analytic depth of the rays it is handed"""
 
