@@ -685,6 +685,51 @@ int mvsnerf_cloud_metrics_fwd(const float* dist, int64_t n, const float* taus, i
 size_t mvsnerf_mesh_sample_workspace_bytes(int64_t n_faces);
 int mvsnerf_mesh_sample_fwd(const float* vertices, int64_t n_vertices, const int* faces, int64_t n_faces, const int64_t* mesh_count, float spacing,
                             int64_t capacity, float* points, int* face, int64_t* count, void* workspace, void* stream);
+/* ---- a triangle mesh -> depth, face and colour maps in pinhole cameras (a z-buffer rasteriser), the views a face owns pixels in, and a mesh cut down to a
+ *      subset of its faces (csrc/raster.hip, DESIGN.md 4r, where the definition is written out too).  No counterpart in the reference. ----
+ * Conventions: tsdf_integrate's (w2c [M][3][4], K [M][3][3], pixel centres at integer coordinates, depth = camera-space z, fp32, every operation rounded on
+ *   its own, IEEE division).  Sub-pixel grid SUB = 256.  mesh_count: NULL, or the device {vertices, faces} counts of a mesh extracted with a capacity: rows
+ *   past min(count, rows) are never read (mesh_sample's convention).  view_ids [n_views] (device int32; NULL: the views 0..M-1): output slot a shows view
+ *   view_ids[a]; an id outside [0, M) is skipped (tsdf_integrate's rule) and its slot is empty.
+ * mesh_raster, per view m and vertex i:  q = ((w0 X + w1 Y) + w2 Z) + w3 per row of w2c_m;  u = K0 q.x / q.z + K2, v = K4 q.y / q.z + K5;
+ *   X = floor(u 256 + 0.5), Y = floor(v 256 + 0.5) as integers;  iz = 1 / q.z.  The vertex is usable iff q.z > z_min, u and v are finite and
+ *   |X|, |Y| <= 2^23 (every edge product then fits int64).
+ *   Per face f = (a, b, c): dropped whole (no clipping) if a vertex number lies outside [0, n_vertices), a vertex is unusable, A == 0 with
+ *   A = (x1-x0)(y2-y0) - (y1-y0)(x2-x0) in int64, or it is culled: cull = 0 keeps both signs, +1 drops A > 0, -1 drops A < 0 (the front faces of the
+ *   library's own meshes seen from outside have A < 0: cull = +1 is back-face culling for them).  If A < 0, b and c are swapped so that A > 0.  Edge functions
+ *   e_i(px,py) = (xb-xa)(py-ya) - (yb-ya)(px-xa) in int64 at px = 256 x, py = 256 y: e0 on (b,c), e1 on (c,a), e2 on (a,b).  Pixel (x,y) of the snapped
+ *   bounding box clipped to the image is covered iff for each edge e > 0, or e == 0 and the edge is top-left (dy < 0, or dy == 0 and dx > 0): shared edges
+ *   are watertight and no pixel is hit twice.  A covered pixel:  b1 = (float)e1 / (float)A, b2 = (float)e2 / (float)A, b0 = (1 - b1) - b2;  t_k = b_k iz_k;
+ *   invz = (t0 + t1) + t2;  z = 1 / invz; the fragment counts iff z is finite and z > z_min.
+ *   Depth test: the smallest z wins, the lowest face number among equal z bits; nothing depends on arrival order (one 64-bit word per pixel,
+ *   float_bits(z) << 32 | face, an unsigned atomic min), so two runs give the same bytes.
+ *   Outputs per slot: depth [.][H][W] fp32 (0 where nothing was hit: the bank's hole), face [.][H][W] int32 (-1 for nothing), and, iff colors [n_vertices][3]
+ *   uint8 is given, out_colors [.][H][W][3] uint8: byte = clamp(floor(((t0 c_a + t1 c_b) + t2 c_c) z + 0.5), 0, 255) per channel (perspective-correct); a
+ *   hole takes background = R | G << 8 | B << 16.
+ *   workspace: mesh_raster_workspace_bytes(n_faces, n_views, H, W) bytes (n_views: the number of output slots), 8-byte aligned; 0 for shapes the entry refuses.
+ * mesh_face_views: face [n_maps][H][W] int32 (mesh_raster's face maps; map a shows view view_ids[a], or view a with view_ids NULL, then n_maps == M) ->
+ *   seen [n_faces][ceil(M / 32)] int32 with bit m & 31 of word m >> 5 set iff face f owns a pixel of view m, and n [n_faces] int32 = the number of such views.
+ *   Entries outside [0, min(count, n_faces)) are ignored.  Integer atomic OR: order-free.
+ * mesh_filter: the faces with keep [n_faces] != 0 (uint8) below the mesh's count whose vertex numbers lie inside the mesh, in order, and the vertices they
+ *   use, in order, renumbered.  vertices / ndc / vertex_edge / colors rows are carried over (ndc, vertex_edge, colors and their outputs may be NULL);
+ *   vertex_index / face_index (int64) hold the original numbers.  count (device, int64 [2]) always receives the true numbers of vertices and faces; rows
+ *   >= cap_vertices / cap_faces are not written and both capacities 0 runs the count alone (mesh_extract's convention).  mark -> count -> scan -> write, no
+ *   atomics, stable.  workspace: mesh_filter_workspace_bytes(n_vertices, n_faces) bytes, 4-byte aligned.
+ * MVSNERF_EINVAL: a NULL pointer that is needed, colors without out_colors or the reverse, a negative count or capacity, M, H, W or n_maps < 1, n_views < 1
+ *   with view_ids, n_maps != M without, a cull outside {-1, 0, 1}; MVSNERF_EUNSUPPORTED: a count or capacity >= 2^31, more than 65535 output slots, M >= 2^22,
+ *   an image larger than 2^15 in a dimension, more than 2^22 workgroups of 256 (face, view) items, z_min not finite or < 0; MVSNERF_EALIGN: a float / int32
+ *   array not 4-byte, an int64 array or the raster workspace not 8-byte aligned.  All before the first launch. */
+size_t mvsnerf_mesh_raster_workspace_bytes(int64_t n_faces, int n_views, int H, int W);
+int mvsnerf_mesh_raster_fwd(const float* vertices, int64_t n_vertices, const int* faces, int64_t n_faces, const unsigned char* colors,
+                            const int64_t* mesh_count, const float* w2c, const float* K, const int* view_ids, int n_views, int M, int H, int W, int cull,
+                            float z_min, unsigned background, float* depth, int* face, unsigned char* out_colors, void* workspace, void* stream);
+int mvsnerf_mesh_face_views_fwd(const int* face, int n_maps, int H, int W, const int* view_ids, int M, int64_t n_faces, const int64_t* mesh_count, int* seen,
+                                int* n, void* stream);
+size_t mvsnerf_mesh_filter_workspace_bytes(int64_t n_vertices, int64_t n_faces);
+int mvsnerf_mesh_filter_fwd(const float* vertices, const float* ndc, const int64_t* vertex_edge, const unsigned char* colors, int64_t n_vertices,
+                            const int* faces, int64_t n_faces, const int64_t* mesh_count, const unsigned char* keep, int64_t cap_vertices, int64_t cap_faces,
+                            float* out_vertices, float* out_ndc, int64_t* out_vertex_edge, unsigned char* out_colors, int64_t* vertex_index, int* out_faces,
+                            int64_t* face_index, int64_t* count, void* workspace, void* stream);
 
 #ifdef __cplusplus
 }

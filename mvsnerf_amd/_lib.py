@@ -316,6 +316,11 @@ SIGNATURES = {
     "mvsnerf_cloud_metrics_fwd": (_c_i, [_c_fp, _c_l, ctypes.POINTER(ctypes.c_float), _c_i, _c_fp, _c_fp, _c_fp]),
     "mvsnerf_mesh_sample_workspace_bytes": (ctypes.c_size_t, [_c_l]),
     "mvsnerf_mesh_sample_fwd": (_c_i, [_c_fp, _c_l, _c_fp, _c_l, _c_fp, ctypes.c_float, _c_l] + [_c_fp] * 5),
+    "mvsnerf_mesh_raster_workspace_bytes": (ctypes.c_size_t, [_c_l, _c_i, _c_i, _c_i]),
+    "mvsnerf_mesh_raster_fwd": (_c_i, [_c_fp, _c_l, _c_fp, _c_l] + [_c_fp] * 5 + [_c_i] * 5 + [ctypes.c_float, ctypes.c_uint] + [_c_fp] * 5),
+    "mvsnerf_mesh_face_views_fwd": (_c_i, [_c_fp, _c_i, _c_i, _c_i, _c_fp, _c_i, _c_l] + [_c_fp] * 4),
+    "mvsnerf_mesh_filter_workspace_bytes": (ctypes.c_size_t, [_c_l, _c_l]),
+    "mvsnerf_mesh_filter_fwd": (_c_i, [_c_fp] * 4 + [_c_l, _c_fp, _c_l, _c_fp, _c_fp, _c_l, _c_l] + [_c_fp] * 10),
 }
 
 _lib = None

@@ -14,6 +14,10 @@ Geometry from depth, as a surface: `fuse_tsdf` integrates the depth maps into a 
 
 Geometry, measured: `PointGrid` answers exact nearest-neighbour queries within a radius between clouds of millions of points and `sample_mesh` puts points on a
 mesh (csrc/cloud_metrics.hip); `evaluate.cloud_metrics` builds DTU's accuracy / completeness and the Tanks-and-Temples F-score on them.
+
+Geometry, looked at: `render_mesh` rasterises a mesh into the scene's cameras (depth, face and colour maps; csrc/raster.hip), `face_views` counts
+the views a face is seen in, `filter_mesh` cuts a mesh down to a subset of its faces, `cull_unseen` composes the three and `mesh_frames` makes the
+`rgb | depth` turntable.  Not pinned against any external rasteriser.
 """
 import math
 
@@ -518,6 +522,230 @@ def sample_mesh(mesh, spacing, capacity=None):
         points, face, count = ops.mesh_sample(mesh.vertices.contiguous(), mesh.faces.contiguous(), spacing, None if capacity is None else int(capacity),
                                               mesh_count=getattr(mesh, "count", None))
     return MeshSamples(points, face, count)
+
+
+# ---- a mesh back in the scene's cameras: the z-buffer rasteriser, the views a face is seen in, a mesh cut down to a subset of its faces (csrc/raster.hip,
+#      DESIGN.md 4r).  Not pinned against any external rasteriser.
+RASTER_MAX_FACES = (1 << 31) - 1
+
+
+class MeshImage:
+    """What render_mesh returns: depth (M,H,W) fp32 camera-space z, 0 where nothing was hit (the bank's hole); face (M,H,W) int32, -1 for nothing;
+    colors (M,H,W,3) uint8 or None (a mesh without vertex colours); views: the view ids shown, in order (None: every view of the bank); mask = face >= 0."""
+
+    def __init__(self, depth, face, colors, views=None):
+        self.depth, self.face, self.colors, self.views = depth, face, colors, views
+
+    @property
+    def mask(self):
+        return self.face >= 0
+
+
+def _raster_mesh(mesh, who):
+    """The refusals of a mesh handed to the rasteriser or the filter, before the library is touched."""
+    if not (hasattr(mesh, "vertices") and hasattr(mesh, "faces")):
+        raise TypeError(f"{who}: a TriangleMesh (vertices, faces) expected, got {type(mesh).__name__}")
+    v, f = mesh.vertices, mesh.faces
+    if not torch.is_tensor(v) or v.dtype != torch.float32:
+        raise TypeError(f"{who}: mesh.vertices must be a float32 tensor of shape (V,3), got {getattr(v, 'dtype', type(v).__name__)}")
+    if v.dim() != 2 or v.shape[1] != 3:
+        raise ValueError(f"{who}: mesh.vertices must be (V,3), got {tuple(v.shape)}")
+    if not torch.is_tensor(f) or f.dtype != torch.int32:
+        raise TypeError(f"{who}: mesh.faces must be an int32 tensor of shape (T,3), got {getattr(f, 'dtype', type(f).__name__)}")
+    if f.dim() != 2 or f.shape[1] != 3:
+        raise ValueError(f"{who}: mesh.faces must be (T,3), got {tuple(f.shape)}")
+    if f.shape[0] > RASTER_MAX_FACES or v.shape[0] > RASTER_MAX_FACES:
+        raise ValueError(f"{who}: at most 2^31 - 1 vertices and faces (a face number is an int32), got {v.shape[0]} and {f.shape[0]}")
+    if f.device != v.device:
+        raise ValueError(f"{who}: mesh.faces must be on the vertices' device {v.device}, got {f.device}")
+    c = getattr(mesh, "colors", None)
+    if c is not None:
+        if not torch.is_tensor(c) or c.dtype != torch.uint8:
+            raise TypeError(f"{who}: mesh.colors must be None or a uint8 tensor of shape ({v.shape[0]},3), got {getattr(c, 'dtype', type(c).__name__)}")
+        if tuple(c.shape) != (v.shape[0], 3):
+            raise ValueError(f"{who}: mesh.colors must be ({v.shape[0]},3), a row per vertex, got {tuple(c.shape)}")
+        if c.device != v.device:
+            raise ValueError(f"{who}: mesh.colors must be on the vertices' device {v.device}, got {c.device}")
+    n = getattr(mesh, "count", None)
+    if n is not None and not (torch.is_tensor(n) and n.dtype == torch.int64 and tuple(n.shape) == (2,) and n.device == v.device):
+        raise ValueError(f"{who}: mesh.count must be None or a (2,) int64 tensor on the vertices' device {v.device}")
+    return v.device
+
+
+def _raster_cameras(scene, cameras, dev, who):
+    """(w2c (M,3,4) float64 -> fp32 rounded once, K (M,3,3) fp32, (H, W)) on the host, from a SceneRays or cameras=(c2ws, intrinsics, (H, W))."""
+    if cameras is not None:
+        if scene is not None:
+            raise ValueError(f"{who}: scene (a SceneRays) and cameras=(c2ws, intrinsics, (H, W)) exclude each other")
+        try:
+            c2ws, K, hw = cameras
+            H, W = (int(v) for v in hw)
+        except (TypeError, ValueError):
+            raise ValueError(f"{who}: cameras must be (c2ws (M,4,4), intrinsics (M,3,3) | (3,3), (H, W)), got {type(cameras).__name__}") from None
+        c2w = torch.as_tensor(c2ws).detach().to("cpu", torch.float64)
+        if c2w.dim() != 3 or c2w.shape[0] < 1 or tuple(c2w.shape[1:]) not in ((4, 4), (3, 4)):
+            raise ValueError(f"{who}: cameras[0] must be (M,4,4) or (M,3,4) poses, got {tuple(c2w.shape)}")
+        M = int(c2w.shape[0])
+        if c2w.shape[1] == 3:
+            c2w = torch.cat((c2w, torch.tensor([0.0, 0.0, 0.0, 1.0], dtype=torch.float64).expand(M, 1, 4)), 1)
+        K64 = torch.as_tensor(K).detach().to("cpu", torch.float64)
+        if tuple(K64.shape) == (3, 3):
+            K64 = K64.expand(M, 3, 3)
+        if tuple(K64.shape) != (M, 3, 3):
+            raise ValueError(f"{who}: cameras[1] must be ({M},3,3) or (3,3) intrinsics, got {tuple(K64.shape)}")
+    else:
+        if not (hasattr(scene, "_c2w64") and hasattr(scene, "_K64") and hasattr(scene, "hw")):
+            raise TypeError(f"{who}: a SceneRays expected (or cameras=(c2ws, intrinsics, (H, W))), got {type(scene).__name__}")
+        bank = scene.images.device if hasattr(scene, "images") else torch.device(scene.device)     # (SceneRays.device may lack the index)
+        if bank != dev:
+            raise ValueError(f"{who}: the mesh must be on the bank's device {bank}, got {dev}")
+        c2w, K64, (H, W) = scene._c2w64, scene._K64, scene.hw
+    if not (1 <= H <= ops.RASTER_MAX_IMAGE and 1 <= W <= ops.RASTER_MAX_IMAGE):
+        raise ValueError(f"{who}: views of 1 x 1 to {ops.RASTER_MAX_IMAGE} x {ops.RASTER_MAX_IMAGE} pixels, got {H} x {W}")
+    w2c = np.linalg.inv(c2w.numpy())[:, :3, :4]                                          # float64 on the host, rounded once
+    return (torch.from_numpy(np.ascontiguousarray(w2c, dtype=np.float32)), K64.to(torch.float32).contiguous(), (int(H), int(W)))
+
+
+def _render_args(views, M, cull, z_min, background, who):
+    ids = None
+    if views is not None:
+        ids = views.cpu().numpy() if torch.is_tensor(views) else np.asarray(views)
+        if ids.ndim != 1 or ids.size < 1 or not np.issubdtype(ids.dtype, np.integer):
+            raise ValueError(f"{who}: views must be a 1-D list of at least one integer view id, got shape {ids.shape} {ids.dtype}")
+        if ids.min() < 0 or ids.max() >= M:
+            raise ValueError(f"{who}: views must hold view ids in [0, {M}), got {ids.tolist()}")
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+    if (ids.size if ids is not None else M) > ops.RASTER_MAX_VIEWS:
+        raise ValueError(f"{who}: at most {ops.RASTER_MAX_VIEWS} views a call, got {ids.size if ids is not None else M}")
+    if isinstance(cull, bool) or cull not in (-1, 0, 1):
+        raise ValueError(f"{who}: cull must be 0 (both windings), +1 (drop A > 0: back faces of the library's own meshes) or -1, got {cull!r}")
+    try:
+        z_min = float(z_min)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: z_min must be finite and >= 0, got {z_min!r}") from None
+    if not (math.isfinite(z_min) and z_min >= 0):
+        raise ValueError(f"{who}: z_min must be finite and >= 0, got {z_min}")
+    try:
+        bg = tuple(int(b) for b in background)
+        ok = len(bg) == 3 and all(int(b) == b for b in background) and min(bg) >= 0 and max(bg) <= 255
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"{who}: background must be three bytes (R, G, B) in 0..255, got {background!r}")
+    return ids, int(cull), z_min, bg
+
+
+@torch.no_grad()
+def render_mesh(mesh, scene=None, views=None, cull=0, z_min=0.0, background=(255, 255, 255), cameras=None):
+    """A TriangleMesh rasterised into the scene's pinhole cameras -> a MeshImage (csrc/raster.hip, DESIGN.md 4r, where the definition is written out).
+        scene       a SceneRays: its cameras and image size.  For novel poses cameras=(c2ws (M,4,4), intrinsics (M,3,3) | (3,3), (H, W)) replaces it.
+        views       a list of view ids, shown in the list's order; default every view
+        cull        0 keeps both windings; +1 drops faces whose snapped screen area A is > 0, -1 those with A < 0.  The front faces of the library's own
+                    meshes (extract_mesh, tsdf_mesh) seen from outside have A < 0, so cull=+1 is back-face culling for them.
+        z_min       a vertex or a fragment nearer than this (camera-space z) is not drawn; a face with such a vertex is dropped whole (no clipping)
+        background  the bytes of a pixel nothing covers in `colors`
+    Vertices are snapped to 1/256 pixel and coverage follows the top-left fill rule in integers: shared edges are watertight and no pixel is hit twice.
+    The nearest fragment wins, the lowest face number among equal depths, whatever the order of arrival: the same bytes every run.  Of a mesh extracted with
+    a capacity only the first min(mesh.count, rows) vertices and faces are read.  Not pinned against any external rasteriser."""
+    who = "render_mesh"
+    dev = _raster_mesh(mesh, who)
+    w2c, K, hw = _raster_cameras(scene, cameras, dev, who)
+    ids, cull, z_min, bg = _render_args(views, int(w2c.shape[0]), cull, z_min, background, who)
+    with torch.cuda.device(dev):
+        depth, face, colors = ops.mesh_raster(mesh.vertices.contiguous(), mesh.faces.contiguous(), w2c.to(dev), K.to(dev), hw,
+                                              colors=None if mesh.colors is None else mesh.colors.contiguous(),
+                                              views=None if ids is None else torch.from_numpy(ids).to(dev), cull=cull, z_min=z_min, background=bg,
+                                              mesh_count=getattr(mesh, "count", None))
+    return MeshImage(depth, face, colors, None if ids is None else ids.tolist())
+
+
+@torch.no_grad()
+def face_views(face, n_faces):
+    """face (M,H,W) int32 on the GPU (MeshImage.face) -> (n_faces,) int32: the number of views in which a face owns at least one pixel."""
+    who = "face_views"
+    if not torch.is_tensor(face) or face.dtype != torch.int32:
+        raise TypeError(f"{who}: face must be an int32 tensor of shape (M,H,W), got {getattr(face, 'dtype', type(face).__name__)}")
+    if face.dim() != 3 or face.numel() < 1:
+        raise ValueError(f"{who}: face must be a non-empty (M,H,W), got {tuple(face.shape)}")
+    if face.shape[0] > ops.RASTER_MAX_VIEWS:
+        raise ValueError(f"{who}: at most {ops.RASTER_MAX_VIEWS} views a call, got {face.shape[0]}")
+    if isinstance(n_faces, bool) or int(n_faces) != n_faces or not 0 <= int(n_faces) <= RASTER_MAX_FACES:
+        raise ValueError(f"{who}: n_faces must be an integer in [0, 2^31), got {n_faces!r}")
+    with torch.cuda.device(face.device):
+        return ops.mesh_face_views(face.contiguous(), int(n_faces))[0]
+
+
+@torch.no_grad()
+def filter_mesh(mesh, keep):
+    """The TriangleMesh of the faces with keep != 0, in order, and the vertices they use, in order.
+        keep        (T,) bool | uint8 on the mesh's device
+    vertices / ndc / vertex_edge / colors are carried over; sub.vertex_index (V',) and sub.face_index (T',) int64 hold the original numbers.  A kept face
+    with a vertex number outside the mesh is dropped.  The two totals are read from the device once; sub.count holds them.  Stable: the same bytes every run."""
+    who = "filter_mesh"
+    dev = _raster_mesh(mesh, who)
+    T = int(mesh.faces.shape[0])
+    if not torch.is_tensor(keep) or keep.dtype not in (torch.bool, torch.uint8):
+        raise TypeError(f"{who}: keep must be a bool or uint8 tensor of shape ({T},), got {getattr(keep, 'dtype', type(keep).__name__)}")
+    if tuple(keep.shape) != (T,):
+        raise ValueError(f"{who}: keep must be ({T},), a flag per face, got {tuple(keep.shape)}")
+    if keep.device != dev:
+        raise ValueError(f"{who}: keep must be on the mesh's device {dev}, got {keep.device}")
+    V = int(mesh.vertices.shape[0])
+    ndc, edge = getattr(mesh, "ndc", None), getattr(mesh, "vertex_edge", None)
+    for name, t, dtype, shape in (("ndc", ndc, torch.float32, (V, 3)), ("vertex_edge", edge, torch.int64, (V,))):
+        if t is not None and not (torch.is_tensor(t) and t.dtype == dtype and tuple(t.shape) == shape and t.device == dev):
+            raise ValueError(f"{who}: mesh.{name} must be None or a {shape} {dtype} tensor on {dev}")
+    with torch.cuda.device(dev):
+        v, n, e, c, vi, f, fi, count = ops.mesh_filter(mesh.vertices.contiguous(), mesh.faces.contiguous(), _u8(keep),
+                                                       ndc=None if ndc is None else ndc.contiguous(), vertex_edge=None if edge is None else edge.contiguous(),
+                                                       colors=None if mesh.colors is None else mesh.colors.contiguous(), mesh_count=getattr(mesh, "count", None))
+    sub = TriangleMesh(v, n, f, e, count, c)
+    sub.vertex_index, sub.face_index = vi, fi
+    return sub
+
+
+@torch.no_grad()
+def cull_unseen(mesh, scene=None, min_views=1, **render_kw):
+    """`mesh` without the faces that fewer than min_views cameras see: render_mesh(mesh, scene, **render_kw) -> face_views -> filter_mesh.  A face is seen by
+    a view when it owns at least one pixel of that view's face map.  Removes the inner shells and back sides of a density mesh, which no scan could contain."""
+    if isinstance(min_views, bool) or int(min_views) != min_views or int(min_views) < 0:
+        raise ValueError(f"cull_unseen: min_views must be an integer >= 0, got {min_views!r}")
+    img = render_mesh(mesh, scene, **render_kw)
+    with torch.cuda.device(img.face.device):
+        n = ops.mesh_face_views(img.face, int(mesh.faces.shape[0]), mesh_count=getattr(mesh, "count", None))[0]
+        return filter_mesh(mesh, n >= int(min_views))
+
+
+@torch.no_grad()
+def mesh_frames(mesh, poses, hw, focal, crop=False, **render_kw):
+    """uint8 (K, H', 2 W', 3) `rgb | depth` frames of the mesh seen from poses (K,4,4) | (K,3,4), the turntable render_path makes for a radiance field:
+    the cameras of train.get_ray_directions (fx, fy = focal, centre (W / 2, H / 2)) -> render_mesh -> ops.frame_u8 per pose, with ONE depth range over the
+    whole path (ops.depth_range of the K depth maps; holes are 0 and do not count towards the minimum), so utils.save_frames works on the result.
+    A mesh without colours is drawn grey (128).  crop: True removes H // 20 rows and W // 20 columns from every side of each panel, or a pair."""
+    H, W = int(hw[0]), int(hw[1])
+    f = [float(v) for v in np.asarray(focal, dtype=np.float64).reshape(-1)]
+    fx, fy = (f[0], f[0]) if len(f) == 1 else (f[0], f[1])
+    K = torch.tensor([[fx, 0.0, W / 2], [0.0, fy, H / 2], [0.0, 0.0, 1.0]], dtype=torch.float64)
+    if getattr(mesh, "colors", None) is None and hasattr(mesh, "vertices"):
+        grey = TriangleMesh(mesh.vertices, getattr(mesh, "ndc", None), mesh.faces, getattr(mesh, "vertex_edge", None), getattr(mesh, "count", None),
+                            torch.full((int(mesh.vertices.shape[0]), 3), 128, dtype=torch.uint8, device=mesh.vertices.device))
+        mesh = grey
+    crop = (H // 20, W // 20) if crop is True else ((0, 0) if not crop else (int(crop[0]), int(crop[1])))
+    if crop[0] < 0 or crop[1] < 0 or 2 * crop[0] >= H or 2 * crop[1] >= W:
+        raise ValueError(f"mesh_frames: crop {crop} leaves nothing of a {H} x {W} frame")
+    img = render_mesh(mesh, None, cameras=(poses, K, (H, W)), **render_kw)
+    n = int(img.depth.shape[0])
+    with torch.cuda.device(img.depth.device):
+        frames = torch.empty((n, H - 2 * crop[0], (W - 2 * crop[1]) * 2, 3), device=img.depth.device, dtype=torch.uint8)
+        mm = ops.depth_range(img.depth)
+        for k in range(n):
+            ops.frame_u8(mesh_rgb(img.colors[k]), img.depth[k], minmax=mm, crop=crop, out=frames[k])
+    return frames
+
+
+def mesh_rgb(colors):
+    """uint8 colours as the fp32 rgb ops.frame_u8 takes: (c + 0.5) / 255, which frame_u8's trunc(clamp(rgb, 0, 1) * 255) maps back to c for every byte."""
+    return (colors.to(torch.float32) + 0.5) / 255.0
 
 
 def _mesh_ply(path, mesh):

@@ -2388,3 +2388,131 @@ def mesh_sample(vertices, faces, spacing, capacity=None, mesh_count=None):
             raise RuntimeError(f"{op}: unsupported shape: {total} points (fewer than 2^31); sample with a larger spacing")
         capacity = total
     return (*run(int(capacity)), count)
+
+
+# ------------------------------------------------------------------ a mesh in the scene's cameras: rasteriser, face visibility, mesh filter (csrc/raster.hip)
+RASTER_MAX_VIEWS = 65535
+RASTER_MAX_IMAGE = 1 << 15
+
+
+def _mesh_rows(vertices, faces, mesh_count, op):
+    """(V, vertices pointer, T, faces pointer, mesh_count pointer) of a mesh on the current GPU."""
+    V, p_v = _cloud_rows(vertices, "vertices", op)
+    dev = vertices.device
+    if not (torch.is_tensor(faces) and faces.dim() == 2 and faces.shape[1] == 3):
+        raise RuntimeError(f"{op}: faces must be a (T,3) tensor, got {tuple(getattr(faces, 'shape', ()))}")
+    T = int(faces.shape[0])
+    p_f = _fusion_map(faces, torch.int32, (T, 3), dev, "faces", op) if T else 0
+    p_mc = 0 if mesh_count is None else _fusion_map(mesh_count, torch.int64, (2,), dev, "mesh_count", op)
+    return V, p_v, T, p_f, p_mc
+
+
+def _view_list(views, dev, op):
+    if views is None:
+        return 0, 0
+    if not (torch.is_tensor(views) and views.dim() == 1 and views.numel() >= 1):
+        raise RuntimeError(f"{op}: views must be a 1-D tensor of at least one view id")
+    n = int(views.numel())
+    return _fusion_map(views, torch.int32, (n,), dev, "views", op), n
+
+
+def mesh_raster(vertices, faces, w2cs, intrinsics, hw, colors=None, views=None, cull=0, z_min=0.0, background=(255, 255, 255), mesh_count=None):
+    """The z-buffer rasteriser (mvsnerf_mesh_raster_fwd; the definition is in DESIGN.md 4r and include/mvsnerf_hip_internal.h): vertices (V,3) fp32, faces
+    (T,3) int32, colors (V,3) uint8 | None, w2cs (M,3,4) and intrinsics (M,3,3) fp32, hw = (H, W), views a 1-D int32 device tensor of view ids (output slot a
+    shows view views[a]) | None for every view -> (depth (n,H,W) fp32, 0 = nothing hit; face (n,H,W) int32, -1 = nothing; colors (n,H,W,3) uint8 | None).
+    cull: 0 both windings, +1 drops A > 0, -1 drops A < 0.  mesh_count: the (2,) int64 device counts of a mesh extracted with a capacity.  Order-free atomic
+    min on 64-bit words: two runs give the same bytes.  Nothing is read from the device."""
+    op = "mesh_raster"
+    _need_no_grad(vertices, w2cs, intrinsics, op=op)
+    V, p_v, T, p_f, p_mc = _mesh_rows(vertices, faces, mesh_count, op)
+    dev = vertices.device
+    if not (torch.is_tensor(w2cs) and w2cs.dim() == 3 and tuple(w2cs.shape[1:]) == (3, 4) and w2cs.shape[0] >= 1):
+        raise RuntimeError(f"{op}: w2cs must be (M,3,4), got {tuple(getattr(w2cs, 'shape', ()))}")
+    M = int(w2cs.shape[0])
+    p_w2c = _fusion_map(w2cs, torch.float32, (M, 3, 4), dev, "w2cs", op)
+    p_K = _fusion_map(intrinsics, torch.float32, (M, 3, 3), dev, "intrinsics", op)
+    p_col = 0 if colors is None else (_fusion_map(colors, torch.uint8, (V, 3), dev, "colors", op) if V else 0)
+    p_views, n_views = _view_list(views, dev, op)
+    n = n_views if views is not None else M
+    H, W = int(hw[0]), int(hw[1])
+    bg = [int(b) for b in background]
+    if len(bg) != 3 or min(bg) < 0 or max(bg) > 255:
+        raise RuntimeError(f"{op}: background must be three bytes, got {background!r}")
+    lib = _lib.lib()
+    ws_bytes = int(lib.mvsnerf_mesh_raster_workspace_bytes(T, n, H, W))
+    if ws_bytes == 0:
+        raise RuntimeError(f"{op}: unsupported shape: {T} faces in {n} views of {H} x {W} (at least 1 x 1 and at most {RASTER_MAX_IMAGE} a side, at most "
+                           f"{RASTER_MAX_VIEWS} views, at most 2^22 workgroups of 256 (face, view) pairs)")
+    ws = torch.empty((ws_bytes // 8,), device=dev, dtype=torch.int64)
+    depth = torch.empty((n, H, W), device=dev, dtype=torch.float32)
+    face = torch.empty((n, H, W), device=dev, dtype=torch.int32)
+    has_colors = colors is not None and V > 0
+    out_colors = torch.empty((n, H, W, 3), device=dev, dtype=torch.uint8) if has_colors else None
+    check(lib.mvsnerf_mesh_raster_fwd(p_v, V, p_f, T, p_col, p_mc, p_w2c, p_K, p_views, n_views, M, H, W, int(cull), float(z_min),
+                                      bg[0] | bg[1] << 8 | bg[2] << 16, depth.data_ptr(), face.data_ptr(), out_colors.data_ptr() if has_colors else 0,
+                                      ws.data_ptr(), stream_ptr()), "mesh_raster_fwd")
+    if colors is not None and not has_colors:                               # a mesh without a vertex: every pixel is background
+        out_colors = torch.tensor(bg, dtype=torch.uint8).to(dev).expand(n, H, W, 3).contiguous()
+    return depth, face, out_colors
+
+
+def mesh_face_views(face, n_faces, views=None, n_bank=None, mesh_count=None):
+    """face (n,H,W) int32 face maps (mesh_raster's) -> (n_views (T,) int32: the views in which a face owns at least one pixel, seen (T, ceil(M / 32)) int32:
+    bit m & 31 of word m >> 5 says so for view m).  views: the 1-D int32 device tensor mesh_raster was given (map a shows view views[a]) with n_bank = M, or
+    None: map a is view a.  Entries outside [0, min(mesh_count[1], T)) are ignored.  Integer atomic OR: order-free (mvsnerf_mesh_face_views_fwd)."""
+    op = "mesh_face_views"
+    if not (torch.is_tensor(face) and face.is_cuda and face.dim() == 3 and face.numel() > 0):
+        raise RuntimeError(f"{op}: face must be a non-empty (n,H,W) tensor on the GPU")
+    n, H, W = (int(v) for v in face.shape)
+    dev = face.device
+    if dev.index != torch.cuda.current_device():
+        raise RuntimeError(f"{op}: face is on {dev} but the current device is cuda:{torch.cuda.current_device()}")
+    p_face = _fusion_map(face, torch.int32, (n, H, W), dev, "face", op)
+    p_views, n_views = _view_list(views, dev, op)
+    if views is not None and n_views != n:
+        raise RuntimeError(f"{op}: {n} face maps but {n_views} view ids")
+    M = n if views is None else int(n_bank)
+    T = int(n_faces)
+    p_mc = 0 if mesh_count is None else _fusion_map(mesh_count, torch.int64, (2,), dev, "mesh_count", op)
+    words = (M + 31) // 32
+    seen = torch.empty((T, words), device=dev, dtype=torch.int32)
+    count = torch.empty((T,), device=dev, dtype=torch.int32)
+    check(_lib.lib().mvsnerf_mesh_face_views_fwd(p_face, n, H, W, p_views, M, T, p_mc, seen.data_ptr() if T else 0, count.data_ptr() if T else 0,
+                                                 stream_ptr()), "mesh_face_views_fwd")
+    return count, seen
+
+
+def mesh_filter(vertices, faces, keep, ndc=None, vertex_edge=None, colors=None, mesh_count=None):
+    """The faces with keep (T,) uint8 != 0, in order, and the vertices they use, in order, renumbered (mvsnerf_mesh_filter_fwd) ->
+    (vertices, ndc | None, vertex_edge | None, colors | None, vertex_index (V',) int64, faces (T',3) int32, face_index (T',) int64, count (2,) int64 on the
+    device).  The two totals are read from the device once.  mark -> count -> scan -> write, no atomics: stable, the same bytes every run."""
+    op = "mesh_filter"
+    _need_no_grad(vertices, op=op)
+    V, p_v, T, p_f, p_mc = _mesh_rows(vertices, faces, mesh_count, op)
+    dev = vertices.device
+    p_keep = _fusion_map(keep, torch.uint8, (T,), dev, "keep", op) if T else 0
+    p_ndc = 0 if ndc is None or not V else _fusion_map(ndc, torch.float32, (V, 3), dev, "ndc", op)
+    p_edge = 0 if vertex_edge is None or not V else _fusion_map(vertex_edge, torch.int64, (V,), dev, "vertex_edge", op)
+    p_col = 0 if colors is None or not V else _fusion_map(colors, torch.uint8, (V, 3), dev, "colors", op)
+    lib = _lib.lib()
+    ws_bytes = int(lib.mvsnerf_mesh_filter_workspace_bytes(V, T))
+    if ws_bytes == 0:
+        raise RuntimeError(f"{op}: {V} vertices and {T} faces are outside what the kernels index (fewer than 2^31)")
+    ws = torch.empty(((ws_bytes + 3) // 4,), device=dev, dtype=torch.int32)
+    count = torch.empty((2,), device=dev, dtype=torch.int64)
+
+    def run(cv, cf):
+        out = (torch.empty((cv, 3), device=dev, dtype=torch.float32),
+               None if ndc is None else torch.empty((cv, 3), device=dev, dtype=torch.float32),
+               None if vertex_edge is None else torch.empty((cv,), device=dev, dtype=torch.int64),
+               None if colors is None else torch.empty((cv, 3), device=dev, dtype=torch.uint8),
+               torch.empty((cv,), device=dev, dtype=torch.int64), torch.empty((cf, 3), device=dev, dtype=torch.int32),
+               torch.empty((cf,), device=dev, dtype=torch.int64))
+        ptr = [t.data_ptr() if t is not None and t.numel() else 0 for t in out]
+        check(lib.mvsnerf_mesh_filter_fwd(p_v, p_ndc, p_edge, p_col, V, p_f, T, p_mc, p_keep, cv, cf, *ptr, count.data_ptr(), ws.data_ptr(), stream_ptr()),
+              "mesh_filter_fwd")
+        return out
+
+    run(0, 0)
+    cv, cf = (int(v) for v in count.tolist())                            # the one host read
+    return (*run(cv, cf), count)
