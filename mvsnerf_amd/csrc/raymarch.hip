@@ -115,18 +115,42 @@ extern "C" int mvsnerf_raymarch_fwd_batched(const mvsnerf_raymarch_args* a, int 
 // so the sub-batch size is free (results do not depend on it); temporaries live in a caller-provided workspace that is
 // reused by every sub-batch (stream order makes that safe).
 // ---------------------------------------------------------------------------------------------
-static size_t render_ws_floats(int64_t B, int S, int V)
+// The workspace of both whole-frame renders: the float offset of every block and the float count, from one walk (so that the size a caller is told
+// and the pointers a render carves cannot disagree).  B rays per sub-batch, S coarse + NI importance samples per ray, F feature channels; every block
+// starts on 16 bytes.  render_pixels is NI = 0, F = 8 + 4V.
+struct RenderWs {
+    int64_t pts, ndc, z, zc, feat, raw, rdir, dirs, total;
+    RenderWs(int64_t B, int S, int NI, int F)
+    {
+        const int64_t P = B * (S + NI);
+        int64_t at = 0;
+        auto block = [&at](int64_t n) { const int64_t o = at; at += (n + 3) & ~(int64_t)3; return o; };
+        pts = block(3 * P);
+        ndc = block(3 * P);
+        z = block(P);
+        zc = block(NI > 0 ? B * S : 0);                            // coarse depths of a sub-batch (importance sampling only; else z itself is used)
+        feat = block(F * P);
+        raw = block(4 * P);
+        rdir = block(3 * B);
+        dirs = block(3 * B);
+        total = at;
+    }
+};
+
+// Rows [off, off + b.N) of a render's outputs as the outputs of sub-batch b (weights and alpha are not produced)
+template <class Args>
+static void march_outputs(MarchBatch& b, const Args* a, int64_t off)
 {
-    const int64_t P = B * S, F = 8 + 4 * V;
-    // pts, ndc (3P each), z (P), feat (F*P), raw (4P), rays_dir + dirs (3B each); every block rounded up to 16 bytes
-    auto r4 = [](int64_t n) { return (n + 3) & ~(int64_t)3; };
-    return (size_t)(r4(3 * P) * 2 + r4(P) + r4(F * P) + r4(4 * P) + r4(3 * B) * 2);
+    b.rgb_map = a->rgb + off * 3;
+    b.disp = a->disp ? a->disp + off : nullptr;
+    b.acc = a->acc ? a->acc + off : nullptr;
+    b.depth = a->depth ? a->depth + off : nullptr;
 }
 
 extern "C" size_t mvsnerf_render_workspace_floats(int batch_rays, int S, int V)
 {
     if (batch_rays < 1 || S < 1 || V < 1) return 0;
-    return render_ws_floats(batch_rays, S, V);
+    return (size_t)RenderWs(batch_rays, S, 0, 8 + 4 * V).total;
 }
 
 extern "C" int mvsnerf_render_pixels_fwd(const mvsnerf_render_args* a, void* stream)
@@ -138,21 +162,15 @@ extern "C" int mvsnerf_render_pixels_fwd(const mvsnerf_render_args* a, void* str
         return MVSNERF_EINVAL;
     if (a->n_pixels < 0 || a->first_pixel < 0 || a->S < 1 || a->V < 1 || a->batch_rays < 1 || a->W_img < 2 || a->H_img < 2) return MVSNERF_EINVAL;
     if (a->first_pixel + a->n_pixels > (int64_t)a->W_img * a->H_img) return MVSNERF_EINVAL;
-    if (a->workspace_floats < render_ws_floats(a->batch_rays, a->S, a->V)) return MVSNERF_EINVAL;
     const int F = 8 + 4 * a->V, S = a->S;
-    const int64_t B = a->batch_rays, P = B * S;
-    auto r4 = [](int64_t n) { return (n + 3) & ~(int64_t)3; };
-    float* pts = a->workspace;
-    float* ndc = pts + r4(3 * P);
-    float* z = ndc + r4(3 * P);
-    float* feat = z + r4(P);
-    float* raw = feat + r4((int64_t)F * P);
-    float* rdir = raw + r4(4 * P);
-    float* dirs = rdir + r4(3 * B);
+    const int64_t B = a->batch_rays;
+    const RenderWs ws(B, S, 0, F);
+    if (a->workspace_floats < (size_t)ws.total) return MVSNERF_EINVAL;
+    float *w = a->workspace, *pts = w + ws.pts, *ndc = w + ws.ndc, *z = w + ws.z, *rdir = w + ws.rdir;
     // every sub-batch: the same workspace slices, its own ray count and output rows (set in the loop); weights and alpha are not produced
     MarchBatch b{.vol = a->vol, .D = a->D, .H = a->H, .W = a->W, .vol_layout = a->vol_layout, .C = 8, .imgs_nhwc4 = a->imgs_nhwc4, .V = a->V, .IH = a->IH,
                  .IW = a->IW, .w2c = a->w2c, .K = a->K, .pts = pts, .ndc = ndc, .z = z, .rays_dir = rdir, .S = S, .white_bkgd = a->white_bkgd,
-                 .feat = feat, .dirs = dirs, .raw = raw, .packed = a->packed_mlp, .packed_bf16 = a->packed_mlp_bf16,
+                 .feat = w + ws.feat, .dirs = w + ws.dirs, .raw = w + ws.raw, .packed = a->packed_mlp, .packed_bf16 = a->packed_mlp_bf16,
                  .packed_split = a->packed_mlp_split, .n_split = a->n_split, .guard = a->guard};
     if (!mlp_choice_ok(b)) return MVSNERF_EINVAL;
     for (int64_t off = 0; off < a->n_pixels; off += B) {
@@ -160,10 +178,7 @@ extern "C" int mvsnerf_render_pixels_fwd(const mvsnerf_render_args* a, void* str
         if (int rc = mvsnerf_raygen_fwd(nullptr, nullptr, a->first_pixel + off, a->W_img, a->H_img, a->W_ref, a->H_ref, a->K_tgt, a->c2w_tgt, a->K_ref,
                                         a->w2c_ref, a->near_far_tgt, a->near_far_ref, a->pad, a->lindisp, nullptr, b.N, S, pts, rdir, ndc, z, nullptr, stream))
             return rc;
-        b.rgb_map = a->rgb + off * 3;
-        b.disp = a->disp ? a->disp + off : nullptr;
-        b.acc = a->acc ? a->acc + off : nullptr;
-        b.depth = a->depth ? a->depth + off : nullptr;
+        march_outputs(b, a, off);
         if (int rc = march_batch(b, (hipStream_t)stream)) return rc;
     }
     return MVSNERF_OK;
@@ -194,19 +209,10 @@ extern "C" int mvsnerf_raymarch_colorvol_fwd_batched(const mvsnerf_raymarch_args
 // volume the merged depths (ray_marcher_fine) and their points (two launches), then march_batch (image gather or colour-volume gather, MLP,
 // compositing).  Temporaries live in the caller's workspace, reused by every sub-batch (stream order makes that safe).
 // ---------------------------------------------------------------------------------------------
-static int64_t ws_r4(int64_t n) { return (n + 3) & ~(int64_t)3; }       // every workspace block starts on 16 bytes
-
-static size_t render_rays_ws_floats(int64_t B, int S, int NI, int F)
-{
-    const int64_t P = B * (S + NI);
-    // pts, ndc (3P each), z (P), coarse z (B*S, importance sampling only), feat (F*P), raw (4P), rays_dir + dirs (3B each)
-    return (size_t)(ws_r4(3 * P) * 2 + ws_r4(P) + (NI > 0 ? ws_r4(B * S) : 0) + ws_r4((int64_t)F * P) + ws_r4(4 * P) + ws_r4(3 * B) * 2);
-}
-
 extern "C" size_t mvsnerf_render_rays_workspace_floats(int batch_rays, int S, int n_importance, int F)
 {
     if (batch_rays < 1 || S < 1 || n_importance < 0 || F < 12 || (F & 3)) return 0;
-    return render_rays_ws_floats(batch_rays, S, n_importance, F);
+    return (size_t)RenderWs(batch_rays, S, n_importance, F).total;
 }
 
 extern "C" int mvsnerf_render_rays_fwd(const mvsnerf_render_rays_args* a, void* stream)
@@ -224,21 +230,15 @@ extern "C" int mvsnerf_render_rays_fwd(const mvsnerf_render_rays_args* a, void* 
     if (a->C != 8 && a->C != F) return MVSNERF_EUNSUPPORTED;
     if (F > 40 || (fine && (S > 512 || NI > 512))) return MVSNERF_EUNSUPPORTED;
     if (a->C == 8 && (!a->imgs_nhwc4 || !a->w2c || !a->K || a->IH < 2 || a->IW < 2)) return MVSNERF_EINVAL;
-    if (a->workspace_floats < render_rays_ws_floats(a->batch_rays, S, NI, F)) return MVSNERF_EINVAL;
+    const int64_t B = a->batch_rays;
+    const RenderWs ws(B, S, NI, F);
+    if (a->workspace_floats < (size_t)ws.total) return MVSNERF_EINVAL;
     if (!mvs_aligned16(a->workspace) || !mvs_aligned16(a->vol) || !mvs_aligned16(a->packed_mlp) || (a->C == 8 && !mvs_aligned16(a->imgs_nhwc4))) return MVSNERF_EALIGN;
-    const int64_t B = a->batch_rays, P = B * St;
-    float* pts = a->workspace;
-    float* ndc = pts + ws_r4(3 * P);
-    float* z = ndc + ws_r4(3 * P);
-    float* zc = z + ws_r4(P);                                      // coarse depths of a sub-batch (importance sampling only; else z itself)
-    float* feat = zc + (NI > 0 ? ws_r4(B * S) : 0);
-    float* raw = feat + ws_r4((int64_t)F * P);
-    float* rdir = raw + ws_r4(4 * P);
-    float* dirs = rdir + ws_r4(3 * B);
+    float *w = a->workspace, *pts = w + ws.pts, *ndc = w + ws.ndc, *z = w + ws.z, *zc = w + ws.zc, *rdir = w + ws.rdir;
     // a colour volume needs the reference view's w2c only (the direction feature); the image gather reads view 0 of w2c as the reference view
     MarchBatch b{.vol = a->vol, .D = a->D, .H = a->H, .W = a->W, .vol_layout = a->vol_layout, .C = a->C, .imgs_nhwc4 = a->C == 8 ? a->imgs_nhwc4 : nullptr,
                  .V = a->V, .IH = a->IH, .IW = a->IW, .w2c = a->C == 8 ? a->w2c : a->w2c_ref, .K = a->K, .pts = pts, .ndc = ndc, .z = z, .rays_dir = rdir,
-                 .S = St, .white_bkgd = a->white_bkgd, .feat = feat, .dirs = dirs, .raw = raw, .packed = a->packed_mlp, .packed_bf16 = a->packed_mlp_bf16,
+                 .S = St, .white_bkgd = a->white_bkgd, .feat = w + ws.feat, .dirs = w + ws.dirs, .raw = w + ws.raw, .packed = a->packed_mlp, .packed_bf16 = a->packed_mlp_bf16,
                  .packed_split = a->packed_mlp_split, .n_split = a->n_split, .guard = a->guard};
     if (!mlp_choice_ok(b)) return MVSNERF_EINVAL;
     for (int64_t off = 0; off < a->n_rays; off += B) {
@@ -255,10 +255,7 @@ extern "C" int mvsnerf_render_rays_fwd(const mvsnerf_render_rays_args* a, void* 
                                         nullptr, nullptr, 0, nullptr, nullptr, stream))
                 return rc;
         }
-        b.rgb_map = a->rgb + off * 3;
-        b.disp = a->disp ? a->disp + off : nullptr;
-        b.acc = a->acc ? a->acc + off : nullptr;
-        b.depth = a->depth ? a->depth + off : nullptr;
+        march_outputs(b, a, off);
         if (int rc = march_batch(b, (hipStream_t)stream)) return rc;
     }
     return MVSNERF_OK;

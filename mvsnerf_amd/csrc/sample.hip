@@ -353,6 +353,31 @@ __global__ __launch_bounds__(256) void gather_fused_counted_kernel(GatherArgs a,
     gather_fused_block<SMALL, ZFAST>(a);
 }
 
+// The launch of both image-gather entries, behind their argument checks: a.P rows (N * S samples, or the capacity of a counted launch); count NULL: the
+// plain kernel, else the counted one on the same grid (one block of 256 threads per 64 rows)
+template <bool SMALL, bool ZFAST>
+static void gather_launch_as(const GatherArgs& a, const int* count, unsigned grid, hipStream_t st)
+{
+    if (count) gather_fused_counted_kernel<SMALL, ZFAST><<<grid, 256, 0, st>>>(a, count);
+    else gather_fused_kernel<SMALL, ZFAST><<<grid, 256, 0, st>>>(a);
+}
+
+static int gather_launch(const GatherArgs& a, const int* count, int vol_layout, void* stream)
+{
+    const bool small = gather_fits_32bit(a.D, a.H, a.W, a.V, a.IH, a.IW, a.P, a.feat_stride);
+    const unsigned grid = mvs_cdiv(a.P * 4, 256);
+    hipStream_t st = (hipStream_t)stream;
+    if (vol_layout == MVSNERF_VOL_HWDC) {
+        if (small) gather_launch_as<true, true>(a, count, grid, st);
+        else gather_launch_as<false, true>(a, count, grid, st);
+    } else {
+        if (small) gather_launch_as<true, false>(a, count, grid, st);
+        else gather_launch_as<false, false>(a, count, grid, st);
+    }
+    MVS_LAUNCH_CHECK();
+    return MVSNERF_OK;
+}
+
 extern "C" int mvsnerf_gather_fwd(const float* vol, int D, int H, int W, const float* imgs_nhwc4, int V, int IH, int IW,
                                   const float* w2c, const float* K, const float* pts, const float* ndc, int64_t N, int S,
                                   const float* rays_dir, float* feat, int feat_stride, float* dirs_out, int vol_layout, void* stream)
@@ -364,20 +389,7 @@ extern "C" int mvsnerf_gather_fwd(const float* vol, int D, int H, int W, const f
     if (feat_stride < 8 + 4 * V) return MVSNERF_EINVAL;
     if ((feat_stride & 3) || !mvs_aligned16(feat) || !mvs_aligned16(vol) || !mvs_aligned16(imgs_nhwc4)) return MVSNERF_EALIGN;
     if (N == 0) return MVSNERF_OK;
-    const int64_t P = N * S;
-    const GatherArgs a{vol, D, H, W, imgs_nhwc4, V, IH, IW, w2c, K, pts, ndc, P, N, rays_dir, feat, feat_stride, dirs_out};
-    const bool small = gather_fits_32bit(D, H, W, V, IH, IW, P, feat_stride);
-    const unsigned grid = mvs_cdiv(P * 4, 256);
-    hipStream_t st = (hipStream_t)stream;
-    if (vol_layout == MVSNERF_VOL_HWDC) {
-        if (small) gather_fused_kernel<true, true><<<grid, 256, 0, st>>>(a);
-        else gather_fused_kernel<false, true><<<grid, 256, 0, st>>>(a);
-    } else {
-        if (small) gather_fused_kernel<true, false><<<grid, 256, 0, st>>>(a);
-        else gather_fused_kernel<false, false><<<grid, 256, 0, st>>>(a);
-    }
-    MVS_LAUNCH_CHECK();
-    return MVSNERF_OK;
+    return gather_launch({vol, D, H, W, imgs_nhwc4, V, IH, IW, w2c, K, pts, ndc, N * S, N, rays_dir, feat, feat_stride, dirs_out}, nullptr, vol_layout, stream);
 }
 
 // mvsnerf_gather_fwd on the first min(max(*count, 0), cap) of cap rows (S = 1: pts / ndc / rays_dir / dirs_out are [cap][3], feat [cap][feat_stride]),
@@ -393,19 +405,7 @@ extern "C" int mvsnerf_gather_fwd_counted(const float* vol, int D, int H, int W,
     if (int rc = mvs_counted_args(count, cap)) return rc;
     if ((feat_stride & 3) || !mvs_aligned16(feat) || !mvs_aligned16(vol) || !mvs_aligned16(imgs_nhwc4)) return MVSNERF_EALIGN;
     if (cap == 0) return MVSNERF_OK;
-    const GatherArgs a{vol, D, H, W, imgs_nhwc4, V, IH, IW, w2c, K, pts, ndc, cap, cap, rays_dir, feat, feat_stride, dirs_out};
-    const bool small = gather_fits_32bit(D, H, W, V, IH, IW, cap, feat_stride);
-    const unsigned grid = mvs_cdiv(cap, 64);
-    hipStream_t st = (hipStream_t)stream;
-    if (vol_layout == MVSNERF_VOL_HWDC) {
-        if (small) gather_fused_counted_kernel<true, true><<<grid, 256, 0, st>>>(a, count);
-        else gather_fused_counted_kernel<false, true><<<grid, 256, 0, st>>>(a, count);
-    } else {
-        if (small) gather_fused_counted_kernel<true, false><<<grid, 256, 0, st>>>(a, count);
-        else gather_fused_counted_kernel<false, false><<<grid, 256, 0, st>>>(a, count);
-    }
-    MVS_LAUNCH_CHECK();
-    return MVSNERF_OK;
+    return gather_launch({vol, D, H, W, imgs_nhwc4, V, IH, IW, w2c, K, pts, ndc, cap, cap, rays_dir, feat, feat_stride, dirs_out}, count, vol_layout, stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -492,6 +492,35 @@ __global__ __launch_bounds__(256) void volume_sample_wide_counted_kernel(WideGat
     volume_sample_wide_block<SMALL, ZFAST>(a);
 }
 
+// The launch of both colour-volume gather entries, behind their argument checks: a.P rows (N * S samples, or the capacity of a counted launch); a.spb
+// and a.magic are filled in here; count NULL: the plain kernel, else the counted one on the same grid
+template <bool SMALL, bool ZFAST>
+static void gather_colorvol_launch_as(const WideGatherArgs& a, const int* count, unsigned grid, hipStream_t st)
+{
+    if (count) volume_sample_wide_counted_kernel<SMALL, ZFAST><<<grid, 256, 0, st>>>(a, count);
+    else volume_sample_wide_kernel<SMALL, ZFAST><<<grid, 256, 0, st>>>(a);
+}
+
+static int gather_colorvol_launch(WideGatherArgs a, const int* count, int vol_layout, int force_offsets64, void* stream)
+{
+    const int Q = a.C >> 2;
+    a.spb = 256 / Q;
+    a.magic = (65536 + Q - 1) / Q;
+    if ((a.P + a.spb - 1) / a.spb >= ((int64_t)1 << 31)) return MVSNERF_EUNSUPPORTED;
+    const bool small = !force_offsets64 && (int64_t)a.D * a.H * a.W * a.C < ((int64_t)1 << 31) && a.P * (int64_t)a.feat_stride < ((int64_t)1 << 31);
+    const unsigned grid = (unsigned)((a.P + a.spb - 1) / a.spb);
+    hipStream_t st = (hipStream_t)stream;
+    if (vol_layout == MVSNERF_VOL_HWDC) {
+        if (small) gather_colorvol_launch_as<true, true>(a, count, grid, st);
+        else gather_colorvol_launch_as<false, true>(a, count, grid, st);
+    } else {
+        if (small) gather_colorvol_launch_as<true, false>(a, count, grid, st);
+        else gather_colorvol_launch_as<false, false>(a, count, grid, st);
+    }
+    MVS_LAUNCH_CHECK();
+    return MVSNERF_OK;
+}
+
 extern "C" int mvsnerf_gather_colorvol_fwd(const float* vol, int D, int H, int W, int C, const float* ndc, int64_t N, int S,
                                            const float* rays_dir, const float* w2c_ref, float* feat, int feat_stride, float* dirs_out,
                                            int vol_layout, int force_offsets64, void* stream)
@@ -502,22 +531,7 @@ extern "C" int mvsnerf_gather_colorvol_fwd(const float* vol, int D, int H, int W
     if ((C & 3) || C <= 8 || C > 40) return MVSNERF_EUNSUPPORTED;
     if ((feat_stride & 3) || !mvs_aligned16(feat) || !mvs_aligned16(vol)) return MVSNERF_EALIGN;
     if (N == 0) return MVSNERF_OK;
-    const int64_t P = N * S;
-    const int Q = C >> 2, spb = 256 / Q;
-    if ((P + spb - 1) / spb >= ((int64_t)1 << 31)) return MVSNERF_EUNSUPPORTED;
-    const WideGatherArgs a{vol, D, H, W, C, ndc, P, dirs_out ? N : 0, rays_dir, w2c_ref, feat, feat_stride, dirs_out, spb, (65536 + Q - 1) / Q};
-    const bool small = !force_offsets64 && (int64_t)D * H * W * C < ((int64_t)1 << 31) && P * (int64_t)feat_stride < ((int64_t)1 << 31);
-    const unsigned grid = (unsigned)((P + spb - 1) / spb);
-    hipStream_t st = (hipStream_t)stream;
-    if (vol_layout == MVSNERF_VOL_HWDC) {
-        if (small) volume_sample_wide_kernel<true, true><<<grid, 256, 0, st>>>(a);
-        else volume_sample_wide_kernel<false, true><<<grid, 256, 0, st>>>(a);
-    } else {
-        if (small) volume_sample_wide_kernel<true, false><<<grid, 256, 0, st>>>(a);
-        else volume_sample_wide_kernel<false, false><<<grid, 256, 0, st>>>(a);
-    }
-    MVS_LAUNCH_CHECK();
-    return MVSNERF_OK;
+    return gather_colorvol_launch({vol, D, H, W, C, ndc, N * S, dirs_out ? N : 0, rays_dir, w2c_ref, feat, feat_stride, dirs_out}, nullptr, vol_layout, force_offsets64, stream);
 }
 
 // mvsnerf_gather_colorvol_fwd on the first min(max(*count, 0), cap) of cap rows (S = 1: ndc / rays_dir / dirs_out are [cap][3], feat
@@ -533,20 +547,7 @@ extern "C" int mvsnerf_gather_colorvol_fwd_counted(const float* vol, int D, int 
     if ((C & 3) || C <= 8 || C > 40) return MVSNERF_EUNSUPPORTED;
     if ((feat_stride & 3) || !mvs_aligned16(feat) || !mvs_aligned16(vol)) return MVSNERF_EALIGN;
     if (cap == 0) return MVSNERF_OK;
-    const int Q = C >> 2, spb = 256 / Q;
-    const WideGatherArgs a{vol, D, H, W, C, ndc, cap, dirs_out ? cap : 0, rays_dir, w2c_ref, feat, feat_stride, dirs_out, spb, (65536 + Q - 1) / Q};
-    const bool small = !force_offsets64 && (int64_t)D * H * W * C < ((int64_t)1 << 31) && cap * (int64_t)feat_stride < ((int64_t)1 << 31);
-    const unsigned grid = (unsigned)((cap + spb - 1) / spb);
-    hipStream_t st = (hipStream_t)stream;
-    if (vol_layout == MVSNERF_VOL_HWDC) {
-        if (small) volume_sample_wide_counted_kernel<true, true><<<grid, 256, 0, st>>>(a, count);
-        else volume_sample_wide_counted_kernel<false, true><<<grid, 256, 0, st>>>(a, count);
-    } else {
-        if (small) volume_sample_wide_counted_kernel<true, false><<<grid, 256, 0, st>>>(a, count);
-        else volume_sample_wide_counted_kernel<false, false><<<grid, 256, 0, st>>>(a, count);
-    }
-    MVS_LAUNCH_CHECK();
-    return MVSNERF_OK;
+    return gather_colorvol_launch({vol, D, H, W, C, ndc, cap, dirs_out ? cap : 0, rays_dir, w2c_ref, feat, feat_stride, dirs_out}, count, vol_layout, force_offsets64, stream);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -350,12 +350,21 @@ def ray_march_bbox(rays, bbox_3d, N_samples, lindisp=False, perturb=0.0, jitter=
     return pts, ndc, z
 
 
+def _bank_images(images, op):
+    """(M, H, W) of an image bank (SceneRays.images): a contiguous (M,H,W,4) uint8 tensor on the current device."""
+    if not (torch.is_tensor(images) and images.is_cuda and images.dtype == torch.uint8 and images.dim() == 4 and images.shape[-1] == 4
+            and images.is_contiguous()):
+        raise RuntimeError(f"{op}: images must be a contiguous (M,H,W,4) uint8 tensor on the GPU (SceneRays.images), got "
+                           f"{tuple(getattr(images, 'shape', ()))} {getattr(images, 'dtype', None)} {getattr(images, 'device', None)}")
+    if images.device.index != torch.cuda.current_device():
+        raise RuntimeError(f"{op}: the bank is on {images.device} but the current device is cuda:{torch.cuda.current_device()}")
+    return tuple(int(v) for v in images.shape[:3])
+
+
 def _scene_bank(images, c2ws, intrinsics, near_far, depths, idx, op):
     """The bank and index pointers of the scene_rays entries (mvsnerf_amd.rays.SceneRays holds the tensors in this form): images (M,H,W,4) uint8,
     c2ws (M,3,4), intrinsics (M,3,3), near_far (M,2) fp32, depths (M,H,W) fp32 | None, idx (B,) int64; all contiguous on the current device."""
-    if images.dim() != 4 or images.shape[-1] != 4 or images.dtype != torch.uint8 or not images.is_cuda or not images.is_contiguous():
-        raise RuntimeError(f"{op}: images must be a contiguous (M,H,W,4) uint8 tensor on the GPU, got {tuple(images.shape)} {images.dtype} {images.device}")
-    M, H, W = (int(v) for v in images.shape[:3])
+    M, H, W = _bank_images(images, op)
     if tuple(c2ws.shape) != (M, 3, 4) or tuple(intrinsics.shape) != (M, 3, 3) or tuple(near_far.shape) != (M, 2):
         raise RuntimeError(f"{op}: c2ws ({M},3,4), intrinsics ({M},3,3) and near_far ({M},2) expected, got {tuple(c2ws.shape)}, "
                            f"{tuple(intrinsics.shape)}, {tuple(near_far.shape)}")
@@ -363,8 +372,6 @@ def _scene_bank(images, c2ws, intrinsics, near_far, depths, idx, op):
         raise RuntimeError(f"{op}: depths must be ({M},{H},{W}), got {tuple(depths.shape)}")
     if idx.dim() != 1 or idx.dtype != torch.int64 or idx.device != images.device or not idx.is_contiguous():
         raise RuntimeError(f"{op}: idx must be a contiguous (B,) int64 tensor on {images.device}, got {tuple(idx.shape)} {idx.dtype} {idx.device}")
-    if images.device.index != torch.cuda.current_device():
-        raise RuntimeError(f"{op}: the bank is on {images.device} but the current device is cuda:{torch.cuda.current_device()}")
     return M, H, W
 
 
@@ -425,13 +432,9 @@ def scene_rays_march(images, c2ws, intrinsics, near_far, idx, N_samples, t=None,
 def source_images(images, ids, mean, std):
     """The `imgs` of read_source_views (data/dtu_ft.py:72-119) from the bank in one launch: images (M,H,W,4) uint8, ids (V,) int64 on the bank's device ->
     (V,3,H,W) fp32 = T.Normalize(mean, std)(ToTensor, blended onto white); an id outside [0, M) gives zeros."""
-    if images.dim() != 4 or images.shape[-1] != 4 or images.dtype != torch.uint8 or not images.is_cuda or not images.is_contiguous():
-        raise RuntimeError(f"source_images: images must be a contiguous (M,H,W,4) uint8 tensor on the GPU, got {tuple(images.shape)} {images.dtype} {images.device}")
+    M, H, W = _bank_images(images, "source_images")
     if ids.dim() != 1 or ids.dtype != torch.int64 or ids.device != images.device or not ids.is_contiguous() or ids.shape[0] < 1:
         raise RuntimeError(f"source_images: ids must be a contiguous (V,) int64 tensor on {images.device}, V >= 1, got {tuple(ids.shape)} {ids.dtype} {ids.device}")
-    if images.device.index != torch.cuda.current_device():
-        raise RuntimeError(f"source_images: the bank is on {images.device} but the current device is cuda:{torch.cuda.current_device()}")
-    M, H, W = (int(v) for v in images.shape[:3])
     V = int(ids.shape[0])
     f3 = ctypes.c_float * 3
     out = torch.empty((V, 3, H, W), device=images.device, dtype=torch.float32)
@@ -770,32 +773,25 @@ def mlp_forward(packed, F, ndc_ptr, ndc_stride, feat_ptr, feat_stride, dirs_ptr,
         if tuple(raw.shape) != (N * S, 1 if alpha_only else 4):
             raise RuntimeError(f"mlp_forward: out must be ({N * S},{1 if alpha_only else 4}), got {tuple(raw.shape)}")
         dev_f32(raw, "mlp_forward: out")
-    if cptr is not None:
-        io = (ndc_ptr, feat_ptr, dirs_ptr, N, cptr, int(alpha_only), raw.data_ptr())
-        if wide:
-            check(l.mvsnerf_mlp_fwd_wide_counted(dev_f32(packed.buffer, "packed"), F, packed.width, *io, stream_ptr()), "mlp_fwd_wide_counted")
-        elif guard is not None:
-            if packed_split is None:
-                raise ValueError("mlp_forward: a guard needs the fp16x3 split planes (the guarded sequence)")
-            check(l.mvsnerf_mlp_fwd_guarded_counted(packed_split[0].data_ptr(), packed.data_ptr(), F, *io, guard.data_ptr(), stream_ptr()), "mlp_fwd_guarded_counted")
-        elif packed_split is not None:
-            check(l.mvsnerf_mlp_fwd_split_counted(packed_split[0].data_ptr(), packed.data_ptr(), F, packed_split[1], *io, stream_ptr()), "mlp_fwd_split_counted")
-        else:
-            check(l.mvsnerf_mlp_fwd_counted(packed.data_ptr(), F, *io, stream_ptr()), "mlp_fwd_counted")
-        return raw
-    io = (ndc_ptr, ndc_stride, feat_ptr, feat_stride, dirs_ptr, dirs_stride, N, S, int(alpha_only), raw.data_ptr())
+    # (wide | guarded | split | bf16 | fp32) x (plain | counted): the entry is mvsnerf_mlp_fwd[_<kernel>][_counted](*head, *io[, guard], stream);
+    # a counted call has been refused above for the kernels without a counted entry
     if wide:
-        check(l.mvsnerf_mlp_fwd_wide(dev_f32(packed.buffer, "packed"), F, packed.width, *io, stream_ptr()), "mlp_fwd_wide")
+        kernel, head = "_wide", (dev_f32(packed.buffer, "packed"), F, packed.width)
     elif guard is not None:
         if packed_split is None or packed_split[1] != N_SPLIT["fp16x3"]:
             raise ValueError("mlp_forward: a guard needs the fp16x3 split planes (the guarded sequence)")
-        check(l.mvsnerf_mlp_fwd_guarded(packed_split[0].data_ptr(), packed.data_ptr(), F, *io, guard.data_ptr(), stream_ptr()), "mlp_fwd_guarded")
+        kernel, head = "_guarded", (packed_split[0].data_ptr(), packed.data_ptr(), F)
     elif packed_split is not None:
-        check(l.mvsnerf_mlp_fwd_split(packed_split[0].data_ptr(), packed.data_ptr(), F, packed_split[1], *io, stream_ptr()), "mlp_fwd_split")
+        kernel, head = "_split", (packed_split[0].data_ptr(), packed.data_ptr(), F, packed_split[1])
     elif packed_bf16 is not None:
-        check(l.mvsnerf_mlp_fwd_bf16(packed_bf16.data_ptr(), packed.data_ptr(), F, *io, stream_ptr()), "mlp_fwd_bf16")
+        kernel, head = "_bf16", (packed_bf16.data_ptr(), packed.data_ptr(), F)
     else:
-        check(l.mvsnerf_mlp_fwd(packed.data_ptr(), F, *io, stream_ptr()), "mlp_fwd")
+        kernel, head = "", (packed.data_ptr(), F)
+    if cptr is None:
+        name, io = f"mlp_fwd{kernel}", (ndc_ptr, ndc_stride, feat_ptr, feat_stride, dirs_ptr, dirs_stride, N, S)
+    else:
+        name, io = f"mlp_fwd{kernel}_counted", (ndc_ptr, feat_ptr, dirs_ptr, N, cptr)
+    check(getattr(l, "mvsnerf_" + name)(*head, *io, int(alpha_only), raw.data_ptr(), *(() if guard is None else (guard.data_ptr(),)), stream_ptr()), name)
     return raw
 
 
@@ -840,25 +836,27 @@ def composite(raw, z_vals, white_bkgd=False):
 
 # ------------------------------------------------------------------ fused ray march
 def _raymarch_block(vol_cl, imgs, w2cs, intrinsics, packed, rays_pts, rays_ndc, z_vals, rays_dir, white_bkgd, packed_bf16, packed_split, guard, want, imgs_cl, cur):
-    """Output tensors + the filled mvsnerf_raymarch_args (_lib.RaymarchArgs) of one batch."""
+    """Output tensors + the filled mvsnerf_raymarch_args (_lib.RaymarchArgs) of one batch.  imgs None: a batch on an (8 + 4V)-channel colour volume
+    (V from w2cs; the caller has checked the channel count) - the image, intrinsics and point fields stay 0."""
     N, S = z_vals.shape
-    V = imgs.shape[0]
-    F = 8 + 4 * V
     D, H, W, C = vol_cl.shape
-    if C != 8:
+    V = w2cs.shape[0] if imgs is None else imgs.shape[0]
+    if imgs is not None and C != 8:
         raise RuntimeError("raymarch: the neural volume must have 8 channels")
-    shapes = {"input_feat": (N, S, F), "raw": (N, S, 4), "rgb_map": (N, 3), "weights": (N, S), "depth": (N,), "alpha": (N, S), **{k: (N,) for k in want},
-              "_dirs_tmp": (N, 3)}
-    out = {k: torch.empty(sh, device=rays_pts.device, dtype=torch.float32) for k, sh in shapes.items()}
-    if imgs_cl is None and FUSED_GATHER:
+    shapes = {"input_feat": (N, S, C if imgs is None else 8 + 4 * V), "raw": (N, S, 4), "rgb_map": (N, 3), "weights": (N, S), "depth": (N,),
+              "alpha": (N, S), **{k: (N,) for k in want}, "_dirs_tmp": (N, 3)}
+    out = {k: torch.empty(sh, device=rays_ndc.device, dtype=torch.float32) for k, sh in shapes.items()}
+    if imgs is not None and imgs_cl is None and FUSED_GATHER:
         imgs_cl = channels_last_images(imgs)
     vp, vl = vol_ptr_layout(vol_cl, cur)
     ptrs = {k: out[k].data_ptr() if k in out else 0 for k in ("input_feat", "raw", "rgb_map", "disp", "acc", "weights", "depth", "alpha")}
+    if imgs is not None:
+        ptrs.update(imgs=dev_f32(imgs, "imgs", cur), IH=imgs.shape[2], IW=imgs.shape[3],
+                    imgs_nhwc4=imgs_cl.data_ptr() if (FUSED_GATHER and imgs_cl is not None) else 0,
+                    K=dev_f32(intrinsics, "intrinsics", cur), rays_pts=dev_f32(rays_pts, "rays_pts", cur))
     return out, _lib.RaymarchArgs(
-        vol=vp, D=D, H=H, W=W, vol_layout=vl, imgs=dev_f32(imgs, "imgs", cur), V=V, IH=imgs.shape[2], IW=imgs.shape[3],
-        imgs_nhwc4=imgs_cl.data_ptr() if (FUSED_GATHER and imgs_cl is not None) else 0,
-        w2c=dev_f32(w2cs, "w2cs", cur), K=dev_f32(intrinsics, "intrinsics", cur), packed_mlp=dev_f32(packed, "packed", cur),
-        rays_pts=dev_f32(rays_pts, "rays_pts", cur), rays_ndc=dev_f32(rays_ndc, "rays_ndc", cur), z_vals=dev_f32(z_vals, "z_vals", cur),
+        vol=vp, D=D, H=H, W=W, vol_layout=vl, V=V, w2c=dev_f32(w2cs, "w2cs", cur), packed_mlp=dev_f32(packed, "packed", cur),
+        rays_ndc=dev_f32(rays_ndc, "rays_ndc", cur), z_vals=dev_f32(z_vals, "z_vals", cur),
         rays_dir=dev_f32(rays_dir, "rays_dir", cur), N=N, S=S, white_bkgd=int(bool(white_bkgd)), dirs_tmp=out["_dirs_tmp"].data_ptr(), **ptrs,
         **_mlp_fields(packed_bf16, packed_split, guard))
 
@@ -898,23 +896,15 @@ def raymarch_colorvol_batched(vol_cl, w2cs, packed, ray_batches, white_bkgd=Fals
     w2cs (V,4,4), view 0 the reference view.  No images, intrinsics or points are needed: the feature row is one lookup of the volume."""
     _need_narrow(packed, "raymarch_colorvol_batched")
     cur = torch.cuda.current_device()
-    D, H, W, C = vol_cl.shape
-    V = w2cs.shape[0]
+    C, V = vol_cl.shape[-1], w2cs.shape[0]
     if C != 8 + 4 * V:
         raise RuntimeError(f"raymarch_colorvol_batched: the volume has {C} channels, 8 + 4V is {8 + 4 * V}")
-    vp, vl = vol_ptr_layout(vol_cl, cur)
+    if not ray_batches:
+        vol_ptr_layout(vol_cl, cur)                 # (a volume no batch would have met is refused all the same)
     outs, blocks = [], (_lib.RaymarchArgs * len(ray_batches))()
     for k, (ndc, z, rdir) in enumerate(ray_batches):
         _need_no_grad(vol_cl, ndc, z, rdir, op="raymarch_colorvol_batched")
-        N, S = z.shape
-        shapes = {"input_feat": (N, S, C), "raw": (N, S, 4), "rgb_map": (N, 3), "weights": (N, S), "depth": (N,), "alpha": (N, S), **{q: (N,) for q in want},
-                  "_dirs_tmp": (N, 3)}
-        out = {q: torch.empty(sh, device=ndc.device, dtype=torch.float32) for q, sh in shapes.items()}
-        ptrs = {q: out[q].data_ptr() if q in out else 0 for q in ("input_feat", "raw", "rgb_map", "disp", "acc", "weights", "depth", "alpha")}
-        blocks[k] = _lib.RaymarchArgs(vol=vp, D=D, H=H, W=W, vol_layout=vl, V=V, w2c=dev_f32(w2cs, "w2cs", cur), packed_mlp=dev_f32(packed, "packed", cur),
-                                      rays_ndc=dev_f32(ndc, "rays_ndc", cur), z_vals=dev_f32(z, "z_vals", cur), rays_dir=dev_f32(rdir, "rays_dir", cur),
-                                      N=N, S=S, white_bkgd=int(bool(white_bkgd)), dirs_tmp=out["_dirs_tmp"].data_ptr(), **ptrs,
-                                      **_mlp_fields(packed_bf16, packed_split, guard))
+        out, blocks[k] = _raymarch_block(vol_cl, None, w2cs, None, packed, None, ndc, z, rdir, white_bkgd, packed_bf16, packed_split, guard, want, None, cur)
         outs.append(out)
     check(_lib.lib().mvsnerf_raymarch_colorvol_fwd_batched(blocks, len(ray_batches), C, stream_ptr()), "raymarch_colorvol_fwd_batched")
     return outs
@@ -945,23 +935,14 @@ def render_rays(vol_cl, rays, t, packed, K_ref, w2c_ref, nf_ref, ref_hw, n_views
     if C == 8 and (imgs is None or w2cs is None or intrinsics is None or imgs.shape[0] != V):
         raise RuntimeError("render_rays: an 8-channel volume needs imgs (n_views,3,H,W), w2cs and intrinsics")
     dev = vol_cl.device
-    f32 = dict(device=dev, dtype=torch.float32)
     B = int(min(batch_rays, max(n, 1)))
     ws_n = lib.mvsnerf_render_rays_workspace_floats(B, S, NI, F)
     if ws_n == 0:
         raise RuntimeError(f"render_rays: unsupported sizes (batch_rays {B}, S {S}, n_importance {NI}, F {F})")
-    # one workspace per (size, device, STREAM), as render_pixels keeps them
-    key = ("rays", ws_n, dev.index if dev.index is not None else torch.cuda.current_device(), torch.cuda.current_stream(dev).cuda_stream)
-    ws = _render_ws.get(key)
-    if ws is None:
-        while len(_render_ws) >= 4:
-            _render_ws.pop(next(iter(_render_ws)))
-        ws = _render_ws[key] = torch.empty(ws_n, **f32)
-    out = {"rgb": torch.empty((n, 3), **f32)}
-    for k in ("depth", "acc", "disp"):
-        out[k] = torch.empty((n,), **f32) if k in want else None
+    ws = _render_workspace(ws_n, dev, "rays")
+    out, ptrs = _render_outputs(n, want, dev)
     if n == 0:
-        return {k: v for k, v in out.items() if v is not None}
+        return out
     c = _Keep()
     vp, vl = vol_ptr_layout(vol_cl)
     src = {}
@@ -973,10 +954,10 @@ def render_rays(vol_cl, rays, t, packed, K_ref, w2c_ref, nf_ref, ref_hw, n_views
         vol=vp, D=D, H=Hv, W=Wv, C=C, vol_layout=vl, V=V, K_ref=c(K_ref, "K_ref"), w2c_ref=c(w2c_ref, "w2c_ref"),
         near_far_ref=c(nf_ref.reshape(-1)[:2], "near_far_ref"), W_ref=int(ref_hw[1]), H_ref=int(ref_hw[0]), pad=int(pad), lindisp=int(bool(lindisp)),
         packed_mlp=packed.data_ptr(), rays=c(rays, "rays"), first_ray=int(first_ray), n_rays=n, t=c(t, "t"), S=S,
-        white_bkgd=int(bool(white_bkgd)), batch_rays=B, workspace=ws.data_ptr(), workspace_floats=ws_n,
-        **{k: 0 if out[k] is None else out[k].data_ptr() for k in out}, **src, **_mlp_fields(packed_bf16, packed_split, guard))
+        white_bkgd=int(bool(white_bkgd)), batch_rays=B, workspace=ws.data_ptr(), workspace_floats=ws_n, **ptrs, **src,
+        **_mlp_fields(packed_bf16, packed_split, guard))
     check(lib.mvsnerf_render_rays_fwd(ctypes.byref(a), stream_ptr()), "render_rays_fwd")
-    return {k: v for k, v in out.items() if v is not None}
+    return out
 
 
 def render_pixels(vol_cl, imgs, w2cs, intrinsics, packed, H, W, K_tgt, c2w_tgt, K_ref, w2c_ref, nf_tgt, nf_ref, N_samples,
@@ -993,21 +974,12 @@ def render_pixels(vol_cl, imgs, w2cs, intrinsics, packed, H, W, K_tgt, c2w_tgt, 
     if C != 8:
         raise RuntimeError("render_pixels: the neural volume must have 8 channels")
     dev = vol_cl.device
-    f32 = dict(device=dev, dtype=torch.float32)
     B = int(min(batch_rays, max(n, 1)))
     ws_n = lib.mvsnerf_render_workspace_floats(B, N_samples, V)
-    # one workspace per (size, device, STREAM): two streams rendering on one device must not share intermediates (same reason as guard_words)
-    key = (ws_n, dev.index if dev.index is not None else torch.cuda.current_device(), torch.cuda.current_stream(dev).cuda_stream)
-    ws = _render_ws.get(key)
-    if ws is None:
-        while len(_render_ws) >= 4:
-            _render_ws.pop(next(iter(_render_ws)))
-        ws = _render_ws[key] = torch.empty(ws_n, **f32)
-    out = {"rgb": torch.empty((n, 3), **f32)}
-    for k in ("depth", "acc", "disp"):
-        out[k] = torch.empty((n,), **f32) if k in want else None
+    ws = _render_workspace(ws_n, dev, "pixels")
+    out, ptrs = _render_outputs(n, want, dev)
     if n == 0:
-        return {k: v for k, v in out.items() if v is not None}
+        return out
     c = _Keep()
     vp, vl = vol_ptr_layout(vol_cl)
     a = _lib.RenderArgs(
@@ -1016,12 +988,32 @@ def render_pixels(vol_cl, imgs, w2cs, intrinsics, packed, H, W, K_tgt, c2w_tgt, 
         K_ref=c(K_ref, "K_ref"), w2c_ref=c(w2c_ref, "w2c_ref"), near_far_tgt=c(nf_tgt, "near_far_tgt"), near_far_ref=c(nf_ref, "near_far_ref"),
         W_img=W, H_img=H, pad=int(pad), lindisp=int(bool(lindisp)), W_ref=0 if ref_hw is None else int(ref_hw[1]), H_ref=0 if ref_hw is None else int(ref_hw[0]),
         first_pixel=int(first_pixel), n_pixels=n, S=int(N_samples), white_bkgd=int(bool(white_bkgd)), batch_rays=B, workspace=ws.data_ptr(),
-        workspace_floats=ws_n, **{k: 0 if out[k] is None else out[k].data_ptr() for k in out}, **_mlp_fields(packed_bf16, packed_split, guard))
+        workspace_floats=ws_n, **ptrs, **_mlp_fields(packed_bf16, packed_split, guard))
     check(lib.mvsnerf_render_pixels_fwd(ctypes.byref(a), stream_ptr()), "render_pixels_fwd")
-    return {k: v for k, v in out.items() if v is not None}
+    return out
 
 
 _render_ws = {}
+
+
+def _render_workspace(ws_n, dev, kind):
+    """The workspace of a whole-frame render, one per (size, device, STREAM, kind): two streams rendering on one device must not share intermediates
+    (same reason as guard_words).  At most four are kept; the oldest goes first."""
+    key = (ws_n, dev.index if dev.index is not None else torch.cuda.current_device(), torch.cuda.current_stream(dev).cuda_stream, kind)
+    ws = _render_ws.get(key)
+    if ws is None:
+        while len(_render_ws) >= 4:
+            _render_ws.pop(next(iter(_render_ws)))
+        ws = _render_ws[key] = torch.empty(ws_n, device=dev, dtype=torch.float32)
+    return ws
+
+
+def _render_outputs(n, want, dev):
+    """(the dict a whole-frame render returns: rgb (n,3) and those of depth / acc / disp (n,) that are in `want`; the four output fields of its
+    argument block, 0 for a map that is not wanted)"""
+    out = {"rgb": torch.empty((n, 3), device=dev, dtype=torch.float32)}
+    out.update({k: torch.empty((n,), device=dev, dtype=torch.float32) for k in ("depth", "acc", "disp") if k in want})
+    return out, {k: out[k].data_ptr() if k in out else 0 for k in ("rgb", "depth", "acc", "disp")}
 
 
 # ------------------------------------------------------------------ empty-space skipping (csrc/sparse.hip)
@@ -1030,6 +1022,20 @@ def _thr_f32(thr, op):
     if thr != thr:
         raise ValueError(f"{op}: the density threshold is NaN")
     return thr
+
+
+def _ray_batch(rays_ndc, rays_pts, rays_dir, ray_T, op):
+    """(N, S) of a ray batch after the shape checks: rays_ndc (N,S,3), rays_pts (N,S,3) | None, rays_dir (N,3) | None, ray_T (N,) | None, S >= 1 and
+    N * S below 2^31."""
+    if rays_ndc.dim() != 3 or rays_ndc.shape[-1] != 3:
+        raise RuntimeError(f"{op}: rays_ndc must be (N,S,3), got {tuple(rays_ndc.shape)}")
+    N, S = int(rays_ndc.shape[0]), int(rays_ndc.shape[1])
+    for t, name, shape in ((rays_pts, "rays_pts", (N, S, 3)), (rays_dir, "rays_dir", (N, 3)), (ray_T, "ray_T", (N,))):
+        if t is not None and tuple(t.shape) != shape:
+            raise RuntimeError(f"{op}: {name} must be ({','.join(map(str, shape))}{',' if len(shape) == 1 else ''}), got {tuple(t.shape)}")
+    if S < 1 or N * S >= 2 ** 31:
+        raise RuntimeError(f"{op}: {N} x {S} samples: S >= 1 and fewer than 2^31 samples (idx is int32)")
+    return N, S
 
 
 def live_samples(density, rays_ndc, thr, rays_pts=None, rays_dir=None):
@@ -1043,16 +1049,8 @@ def live_samples(density, rays_ndc, thr, rays_pts=None, rays_dir=None):
     thr = _thr_f32(thr, "live_samples")
     if density.dim() != 3:
         raise RuntimeError(f"live_samples: density must be (D,H,W), got {tuple(density.shape)}")
-    if rays_ndc.dim() != 3 or rays_ndc.shape[-1] != 3:
-        raise RuntimeError(f"live_samples: rays_ndc must be (N,S,3), got {tuple(rays_ndc.shape)}")
-    N, S = int(rays_ndc.shape[0]), int(rays_ndc.shape[1])
+    N, S = _ray_batch(rays_ndc, rays_pts, rays_dir, None, "live_samples")
     P = N * S
-    if rays_pts is not None and tuple(rays_pts.shape) != (N, S, 3):
-        raise RuntimeError(f"live_samples: rays_pts must be ({N},{S},3), got {tuple(rays_pts.shape)}")
-    if rays_dir is not None and tuple(rays_dir.shape) != (N, 3):
-        raise RuntimeError(f"live_samples: rays_dir must be ({N},3), got {tuple(rays_dir.shape)}")
-    if S < 1 or P >= 2 ** 31:
-        raise RuntimeError(f"live_samples: {N} x {S} samples: S >= 1 and fewer than 2^31 samples (idx is int32)")
     lib = _lib.lib()
     dev = rays_ndc.device
     D, H, W = density.shape
@@ -1068,6 +1066,11 @@ def live_samples(density, rays_ndc, thr, rays_pts=None, rays_dir=None):
     return (count, idx, *rows)
 
 
+def _need_row_index(idx, count, op):
+    if not (idx.dtype == torch.int32 and idx.is_cuda and idx.is_contiguous() and count.dtype == torch.int32 and count.is_cuda and count.numel() == 1):
+        raise RuntimeError(f"{op}: idx and count are the int32 device tensors of ops.live_samples / ops.live_samples_range")
+
+
 def expand_rows(src, idx, count, P, out=None):
     """dst (P,C) with dst[idx[j]] = src[j] for j < count and every other row zero (mvsnerf_expand_rows_fwd): src (n,C) fp32, idx / count as
     ops.live_samples returns them (count is read on the device and clamped to n).  Every element of dst is written, whatever it held
@@ -1077,8 +1080,7 @@ def expand_rows(src, idx, count, P, out=None):
         raise RuntimeError(f"expand_rows: src must be (n,C), got {tuple(src.shape)}")
     n, C = int(src.shape[0]), int(src.shape[1])
     P = int(P)
-    if not (idx.dtype == torch.int32 and idx.is_cuda and idx.is_contiguous() and count.dtype == torch.int32 and count.is_cuda and count.numel() == 1):
-        raise RuntimeError("expand_rows: idx and count are the int32 device tensors of ops.live_samples")
+    _need_row_index(idx, count, "expand_rows")
     if n > P or idx.numel() < n:
         raise RuntimeError(f"expand_rows: {n} source rows, {idx.numel()} indices, {P} destination rows")
     c = _Keep()
@@ -1100,8 +1102,7 @@ def compact_rows(src, idx, count, n_rows, out=None):
         raise RuntimeError(f"compact_rows: src must be (P,C), got {tuple(src.shape)}")
     P, C = int(src.shape[0]), int(src.shape[1])
     n = int(n_rows)
-    if not (idx.dtype == torch.int32 and idx.is_cuda and idx.is_contiguous() and count.dtype == torch.int32 and count.is_cuda and count.numel() == 1):
-        raise RuntimeError("compact_rows: idx and count are the int32 device tensors of ops.live_samples")
+    _need_row_index(idx, count, "compact_rows")
     if n < 0 or n > P or idx.numel() < n:
         raise RuntimeError(f"compact_rows: {P} source rows, {idx.numel()} indices, {n} destination rows")
     c = _Keep()
@@ -1114,51 +1115,59 @@ def compact_rows(src, idx, count, n_rows, out=None):
     return dst
 
 
-def _sparse_march(vol_cl, imgs, w2cs, intrinsics, rays_pts, rays_ndc, z_vals, rays_dir, density, thr, white_bkgd, mlp):
+def _sparse_march(vol_cl, imgs, w2cs, intrinsics, rays_pts, rays_ndc, z_vals, rays_dir, density, thr, white_bkgd, mlp, device_count=False):
     """The sparse ray march both faces run (ops.raymarch_sparse, SparseRayMarchFunction.forward): live_samples of `density` at `thr` -> ONE host read
     of the count (the only synchronisation; at 0 neither a gather nor an MLP launch is enqueued and raw_c is empty) -> ops.gather (ops.gather_colorvol
     for an (8+4V)-channel colour volume, which needs no imgs / intrinsics / rays_pts) on the compact rows as (n_live,1,3) -> the MLP stage with
     N = n_live, S = 1: mlp(ndc_l (n_live,3), feat (n_live,1,F), dirs (n_live,3), n_live) -> raw_c (n_live,4) -> expand_rows into raw (N,S,4) ->
     ops.composite (mvsnerf_composite_fwd).  Dead samples have raw = (0,0,0,0), so alpha = weight = 0; live ones the bits of the dense sequence (a
     sample's MLP column does not depend on its neighbours in the tile).
+    device_count=True: no host read - the count goes to _compact_rows_mlp as the device tensor, the rows are the worst-case N*S, mlp
+    is called with count= and n_live is the int32 device scalar.
     Returns (idx, count, ndc_l, raw_c, raw, n_live) - what a backward has to keep - and ops.composite's (rgb_map, disp, acc, weights, depth, alpha)."""
     N, S = z_vals.shape
     color_vol = vol_cl.shape[-1] != 8
     count, idx, ndc_c, pts_c, dir_c = live_samples(density, rays_ndc, thr, None if color_vol else rays_pts, rays_dir)
-    n_live = int(count.item())
-    ndc_l, raw_c = _compact_rows_mlp(vol_cl, imgs, w2cs, intrinsics, ndc_c, pts_c, dir_c, n_live, mlp)
+    n_live = count.reshape(()) if device_count else int(count.item())
+    ndc_l, raw_c = _compact_rows_mlp(vol_cl, imgs, w2cs, intrinsics, ndc_c, pts_c, dir_c, count if device_count else n_live, mlp)
     raw = expand_rows(raw_c, idx, count, N * S).view(N, S, 4)
     return (idx, count, ndc_l, raw_c, raw, n_live), composite(raw, z_vals, white_bkgd)
 
 
 def _compact_rows_mlp(vol_cl, imgs, w2cs, intrinsics, ndc_c, pts_c, dir_c, n, mlp):
-    """The gather-and-MLP stage of the compacted marches (_sparse_march, raymarch_early_stop) on the first n compact rows of ops.live_samples /
-    ops.live_samples_range: ops.gather (ops.gather_colorvol for a colour volume) on the rows as (n,1,3) -> mlp(ndc_l, feat, dirs, n).  n == 0 enqueues
-    nothing.  Returns (ndc_l (n,3), raw_c (n,4))."""
-    ndc_l = ndc_c[:n]
-    if not n:
+    """The gather-and-MLP stage of the compacted marches (_sparse_march, raymarch_early_stop) on the compact rows of ops.live_samples /
+    ops.live_samples_range: ops.gather (ops.gather_colorvol for a colour volume) on the rows as (rows,1,3) -> mlp(ndc_l, feat, dirs, rows).
+    n a host integer: the first n rows, and n == 0 enqueues nothing.  n the (1,) int32 device count: the worst-case buffers whole, the
+    counted gather and mlp(..., count=n), both enqueued whatever the count holds - rows [0, count) of raw_c are written; a capacity of 0 rows enqueues
+    nothing.  Returns (ndc_l (rows,3), raw_c (rows,4))."""
+    if torch.is_tensor(n):
+        rows, take, kw = ndc_c.shape[0], (lambda t: t), {"count": n}
+    else:
+        rows, take, kw = n, (lambda t: t[:n]), {}
+    ndc_l = take(ndc_c)
+    if not rows:
         return ndc_l, torch.empty((0, 4), device=ndc_c.device, dtype=torch.float32)
-    ndc_g, dir_l = ndc_l.view(n, 1, 3), dir_c[:n]
+    ndc_g, dir_l = ndc_l.view(rows, 1, 3), take(dir_c)
     if vol_cl.shape[-1] != 8:
-        feat, dirs = gather_colorvol(vol_cl, ndc_g, dir_l, w2cs[0].contiguous())
+        feat, dirs = gather_colorvol(vol_cl, ndc_g, dir_l, w2cs[0].contiguous(), **kw)
     else:
-        feat, dirs = gather(vol_cl, imgs, w2cs, intrinsics, pts_c[:n].view(n, 1, 3), ndc_g, dir_l)
-    return ndc_l, mlp(ndc_l, feat, dirs, n)
+        feat, dirs = gather(vol_cl, imgs, w2cs, intrinsics, take(pts_c).view(rows, 1, 3), ndc_g, dir_l, **kw)
+    return ndc_l, mlp(ndc_l, feat, dirs, rows, **kw)
 
 
-def _compact_rows_mlp_counted(vol_cl, imgs, w2cs, intrinsics, ndc_c, pts_c, dir_c, count, mlp):
-    """_compact_rows_mlp without the host: the counted gather and the counted MLP stage on the worst-case buffers of ops.live_samples /
-    ops.live_samples_range, both enqueued whatever `count` holds: mlp(ndc_c (cap,3), feat (cap,1,F), dirs (cap,3), cap) -> raw_c (cap,4), of which
-    rows [0, count) are written.  A capacity of 0 rows enqueues nothing."""
-    cap = ndc_c.shape[0]
-    if not cap:
-        return torch.empty((0, 4), device=ndc_c.device, dtype=torch.float32)
-    ndc_g = ndc_c.view(cap, 1, 3)
-    if vol_cl.shape[-1] != 8:
-        feat, dirs = gather_colorvol(vol_cl, ndc_g, dir_c, w2cs[0].contiguous(), count=count)
-    else:
-        feat, dirs = gather(vol_cl, imgs, w2cs, intrinsics, pts_c.view(cap, 1, 3), ndc_g, dir_c, count=count)
-    return mlp(ndc_c, feat, dirs, cap)
+def _rows_mlp(packed, F, dev, **packed_alt):
+    """ops.mlp_forward as the MLP stage of _compact_rows_mlp: (ndc_l (n,3), feat (n,1,F), dirs (n,3), n[, count=]) -> raw_c (n,4), N = n, S = 1."""
+    return lambda ndc_l, feat, dirs, n, count=None: mlp_forward(packed, F, ndc_l.data_ptr(), 3, feat.data_ptr(), F, dirs.data_ptr(), 3, n, 1, 0, dev,
+                                                                count=count, **packed_alt)
+
+
+def _march_outputs(raw, composited, want, **extras):
+    """The dict a compacted march returns: raw, ops.composite's maps (disp / acc when in `want`), then the counts."""
+    rgb, disp, acc, weights, depth, alpha = composited
+    out = {"raw": raw, "rgb_map": rgb, "weights": weights, "depth": depth, "alpha": alpha}
+    out.update({k: v for k, v in (("disp", disp), ("acc", acc)) if k in want})
+    out.update(extras)
+    return out
 
 
 def raymarch_sparse(vol_cl, imgs, w2cs, intrinsics, packed, rays_pts, rays_ndc, z_vals, rays_dir, density, thr, white_bkgd=False, want=(),
@@ -1177,24 +1186,9 @@ def raymarch_sparse(vol_cl, imgs, w2cs, intrinsics, packed, rays_pts, rays_ndc, 
     F = C if C != 8 else 8 + 4 * imgs.shape[0]
     if C != 8 and C != 8 + 4 * w2cs.shape[0]:
         raise RuntimeError(f"raymarch_sparse: the volume has {C} channels, 8 + 4V is {8 + 4 * w2cs.shape[0]}")
-    if device_count:
-        N, S = z_vals.shape
-        dev = rays_ndc.device
-        count, idx, ndc_c, pts_c, dir_c = live_samples(density, rays_ndc, thr, None if C != 8 else rays_pts, rays_dir)
-        raw_c = _compact_rows_mlp_counted(
-            vol_cl, imgs, w2cs, intrinsics, ndc_c, pts_c, dir_c, count,
-            lambda ndc_l, feat, dirs, cap: mlp_forward(packed, F, ndc_l.data_ptr(), 3, feat.data_ptr(), F, dirs.data_ptr(), 3, cap, 1, 0, dev, count=count, **packed_alt))
-        raw = expand_rows(raw_c, idx, count, N * S).view(N, S, 4)
-        rgb, disp, acc, weights, depth, alpha = composite(raw, z_vals, white_bkgd)
-        out = {"raw": raw, "rgb_map": rgb, "weights": weights, "depth": depth, "alpha": alpha, "n_live": count.reshape(())}
-        out.update({k: v for k, v in (("disp", disp), ("acc", acc)) if k in want})
-        return out
-    (_, _, _, _, raw, n_live), (rgb, disp, acc, weights, depth, alpha) = _sparse_march(
-        vol_cl, imgs, w2cs, intrinsics, rays_pts, rays_ndc, z_vals, rays_dir, density, thr, white_bkgd,
-        lambda ndc_l, feat, dirs, n: mlp_forward(packed, F, ndc_l.data_ptr(), 3, feat.data_ptr(), F, dirs.data_ptr(), 3, n, 1, 0, rays_ndc.device, **packed_alt))
-    out = {"raw": raw, "rgb_map": rgb, "weights": weights, "depth": depth, "alpha": alpha, "n_live": n_live}
-    out.update({k: v for k, v in (("disp", disp), ("acc", acc)) if k in want})
-    return out
+    (_, _, _, _, raw, n_live), composited = _sparse_march(vol_cl, imgs, w2cs, intrinsics, rays_pts, rays_ndc, z_vals, rays_dir, density, thr, white_bkgd,
+                                                          _rows_mlp(packed, F, rays_ndc.device, **packed_alt), device_count)
+    return _march_outputs(raw, composited, want, n_live=n_live)
 
 
 # ------------------------------------------------------------------ early ray termination (csrc/sparse.hip)
@@ -1240,17 +1234,7 @@ def live_samples_range(density, rays_ndc, thr, s0, s1, ray_T=None, eps=0.0, rays
         raise ValueError("live_samples_range: eps is NaN")
     if density is not None and density.dim() != 3:
         raise RuntimeError(f"live_samples_range: density must be (D,H,W), got {tuple(density.shape)}")
-    if rays_ndc.dim() != 3 or rays_ndc.shape[-1] != 3:
-        raise RuntimeError(f"live_samples_range: rays_ndc must be (N,S,3), got {tuple(rays_ndc.shape)}")
-    N, S = int(rays_ndc.shape[0]), int(rays_ndc.shape[1])
-    if rays_pts is not None and tuple(rays_pts.shape) != (N, S, 3):
-        raise RuntimeError(f"live_samples_range: rays_pts must be ({N},{S},3), got {tuple(rays_pts.shape)}")
-    if rays_dir is not None and tuple(rays_dir.shape) != (N, 3):
-        raise RuntimeError(f"live_samples_range: rays_dir must be ({N},3), got {tuple(rays_dir.shape)}")
-    if ray_T is not None and tuple(ray_T.shape) != (N,):
-        raise RuntimeError(f"live_samples_range: ray_T must be ({N},), got {tuple(ray_T.shape)}")
-    if S < 1 or N * S >= 2 ** 31:
-        raise RuntimeError(f"live_samples_range: {N} x {S} samples: S >= 1 and fewer than 2^31 samples (idx is int32)")
+    N, S = _ray_batch(rays_ndc, rays_pts, rays_dir, ray_T, "live_samples_range")
     s0, s1 = _window(S, s0, s1, "live_samples_range")
     lib = _lib.lib()
     dev = rays_ndc.device
@@ -1275,8 +1259,7 @@ def scatter_rows(src, idx, count, dst):
     if src.dim() != 2 or dst.dim() != 2 or src.shape[1] != dst.shape[1] or not dst.is_contiguous():
         raise RuntimeError(f"scatter_rows: src must be (n,C) and dst a contiguous (P,C), got {tuple(src.shape)} and {tuple(dst.shape)}")
     n, C, P = int(src.shape[0]), int(src.shape[1]), int(dst.shape[0])
-    if not (idx.dtype == torch.int32 and idx.is_cuda and idx.is_contiguous() and count.dtype == torch.int32 and count.is_cuda and count.numel() == 1):
-        raise RuntimeError("scatter_rows: idx and count are the int32 device tensors of ops.live_samples_range")
+    _need_row_index(idx, count, "scatter_rows")
     if n > P or idx.numel() < n:
         raise RuntimeError(f"scatter_rows: {n} source rows, {idx.numel()} indices, {P} destination rows")
     if n:
@@ -1317,44 +1300,31 @@ def raymarch_early_stop(vol_cl, imgs, w2cs, intrinsics, packed, rays_pts, rays_n
         raise RuntimeError(f"raymarch_early_stop: the volume has {C} channels, 8 + 4V is {8 + 4 * w2cs.shape[0]}")
     N, S = z_vals.shape
     dev = rays_ndc.device
-    mlp = lambda ndc_l, feat, dirs, n: mlp_forward(packed, F, ndc_l.data_ptr(), 3, feat.data_ptr(), F, dirs.data_ptr(), 3, n, 1, 0, dev, **packed_alt)
+    mlp = _rows_mlp(packed, F, dev, **packed_alt)
     raw = torch.zeros((N, S, 4), device=dev, dtype=torch.float32)
     bounds = list(range(0, S, G)) + [S]
     ray_T = torch.ones((N,), device=dev, dtype=torch.float32) if len(bounds) > 2 else None
-    if device_count:
-        n_live = torch.zeros((), device=dev, dtype=torch.int32)
-        for k, (s0, s1) in enumerate(zip(bounds[:-1], bounds[1:])):
-            count, idx, ndc_c, pts_c, dir_c = live_samples_range(density, rays_ndc, thr, s0, s1, ray_T if k else None, eps,
-                                                                 None if color_vol else rays_pts, rays_dir)
-            n_live = n_live + count[0]
-            raw_c = _compact_rows_mlp_counted(
-                vol_cl, imgs, w2cs, intrinsics, ndc_c, pts_c, dir_c, count,
-                lambda ndc_l, feat, dirs, cap: mlp_forward(packed, F, ndc_l.data_ptr(), 3, feat.data_ptr(), F, dirs.data_ptr(), 3, cap, 1, 0, dev, count=count, **packed_alt))
-            scatter_rows(raw_c, idx, count, raw.view(N * S, 4))
-            if s1 < S:
-                ray_transmittance(raw, s0, s1, ray_T)
-        n_stopped = torch.zeros((), device=dev, dtype=torch.int32) if ray_T is None else (ray_T < eps).sum(dtype=torch.int32)
-        rgb, disp, acc, weights, depth, alpha = composite(raw, z_vals, white_bkgd)
-        out = {"raw": raw, "rgb_map": rgb, "weights": weights, "depth": depth, "alpha": alpha, "n_live": n_live, "n_stopped": n_stopped}
-        out.update({k: v for k, v in (("disp", disp), ("acc", acc)) if k in want})
-        return out
-    n_live, n_stopped = 0, 0
+    # the two modes differ in how a segment's count reaches the stage and in how the counts are summed: Python ints read from the device, or int32
+    # device scalars
+    n_live, n_stopped = (torch.zeros((), device=dev, dtype=torch.int32) if device_count else 0), 0
     for k, (s0, s1) in enumerate(zip(bounds[:-1], bounds[1:])):
         count, idx, ndc_c, pts_c, dir_c = live_samples_range(density, rays_ndc, thr, s0, s1, ray_T if k else None, eps,
                                                              None if color_vol else rays_pts, rays_dir)
-        if s1 == S and ray_T is not None:           # the last segment: the stopped rays travel with its count, one host read
-            n, n_stopped = torch.stack((count[0], (ray_T < eps).sum(dtype=torch.int32))).tolist()
+        if device_count:
+            n, n_live = count, n_live + count[0]
         else:
-            n = int(count.item())
-        n_live += n
+            if s1 == S and ray_T is not None:       # the last segment: the stopped rays travel with its count, one host read
+                n, n_stopped = torch.stack((count[0], (ray_T < eps).sum(dtype=torch.int32))).tolist()
+            else:
+                n = int(count.item())
+            n_live += n
         _, raw_c = _compact_rows_mlp(vol_cl, imgs, w2cs, intrinsics, ndc_c, pts_c, dir_c, n, mlp)
         scatter_rows(raw_c, idx, count, raw.view(N * S, 4))
         if s1 < S:
             ray_transmittance(raw, s0, s1, ray_T)
-    rgb, disp, acc, weights, depth, alpha = composite(raw, z_vals, white_bkgd)
-    out = {"raw": raw, "rgb_map": rgb, "weights": weights, "depth": depth, "alpha": alpha, "n_live": n_live, "n_stopped": n_stopped}
-    out.update({k: v for k, v in (("disp", disp), ("acc", acc)) if k in want})
-    return out
+    if device_count:
+        n_stopped = torch.zeros((), device=dev, dtype=torch.int32) if ray_T is None else (ray_T < eps).sum(dtype=torch.int32)
+    return _march_outputs(raw, composite(raw, z_vals, white_bkgd), want, n_live=n_live, n_stopped=n_stopped)
 
 
 # ------------------------------------------------------------------ a density volume in the renderer's frame (csrc/occupancy.hip)
@@ -2020,14 +1990,9 @@ def frame_u8(rgb, depth=None, minmax=None, lut=None, crop=(0, 0), out=None):
 
 # ------------------------------------------------------------------ depth maps -> point cloud (csrc/depth_fusion.hip)
 def _fusion_bank(images, c2ws, intrinsics, op):
-    if not (torch.is_tensor(images) and images.is_cuda and images.dtype == torch.uint8 and images.dim() == 4 and images.shape[-1] == 4
-            and images.is_contiguous()):
-        raise RuntimeError(f"{op}: images must be a contiguous (M,H,W,4) uint8 tensor on the GPU (SceneRays.images)")
-    M, H, W = (int(v) for v in images.shape[:3])
+    M, H, W = _bank_images(images, op)
     if tuple(c2ws.shape) != (M, 3, 4) or tuple(intrinsics.shape) != (M, 3, 3):
         raise RuntimeError(f"{op}: c2ws ({M},3,4) and intrinsics ({M},3,3) expected, got {tuple(c2ws.shape)}, {tuple(intrinsics.shape)}")
-    if images.device.index != torch.cuda.current_device():
-        raise RuntimeError(f"{op}: the bank is on {images.device} but the current device is cuda:{torch.cuda.current_device()}")
     return M, H, W
 
 
@@ -2106,6 +2071,14 @@ def point_cloud(images, c2ws, intrinsics, fused, seen, mask, capacity, out=None)
 MESH_MAX_NODES = 1 << 27
 
 
+def _box6(box, op):
+    """(lo, hi) of a world box, 2 x 3 numbers read on the host, as the float[6] the C entries take."""
+    vals = [float(v) for v in torch.as_tensor(box, dtype=torch.float32).reshape(-1).tolist()]
+    if len(vals) != 6:
+        raise RuntimeError(f"{op}: box must hold (lo, hi), 2 x 3 numbers")
+    return (ctypes.c_float * 6)(*vals)
+
+
 def mesh_extract(field, level, positions=None, box=None, capacity=None, valid=None):
     """Marching tetrahedra over the Kuhn split of the cells of field (D,H,W) fp32 (mvsnerf_mesh_extract_fwd; the definition is in DESIGN.md 4n and
     include/mvsnerf_hip_internal.h) -> (vertices (V,3) fp32, ndc (V,3) fp32, vertex_edge (V,) int64, faces (T,3) int32, count (2,) int64 on the device).
@@ -2128,12 +2101,7 @@ def mesh_extract(field, level, positions=None, box=None, capacity=None, valid=No
             raise RuntimeError(f"{op}: positions must be ({D},{H},{W},3), got {tuple(positions.shape)}")
         p_pos = dev_f32(positions, f"{op}: positions")
     p_valid = 0 if valid is None else _fusion_map(valid, torch.uint8, (D, H, W), dev, "valid", op)
-    c_box = None
-    if box is not None:
-        vals = [float(v) for v in torch.as_tensor(box, dtype=torch.float32).reshape(-1).tolist()]
-        if len(vals) != 6:
-            raise RuntimeError(f"{op}: box must hold (lo, hi), 2 x 3 numbers")
-        c_box = (ctypes.c_float * 6)(*vals)
+    c_box = None if box is None else _box6(box, op)
     lib = _lib.lib()
     ws_bytes = int(lib.mvsnerf_mesh_workspace_bytes(D, H, W))
     if ws_bytes == 0:
@@ -2194,27 +2162,16 @@ def tsdf_integrate(images, w2cs, intrinsics, depths, box, dims, trunc, valid=Non
     node, no atomics, every output element written."""
     op = "tsdf_integrate"
     _need_no_grad(depths, w2cs, intrinsics, op=op)
-    if not (torch.is_tensor(images) and images.is_cuda and images.dtype == torch.uint8 and images.dim() == 4 and images.shape[-1] == 4
-            and images.is_contiguous()):
-        raise RuntimeError(f"{op}: images must be a contiguous (M,H,W,4) uint8 tensor on the GPU (SceneRays.images)")
-    M, H, W = (int(v) for v in images.shape[:3])
+    M, H, W = _bank_images(images, op)
     dev = images.device
-    if dev.index != torch.cuda.current_device():
-        raise RuntimeError(f"{op}: the bank is on {dev} but the current device is cuda:{torch.cuda.current_device()}")
     if tuple(w2cs.shape) != (M, 3, 4) or tuple(intrinsics.shape) != (M, 3, 3):
         raise RuntimeError(f"{op}: w2cs ({M},3,4) and intrinsics ({M},3,3) expected, got {tuple(w2cs.shape)}, {tuple(intrinsics.shape)}")
     p_depth = _fusion_map(depths, torch.float32, (M, H, W), dev, "depths", op)
     p_valid = 0 if valid is None else _fusion_map(valid, torch.uint8, (M, H, W), dev, "valid", op)
-    p_views, n_views = 0, M
-    if views is not None:
-        if not (torch.is_tensor(views) and views.dim() == 1 and views.numel() >= 1):
-            raise RuntimeError(f"{op}: views must be a 1-D tensor of at least one view id")
-        n_views = int(views.numel())
-        p_views = _fusion_map(views, torch.int32, (n_views,), dev, "views", op)
-    vals = [float(v) for v in torch.as_tensor(box, dtype=torch.float32).reshape(-1).tolist()]
-    if len(vals) != 6:
-        raise RuntimeError(f"{op}: box must hold (lo, hi), 2 x 3 numbers")
-    c_box = (ctypes.c_float * 6)(*vals)
+    p_views, n_views = _view_list(views, dev, op)
+    if views is None:
+        n_views = M
+    c_box = _box6(box, op)
     D, Hn, Wn = (int(v) for v in dims)
     if min(D, Hn, Wn) < 2 or D * Hn * Wn > MESH_MAX_NODES:
         raise RuntimeError(f"{op}: a ({D},{Hn},{Wn}) grid is outside what the kernels index (every dimension >= 2, at most 2^27 nodes)")
@@ -2357,13 +2314,8 @@ def mesh_sample(vertices, faces, spacing, capacity=None, mesh_count=None):
     mesh_count: the (2,) int64 device counts of a mesh extracted with a capacity: rows past them are not read."""
     op = "mesh_sample"
     _need_no_grad(vertices, op=op)
-    V, p_v = _cloud_rows(vertices, "vertices", op)
+    V, p_v, T, p_f, p_mc = _mesh_rows(vertices, faces, mesh_count, op)
     dev = vertices.device
-    if not (torch.is_tensor(faces) and faces.dim() == 2 and faces.shape[1] == 3):
-        raise RuntimeError(f"{op}: faces must be a (T,3) tensor, got {tuple(getattr(faces, 'shape', ()))}")
-    T = int(faces.shape[0])
-    p_f = _fusion_map(faces, torch.int32, (T, 3), dev, "faces", op) if T else 0
-    p_mc = 0 if mesh_count is None else _fusion_map(mesh_count, torch.int64, (2,), dev, "mesh_count", op)
     lib = _lib.lib()
     ws_bytes = int(lib.mvsnerf_mesh_sample_workspace_bytes(T))
     if ws_bytes == 0:

@@ -71,6 +71,26 @@ def test_library_builds_and_exports_header_symbols():
     assert _lib.lib().mvsnerf_mlp_packed_floats(21) == 0
 
 
+def test_render_workspace_sizes():
+    """The float counts of the two whole-frame workspaces: blocks pts, ndc (3P each), z (P), coarse z (B*S, importance sampling only), feat (F*P),
+    raw (4P), rays_dir and dirs (3B each), every block rounded up to 16 bytes; P = B * (S + NI), and render_pixels is NI = 0, F = 8 + 4V."""
+    lib = _lib.lib()
+    r4 = lambda n: (n + 3) // 4 * 4
+    for B in (1, 3, 512):
+        for S in (1, 5, 128):
+            for V in (1, 3, 8):
+                F = 8 + 4 * V
+                assert lib.mvsnerf_render_workspace_floats(B, S, V) == 2 * r4(3 * B * S) + r4(B * S) + r4(F * B * S) + r4(4 * B * S) + 2 * r4(3 * B)
+                for NI in (0, 3):
+                    P = B * (S + NI)
+                    assert lib.mvsnerf_render_rays_workspace_floats(B, S, NI, F) == (2 * r4(3 * P) + r4(P) + (r4(B * S) if NI > 0 else 0) + r4(F * P)
+                                                                                     + r4(4 * P) + 2 * r4(3 * B)), (B, S, NI, F)
+    for bad in ((0, 5, 3), (3, 0, 3), (3, 5, 0), (-1, 5, 3)):
+        assert lib.mvsnerf_render_workspace_floats(*bad) == 0, bad
+    for bad in ((0, 5, 0, 20), (3, 0, 0, 20), (3, 5, -1, 20), (3, 5, 0, 8), (3, 5, 0, 22), (3, 5, 3, 18)):
+        assert lib.mvsnerf_render_rays_workspace_floats(*bad) == 0, bad
+
+
 def test_only_gfx950_code_objects():
     out = subprocess.run(["/opt/rocm/lib/llvm/bin/clang-offload-bundler", "--list", "--type=o", f"--input={_lib.LIB_PATH}"],
                          capture_output=True, text=True).stdout
