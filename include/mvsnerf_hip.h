@@ -18,7 +18,7 @@
  *   - plain pointers + sizes, no torch types.  Every pointer is a DEVICE pointer (fp32 unless noted)
  *     owned by the caller; outputs are caller-allocated and fully written.  The library allocates
  *     nothing and has no behavioural state: its only process-global data are per-device "dynamic-LDS cap already
- *     raised" bits (idempotent).  (Which kernel family a dispatcher picks is a compile-time constant, csrc/knobs.h; only the entry points declared in the two headers are exported, csrc/exports.map.)
+ *     raised" bits (idempotent).  (Which kernel a shape takes is written in its dispatcher, nothing is switchable; only the entry points declared in the two headers are exported, csrc/exports.map.)
  *   - `stream` is a hipStream_t passed as void* (NULL = default stream).  Calls only enqueue work.
  *   - return 0 on success, a negative MVSNERF_E* for rejected arguments (nothing was launched),
  *     or a positive hipError_t from the launch.

@@ -1,10 +1,13 @@
-// Lazily-activated operands shared by the 3-D (encoder.hip) and 2-D (featnet.hip) convolution kernels.
+// Lazily-activated operands shared by the 3-D (conv3d.hip, abn.hip, wgrad3d.hip) and 2-D (featnet.hip) convolution kernels.
 #pragma once
 #include "common.h"
 
 // lazily-activated operand: value = leaky(x*scale[c]+shift[c]) (scale == null: identity, no activation),
 // optionally + a second such tensor (the U-Net skip sums).
 struct ActSrc { const float* x; const float* scale; const float* shift; };
+
+// what an entry accepts as such an operand: a 16-byte aligned tensor, scale and shift both present or both NULL
+static inline bool act_ok(const float* x, const float* sc, const float* sh) { return x && ((sc == nullptr) == (sh == nullptr)) && mvs_aligned16(x); }
 
 __device__ __forceinline__ float act_apply(float x, float sc, float sh) { const float y = fmaf(x, sc, sh); return y > 0.f ? y : 0.01f * y; }
 

@@ -96,3 +96,6 @@ __device__ __forceinline__ int xcd_contiguous_tile(int bid, int nb)
     const int xcd = bid & 7, idx = bid >> 3;
     return xcd * per + (xcd < rem ? xcd : rem) + idx;
 }
+// What every launch site hands to the `swz` / `xcd` argument of those kernels: the renumbering is on.  (The argument is the kernels' own;
+// folding it into them would change their code.)
+constexpr int MVS_XCD_CONTIGUOUS = 1;

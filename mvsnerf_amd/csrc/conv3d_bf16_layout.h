@@ -1,4 +1,4 @@
-// Fragment layout of the bf16 weight buffers of conv3d_bf16.hip, shared with the multi-job weight pack of encoder.hip (kinds 3 / 4).
+// Fragment layout of the bf16 weight buffers of conv3d_bf16.hip, shared with the multi-job weight pack of conv3d.hip (kinds 3 / 4).
 #pragma once
 #include "common.h"
 

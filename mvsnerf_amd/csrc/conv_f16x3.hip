@@ -2,7 +2,7 @@
 // the fp16 matrix cores: the two-piece operand split of mlp_f16x3.hip applied to the encoder's largest layer.  conv0 of every no-grad encode
 // (`encoder.ENCODER_PRECISION = "auto"`) as a GUARDED sequence: a cost value or weight outside fp16's range sets the guard word and the fp32
 // plane sweep + fp32-MFMA conv0 of conv_mfma.hip, enqueued behind this kernel and predicated on that word, recompute the layer
-// (mvsnerf_sweep_conv0_guarded_fwd, encoder.hip).  `encoder_precision("fp16x3")` is the unguarded pair (saturating); gradients take fp32 kernels.
+// (mvsnerf_sweep_conv0_guarded_fwd, guarded.hip).  `encoder_precision("fp16x3")` is the unguarded pair (saturating); gradients take fp32 kernels.
 //
 //     x = x0 + x1 (+ 2^-22 |x|),  x0 = fp16(x), x1 = fp16(x - x0);   w likewise;      x * w ~= x0*w0 + x0*w1 + x1*w0      (dropped: x1*w1 <= 2^-22 |x w|)
 //
@@ -21,13 +21,14 @@
 // dy = 1 taps of an input row share one MFMA through the two halves of the 16 B columns (see the accumulator comment in the kernel).
 #include "common.h"
 #include "act.h"
+#include "conv.h"
 #include "lds_dma.h"
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 namespace {
 
-constexpr int W_SCALE_LOG2 = 4;                                  // weights * 2^4 <-> cost volume * 2^-4 (encoder.hip, blocked mode 3)
+constexpr int W_SCALE_LOG2 = 4;                                  // weights * 2^4 <-> cost volume * 2^-4 (planesweep.hip, blocked mode 3)
 
 __device__ const f32x4 g_zero16h = {0.0f, 0.0f, 0.0f, 0.0f};     // what a DMA lane reads for a voxel outside the volume (zero padding)
 

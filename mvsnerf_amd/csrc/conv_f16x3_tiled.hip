@@ -6,13 +6,14 @@
 //     x = x0 + x1,  x0 = fp16(x 2^4), x1 = fp16(x 2^4 - x0);   w likewise with 2^8;   x w 2^12 ~= x1 w0 + x0 w1 + x0 w0   (dropped: x1 w1 <= 2^-22 |x w|)
 // three v_mfma_f32_16x16x32_f16 per product, fp32 accumulation, the power-of-two scales taken out of the accumulator exactly.  The scales keep the SECOND
 // pieces of ordinary activations (|x| ~ 1e-3 .. 50 after InPlaceABN) and weights (~1e-2 .. 1) out of fp16's subnormals.  Range: |x| < 4094, |w| < 255; a value
-// beyond becomes inf, every output it touches NaN, and the NaN partial sums set *guard: mvsnerf_conv3d_f16x3_guarded_fwd (encoder.hip) enqueues the fp32 kernel
+// beyond becomes inf, every output it touches NaN, and the NaN partial sums set *guard: mvsnerf_conv3d_f16x3_guarded_fwd (guarded.hip) enqueues the fp32 kernel
 // of the layer behind this one, predicated on that word (include/mvsnerf_hip.h, "guarded 16-bit sequences").
 // Measured on the way (scratch/r5_prep/NOTES.md, profiles/r04_r5prep_*): the compiler's own schedule (4 reads, wait, 3 dependent MFMAs per k-step and M-tile) 90 us at
 // conv2; fragments of k-step ks + 1 requested before the MFMAs of ks, the three piece products as three passes over the M-tiles: 78; the tile-independent half of the
 // prefetch addressing hoisted out of the tile loop: 73; 16-wide tiles for rows that are not multiples of 32 voxels (104: 93 % of the M-tile rows used instead of 81 %): 43.
 #include "common.h"
 #include "act.h"
+#include "conv.h"
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));

@@ -22,6 +22,7 @@
 // dependent-accumulator MFMA stream at 53 TFLOP/s; it takes the second wave to fill the matrix pipe.)
 #include "common.h"
 #include "act.h"
+#include "conv.h"
 #include "lds_dma.h"
 
 #ifdef MVS_CONV_DBG
@@ -943,7 +944,7 @@ __global__ __launch_bounds__(256) void convT3d_k3s2_c16to8_mfma4_kernel(ActSrc x
 
 }  // namespace
 
-// Called by mvsnerf_conv3d_fwd (encoder.hip) for the layers with 32 / 64 output channels; MVSNERF_EUNSUPPORTED = not instantiated.
+// Called by mvsnerf_conv3d_fwd (conv3d.hip) for the layers with 32 / 64 output channels; MVSNERF_EUNSUPPORTED = not instantiated.
 // ---------------------------------------------------------------------------------------------------------------------------
 // conv1 (8 -> 16, stride 2; and the data gradient of conv11, the same shape) of CostRegNet (models.py:757) on v_mfma_f32_16x16x4_f32.
 // Measured (profiles/r03_*): 110 us against 109 us for the VALU kernel it replaces - the layer reads 150 MB and is bound by that - but the
@@ -1056,10 +1057,10 @@ int mvs_conv3d_mfma32(const ActSrc& a, const ActSrc& b, int Cin, int cin_ld, int
 // conv11-shaped transposed convolution (16 -> 8) without padded products (mvsnerf_conv_transpose3d_c8_fwd); wq: [ci/4][tap][co][4]
 int mvs_convT3d_c16to8_tiles(int D, int H, int W) { return ((W + CT8_TX - 1) / CT8_TX) * ((H + CT8_TY - 1) / CT8_TY) * ((D + CT8_TZ - 1) / CT8_TZ); }
 
-int mvs_convT3d_c16to8_mfma4(const ActSrc& xa, const ActSrc& xb, int D, int H, int W, const float* wq, float* out, int xcd, float* stats, hipStream_t st)
+int mvs_convT3d_c16to8_mfma4(const ActSrc& xa, const ActSrc& xb, int D, int H, int W, const float* wq, float* out, float* stats, hipStream_t st)
 {
     const unsigned grid = (unsigned)mvs_convT3d_c16to8_tiles(D, H, W);
-    convT3d_k3s2_c16to8_mfma4_kernel<<<grid, 256, 0, st>>>(xa, xb, D, H, W, wq, out, xcd, stats);
+    convT3d_k3s2_c16to8_mfma4_kernel<<<grid, 256, 0, st>>>(xa, xb, D, H, W, wq, out, MVS_XCD_CONTIGUOUS, stats);
     MVS_LAUNCH_CHECK();
     return MVSNERF_OK;
 }
@@ -1133,12 +1134,12 @@ int mvs_conv3d_c8_wgrad4(const float* x4, int Cin, int cin_real, int D, int H, i
 // conv0 on a cost volume in channel blocks of four (mvsnerf_conv3d_c8_blocked_fwd)
 int mvs_conv3d_c8_mfma4_tiles(int D, int H, int W) { return ((W + TX - 1) / TX) * ((H + TY - 1) / TY) * ((D + TZ - 1) / TZ); }
 
-int mvs_conv3d_c8_mfma4(const float* x4, int Cin, int cin_real, int D, int H, int W, const float* wq, float* out, int xcd, float* stats, hipStream_t st,
+int mvs_conv3d_c8_mfma4(const float* x4, int Cin, int cin_real, int D, int H, int W, const float* wq, float* out, float* stats, hipStream_t st,
                         const int* run_if)
 {
     if ((int64_t)D * H * W * 4 >= (int64_t)1 << 31) return MVSNERF_EUNSUPPORTED;
     const unsigned grid = (unsigned)(((W + TX - 1) / TX) * ((H + TY - 1) / TY) * ((D + TZ - 1) / TZ));
-#define MVS_L4(CIN, CREAL) case CIN * 100 + CREAL: conv3d_k3s1_c8_mfma4_kernel<CIN, CREAL><<<grid, 256, 0, st>>>(x4, D, H, W, wq, out, xcd, stats, run_if); break
+#define MVS_L4(CIN, CREAL) case CIN * 100 + CREAL: conv3d_k3s1_c8_mfma4_kernel<CIN, CREAL><<<grid, 256, 0, st>>>(x4, D, H, W, wq, out, MVS_XCD_CONTIGUOUS, stats, run_if); break
     switch (Cin * 100 + cin_real) {
         MVS_L4(32, 32); MVS_L4(36, 35); MVS_L4(40, 38); MVS_L4(44, 41); MVS_L4(44, 44); MVS_L4(48, 47); MVS_L4(52, 50); MVS_L4(56, 53); MVS_L4(56, 56);
         default: return MVSNERF_EUNSUPPORTED;
@@ -1155,19 +1156,19 @@ int mvs_conv_w4_repack(const float* wpacked, float* wq, int Cin, hipStream_t st)
     return MVSNERF_OK;
 }
 
-// Called by mvsnerf_conv3d_fwd (encoder.hip) for stride-1 layers with 8 output channels and a channel-last input.  Cin: padded
+// Called by mvsnerf_conv3d_fwd (conv3d.hip) for stride-1 layers with 8 output channels and a channel-last input.  Cin: padded
 // channel count (multiple of 4), cin_real: how many of them exist (products with the zero padding are skipped).  Returns
 // MVSNERF_EUNSUPPORTED for a channel count it is not instantiated for (the caller then takes the VALU kernel).
 int mvs_conv3d_c8_mfma(const ActSrc& a, const ActSrc& b, int Cin, int cin_real, int cin_ld, int D, int H, int W, const float* wpacked, float* out,
-                       int xcd, hipStream_t st)
+                       hipStream_t st)
 {
     if (b.x) return MVSNERF_EUNSUPPORTED;                         // one lazily-activated source only (conv0's input is the raw cost volume)
     const bool blocked = cin_ld == -8;                            // input in channel blocks of 8: x[(Cin+7)/8][D*H*W][8]
     if ((int64_t)D * H * W * (blocked ? 8 : cin_ld) >= (int64_t)1 << 31) return MVSNERF_EUNSUPPORTED;      // 32-bit element offsets in the staging slots
     const unsigned grid = (unsigned)(((W + TX - 1) / TX) * ((H + TY - 1) / TY) * ((D + TZ - 1) / TZ));
 #define MVS_L(CIN, CREAL) case CIN * 100 + CREAL:                                                                                             \
-        if (blocked) conv3d_k3s1_c8_mfma_kernel<CIN, CREAL, true><<<grid, 256, 0, st>>>(a, cin_ld, D, H, W, wpacked, out, xcd);                \
-        else conv3d_k3s1_c8_mfma_kernel<CIN, CREAL, false><<<grid, 256, 0, st>>>(a, cin_ld, D, H, W, wpacked, out, xcd);                       \
+        if (blocked) conv3d_k3s1_c8_mfma_kernel<CIN, CREAL, true><<<grid, 256, 0, st>>>(a, cin_ld, D, H, W, wpacked, out, MVS_XCD_CONTIGUOUS); \
+        else conv3d_k3s1_c8_mfma_kernel<CIN, CREAL, false><<<grid, 256, 0, st>>>(a, cin_ld, D, H, W, wpacked, out, MVS_XCD_CONTIGUOUS);        \
         break
     if (cin_real <= 0 || cin_real > Cin) cin_real = Cin;
     switch (Cin * 100 + cin_real) {

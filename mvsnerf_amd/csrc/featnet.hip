@@ -1,6 +1,6 @@
 // FeatureNet (reference models.py:688-722) building blocks: 2-D convolutions over a batch of N images, channel-last
 //   act[n][y][x][C]   C in {4 (rgb + pad), 8, 16, 32}
-// with the same lazy InPlaceABN convention as the 3-D U-Net (encoder.hip): a conv writes its RAW output, the
+// with the same lazy InPlaceABN convention as the 3-D U-Net (conv3d.hip): a conv writes its RAW output, the
 // statistics kernel (mvsnerf_abn_stats over N*H*W pixels) turns batch statistics into (scale, shift), and every
 // consumer applies leaky_relu(x*scale+shift) on load.  Kernels here:
 //   conv2d_kernel        k in {1,3,5}, stride in {1,2}, padding k/2; also the data gradient of the stride-1 layers
@@ -12,7 +12,7 @@
 // wave-uniform, are fetched through the scalar cache.
 #include "common.h"
 #include "act.h"
-#include "knobs.h"
+#include "conv.h"
 
 __global__ void conv2d_pack_kernel(const float* __restrict__ w, int ci_real, int co_real, int cin_pad, int cout_pad,
                                    int s_ci, int s_co, int ntaps, int flip, float* __restrict__ packed)
@@ -39,7 +39,7 @@ extern "C" int mvsnerf_conv2d_pack_weights(const float* w, int ci_real, int co_r
 
 // One thread = one output pixel x CT output channels; a workgroup owns a 16x16 pixel tile so that the K*K-fold input
 // reuse is served by L1 (a pixel's channels are one contiguous vector, 16 lanes of a row read one contiguous span).
-template <int CIN, int CT, int K, int S, int COUT>     // COUT a template constant: weight offsets are s_load immediates (see encoder.hip)
+template <int CIN, int CT, int K, int S, int COUT>     // COUT a template constant: weight offsets are s_load immediates (see conv3d.hip)
 __global__ __launch_bounds__(256) void conv2d_kernel(ActSrc a, int ld, int Hi, int Wi, const float* __restrict__ wp,
                                                      const float* __restrict__ bias,
                                                      float* __restrict__ out, int Ho, int Wo, float* __restrict__ stats = nullptr)
@@ -290,8 +290,8 @@ __global__ __launch_bounds__(256) void conv2d_mfma_kernel(ActSrc a, int ld, int 
 static bool conv2d_mfma_shape(int Cin, int Cout, int ksize, int stride)
 {
     const int key = ((Cin * 100 + Cout) * 10 + ksize) * 10 + stride;
-    return g_conv_mfma && (key == ((8 * 100 + 16) * 10 + 5) * 10 + 2 || key == ((16 * 100 + 16) * 10 + 3) * 10 + 1 ||
-                           key == ((16 * 100 + 32) * 10 + 5) * 10 + 2 || key == ((32 * 100 + 32) * 10 + 3) * 10 + 1);
+    return key == ((8 * 100 + 16) * 10 + 5) * 10 + 2 || key == ((16 * 100 + 16) * 10 + 3) * 10 + 1 ||
+           key == ((16 * 100 + 32) * 10 + 5) * 10 + 2 || key == ((32 * 100 + 32) * 10 + 3) * 10 + 1;
 }
 
 // number of M-tiles (= rows of InPlaceABN partial sums) mvsnerf_conv2d_fwd_stats leaves for this layer; 0: the layer has no matrix-core kernel
@@ -513,10 +513,6 @@ __global__ __launch_bounds__(256) void conv2d_wgrad_kernel(const float* __restri
         }
 }
 
-int mvs_conv2d_wgrad_mfma4_parts(int A, int B, int N, int Ho, int Wo, int ksize, int stride, int cap_parts);
-int mvs_conv2d_wgrad_mfma4(const float* g, int A, const ActSrc& x1, int B, int ldx, int N, int Ho, int Wo, int Hi, int Wi, int ksize, int stride,
-                           float* partial, int cap_parts, hipStream_t st);
-
 // >= 64 pixels per workgroup, <= 4096 workgroups over all channel groups (bounds the partials to 32768*B*k*k floats)
 static int wgrad2d_nwg(int64_t npix, int A)
 {
@@ -539,16 +535,14 @@ extern "C" int mvsnerf_conv2d_wgrad(const float* g, int A, const float* x, const
     const int64_t npix = (int64_t)N * Ho * Wo;
     if (npix > 0x7fffffff) return MVSNERF_EUNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
-    if (g_conv_mfma) {                                     // matrix cores (wgrad_mfma.hip) for FeatureNet's eight k3 / k5 layers
-        const int cap = 4096 / (A / 8);
-        const int rc = mvs_conv2d_wgrad_mfma4(g, A, X1, B, ldx, N, Ho, Wo, Hi, Wi, ksize, stride, workspace, cap, st);
-        if (rc != MVSNERF_EUNSUPPORTED) {
-            if (rc != MVSNERF_OK || !gw) return rc;
-            const int64_t n_out = (int64_t)A * B * ksize * ksize;
-            mvs_partial_sum(workspace, mvs_conv2d_wgrad_mfma4_parts(A, B, N, Ho, Wo, ksize, stride, cap), n_out, workspace + (size_t)cap * n_out, gw, st);
-            MVS_LAUNCH_CHECK();
-            return MVSNERF_OK;
-        }
+    const int cap = 4096 / (A / 8);                        // matrix cores (wgrad_mfma.hip) for FeatureNet's eight k3 / k5 layers
+    const int rc = mvs_conv2d_wgrad_mfma4(g, A, X1, B, ldx, N, Ho, Wo, Hi, Wi, ksize, stride, workspace, cap, st);
+    if (rc != MVSNERF_EUNSUPPORTED) {
+        if (rc != MVSNERF_OK || !gw) return rc;
+        const int64_t n_out = (int64_t)A * B * ksize * ksize;
+        mvs_partial_sum(workspace, mvs_conv2d_wgrad_mfma4_parts(A, B, N, Ho, Wo, ksize, stride, cap), n_out, workspace + (size_t)cap * n_out, gw, st);
+        MVS_LAUNCH_CHECK();
+        return MVSNERF_OK;
     }
     const int nwg = wgrad2d_nwg(npix, A);
     const int pairs = ksize * ksize * B;
@@ -577,10 +571,8 @@ extern "C" int mvsnerf_conv2d_wgrad(const float* g, int A, const float* x, const
 extern "C" int mvsnerf_conv2d_wgrad_parts(int A, int B, int N, int Ho, int Wo, int ksize, int stride)
 {
     if (A < 8) return 0;
-    if (g_conv_mfma) {
-        const int n = mvs_conv2d_wgrad_mfma4_parts(A, B, N, Ho, Wo, ksize, stride, 4096 / (A / 8));
-        if (n > 0) return n;
-    }
+    const int n = mvs_conv2d_wgrad_mfma4_parts(A, B, N, Ho, Wo, ksize, stride, 4096 / (A / 8));
+    if (n > 0) return n;
     return wgrad2d_nwg((int64_t)N * Ho * Wo, A);
 }
 

@@ -33,7 +33,10 @@ int mvs_mlp_fwd_counted(const float* packed, int F, const float* ndc, const floa
                         int alpha_only, float* raw, const int* run_if, void* stream);
 int mvs_mlp_f16x3_fwd_counted(const void* packed_h, const float* packed_f32, int F, const float* ndc, const float* feat, const float* dirs,
                               int cap, const int* count, int alpha_only, float* raw, hipStream_t st, int* guard = nullptr);
-// encoder.hip: ends a guarded sequence whose last kernel does not: counts a tripped guard, re-arms it
+// mlp_f16x3.hip: elements and packing of that MLP's weight buffer, behind mvsnerf_mlp_{packed_split_elems, pack_split}(n_split = MVSNERF_SPLIT_FP16)
+size_t mvs_mlp_f16x3_elems(int F);
+int mvs_mlp_f16x3_pack(const float* const w[11], int F, void* packed, hipStream_t st);
+// guarded.hip: ends a guarded sequence whose last kernel does not: counts a tripped guard, re-arms it
 int mvs_guard_consume(int* guard, hipStream_t st);
 // mlp.hip: the one-launch fp32 ray march (raymarch_fused_kernel) and whether it applies to a batch: fp32 MLP, no guard, channel-last images,
 // HWDC volume, pointers present (volume, images, weights, feat and raw 16-byte aligned), F <= MAX_F, N >= 1, 32-bit offsets (gather_fits_32bit).

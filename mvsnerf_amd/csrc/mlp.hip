@@ -14,7 +14,6 @@
 #include "mlp_layout.h"
 #include "lds_dma.h"
 #include "mlp_fp32_dev.h"
-#include "knobs.h"
 #include "sample_dev.h"
 #include "composite_wave.h"
 #include "march.h"

@@ -138,8 +138,3 @@ __device__ __forceinline__ bool stage_features(float (&fv)[MAXV], const float* _
 }
 
 }  // namespace mlp
-
-// mlp_f16x3.hip: the two-piece fp16 split behind mvsnerf_mlp_{packed_split_elems, pack_split, fwd_split}(n_split = MVSNERF_SPLIT_FP16);
-// its forward, mvs_mlp_f16x3_fwd, is declared in march.h
-size_t mvs_mlp_f16x3_elems(int F);
-int mvs_mlp_f16x3_pack(const float* const w[11], int F, void* packed, hipStream_t st);

@@ -12,7 +12,6 @@
 #include "mlp_layout.h"
 #include "mlp_b16_dev.h"
 #include "march.h"
-#include "knobs.h"
 
 using namespace mlp;
 

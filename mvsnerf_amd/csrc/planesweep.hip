@@ -1,5 +1,5 @@
-// Plane-sweep cost volume, forward (utils.py:580-630 homo_warp + models.py:787-893 build_volume_costvar[_img]): the kernels that were part of
-// encoder.hip until round 4, in their own translation unit because this file is compiled with -fno-slp-vectorize (Makefile), i.e. WITHOUT
+// Plane-sweep cost volume, forward (utils.py:580-630 homo_warp + models.py:787-893 build_volume_costvar[_img]): the kernels that shared a
+// file with the rest of the encoder until round 4, in their own translation unit because this file is compiled with -fno-slp-vectorize (Makefile), i.e. WITHOUT
 // packed fp32 instructions (v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32; `make` checks the code object for them).
 //
 // Why (scratch/r4/race_probe2.py, profiles/r04_pk_mfma_hazard.txt): with the SLP vectoriser's packed fp32 arithmetic this kernel computed wrong
@@ -17,10 +17,10 @@
 // FINITE (p2 == 0: +-inf and 0/0; an overflowing T / depth) has FOUR ZERO WEIGHTS: every comparison of the `x0in && ...` selects is false for NaN and inf, so
 // the view adds nothing to the voxel's sums and is not counted, and no address is formed from it (`any ? clamp : 0`).  The CPU reference returns NaN on exactly
 // those voxels; the zero is this project's definition (one NaN voxel would poison CostRegNet's batch statistics), shared by the two backward kernels in
-// encoder.hip, whose geometry blocks must stay equal to phase 1 below.  The stand-alone homo_warp_kernel (encoder.hip) deliberately returns the reference's NaN.
+// planesweep_bwd.hip, whose geometry blocks must stay equal to phase 1 below.  The stand-alone homo_warp_kernel (encoder_prep.hip) deliberately returns the reference's NaN.
 #include "common.h"
 #include "act.h"
-#include "knobs.h"
+#include "conv.h"
 
 // =============================================================================================
 // plane sweep: homo_warp (utils.py:580-630) + build_volume_costvar[_img] (models.py:787-893) in ONE pass.
@@ -343,10 +343,6 @@ __global__ __launch_bounds__(64) void planesweep_if_kernel(
         __syncthreads();
     }
 }
-
-int mvs_planesweep_launch(const float* feats_cl, const float* imgs_cl, const float* proj, const float* depth,
-                          int V, int C, int H, int W, int D, int pad, float* cost, int CP, float* masks,
-                          int with_img, int blocked, void* stream, int* guard = nullptr, const int* run_if = nullptr);
 
 extern "C" int mvsnerf_planesweep_costvar_fwd(const float* feats_cl, const float* imgs_cl, const float* proj, const float* depth,
                                               int V, int C, int H, int W, int D, int pad, float* cost, int CP, float* masks,

@@ -13,6 +13,7 @@
 // wrote one partial result per 1 - 14 output rows (up to 150 MB per layer).
 #include "common.h"
 #include "act.h"
+#include "conv.h"
 
 namespace {
 

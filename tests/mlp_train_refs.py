@@ -140,8 +140,8 @@ def signs_differ(pre_a, pre_b):
 
 
 def psum_depth(n_part, slices=32):
-    """Additions on the longest path of one output of mvsnerf_partial_sum_multi over n_part partials (csrc/act.h:81-98, csrc/encoder.hip:1351-1352):
-    a walk keeps eight running sums, ceil(rows / 8) additions each, folded by a three-level tree (act.h:97); n_part > MVS_RED_SLICES = 32 (act.h:37)
+    """Additions on the longest path of one output of mvsnerf_partial_sum_multi over n_part partials (mvs_psum_walk in csrc/act.h; chunk and slices in
+    mvsnerf_partial_sum_multi, csrc/wgrad3d.hip): a walk keeps eight running sums, ceil(rows / 8) additions each, folded by a three-level tree (its last line); n_part > MVS_RED_SLICES = 32 (act.h)
     walks chunks of ceil(n_part / 32) rows first and then the slices."""
     walk = lambda rows: -(-rows // 8) + 3
     if n_part <= slices:

@@ -44,7 +44,7 @@ def test_c_abi_rejects_bad_arguments_without_launching():
     assert l.mvsnerf_mlp_fwd_guarded(p, p, 20, p, 3, p, 20, p, 3, 0, 1, 0, p, p, 0) == 0                  # empty batch: no launch
     assert l.mvsnerf_sweep_conv0_guarded_fwd(None, 0) == EINVAL
     assert l.mvsnerf_conv0_f16x3_packed_elems(41) == 3 * 7680 + 8
-    assert not hasattr(l, "mvsnerf_tune") and not hasattr(l, "mvsnerf_debug_set_census")     # the library has no A/B switches (csrc/knobs.h: constants)
+    assert not hasattr(l, "mvsnerf_tune") and not hasattr(l, "mvsnerf_debug_set_census")     # the library has no A/B switches: which kernel a shape takes is written in its dispatcher
 
 
 def test_ray_march_rejects_a_guard_without_fp16_planes_before_launching():

@@ -1,10 +1,10 @@
-"""The fp32 family of CostRegNet's 3-D layers (csrc/conv_mfma.hip and the convolution / transposed-convolution / InPlaceABN parts of
-csrc/encoder.hip; reference models.py:674-685, 725-769), layer by layer against float64 on exactly the kernel's fp32 operands: forward and
+"""The fp32 family of CostRegNet's 3-D layers (csrc/conv_mfma.hip and the convolution / transposed-convolution / InPlaceABN kernels of
+csrc/conv3d.hip and csrc/abn.hip; reference models.py:674-685, 725-769), layer by layer against float64 on exactly the kernel's fp32 operands: forward and
 data gradient of every layer through every route encoder._conv / encoder._conv_t can take, the statistics that leave with a launch, the
 InPlaceABN statistics / backward / apply-and-add kernels and the depth-fastest output sum.  Sizes have ragged last tiles in every dimension,
 odd sizes for the strided layers, one single partial tile and one with more than one full tile plus a remainder per tile dimension.
 
-route -> kernel (read against encoder._conv / _conv_t and the dispatchers in encoder.hip / conv_mfma.hip):
+route -> kernel (read against encoder._conv / _conv_t and the dispatchers in conv3d.hip / conv_mfma.hip):
   _conv   packed=pk, one source (plain | _Lazy)   conv1, dgrad of conv11            conv3d_k3_mfma16_kernel<8, 2>          (32 voxels / wave, 4 waves)
                                                   conv3 .. conv6, their s1 dgrads,
                                                   dgrad of conv7 / conv9            conv3d_k3_mfma32_kernel                (32 voxels / workgroup)

@@ -6,7 +6,7 @@ row permutation, rows that add zero, a power-of-two scale of the gradient.  A fl
 exponent changes bits and fails these (tests/test_scatter_det_refs.py shows that a float32 sum of the same products moves in 31-75 % of the elements under
 the permutation used here).  ops.volume_grad_from_gathered_rows - the N-rank path - is held to "the single-call scatter of all rows, divided by world".
 
-mvsnerf_planesweep_costvar_bwd_det (csrc/encoder.hip) accumulates along a column in registers with v_rcp_f32, which a CPU restatement cannot follow bit for
+mvsnerf_planesweep_costvar_bwd_det (csrc/planesweep_bwd.hip) accumulates along a column in registers with v_rcp_f32, which a CPU restatement cannot follow bit for
 bit: property tests only (power-of-two scales of either operand, torch.equal).
 
 Both entries must hand an inf or NaN gradient on to the elements the float-atomic entries hand it to.  The only tolerance in this file is 3e-6 of the largest

@@ -1,5 +1,5 @@
 """Degenerate geometry and tiny shapes for the encode head: the plane sweep (csrc/planesweep.hip, four store layouts), its two backward
-kernels and the stand-alone homo_warp (csrc/encoder.hip), and the image-prep helpers, through the C ABI.  References, geometries and
+kernels (csrc/planesweep_bwd.hip), the stand-alone homo_warp and the image-prep helpers (csrc/encoder_prep.hip), through the C ABI.  References, geometries and
 shapes: tests/sweep_refs.py (checked on the CPU by test_sweep_refs.py).
 
 What is pinned here and nowhere else: a source view whose fp32 sample coordinate is not finite has four zero weights in the sweep and in
@@ -291,7 +291,7 @@ def test_resize_bilinear_both_forms(size_in, size_out, N):
     resize_f64: within 8 u max|src| (six roundings of a convex combination, and weights that sum to 1 + 2u); the channel-last form holds the
     bits of the planar one.  (It did not when this test was written: left to the compiler, the one source expression was contracted differently in
     the two kernels and per channel - 11 of 48 green values at (7, 9) -> (3, 4) differed in the last bit.  Both kernels now share resize_axis /
-    resize_blend in csrc/encoder.hip, every operation spelled out.)"""
+    resize_blend in csrc/encoder_prep.hip, every operation spelled out.)"""
     (Hi, Wi), (Ho, Wo) = size_in, size_out
     L = _lib()
     src = torch.randn((N, 3, Hi, Wi), generator=torch.Generator().manual_seed(Hi * 100 + Wo + N))
